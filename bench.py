@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """Headline benchmark: Monte-Carlo rays/second on benchmark/lensesAndMirrors.
 
-  python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5]
+  python bench.py --gpus N --steps K --warmup W [--config c3|c4|c5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, ms_per_step, ...).
+--full adds everything else the benchmark measures, each after the timed steps: the roofline block (kernel
+times of the timed steps + the committed counter pass), the end-to-end rate with hit rows on the host, the
+CPU baseline, for c3 the c4 and c5 lines under "extra_configs", for c5 the batch launch by itself and the
+notebook-size FWHM.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float64): c3 / c4 the job's detector histogram and counters and a fixed sample of the step's hit rows
+(every k-th row in (ray, bounce) order), c5 the sweep's table.
 
 N > 1 without a launcher: this script starts `python -m torch.distributed.run
 --nproc-per-node N bench.py ...` itself as a CHILD process -- before anything
@@ -59,6 +67,26 @@ CONFIGS = {
                         'calcFwhm of optimize-spotsize.ipynb per radius'),
 }
 N_RADII = 64
+DUMP_ROWS = 1 << 17     # --dump-outputs: hit rows [::max(1, n // DUMP_ROWS)], fewer than 2 * DUMP_ROWS (< 21 MB as float64)
+
+
+def dump_outputs(dirname, arrays):
+  """--dump-outputs: every array as DIR/<name>.npy in float64"""
+  import numpy as np
+  os.makedirs(dirname, exist_ok=True)
+  for name, a in arrays.items():
+    np.save(os.path.join(dirname, name + '.npy'), np.asarray(a, dtype=np.float64))
+
+
+def hit_row_outputs(tr):
+  """a fixed sample of the hit rows in the tracer's list: rows [::max(1, n // DUMP_ROWS)] in (ray index, bounce) order,
+  gathered on the device, as float64 columns (tag split into ray index, group and isEntering)"""
+  import numpy as np
+  rows = tr.deviceHits().thinned(DUMP_ROWS)
+  tag = rows['tag']
+  return {'hits_point': rows['point'], 'hits_direction': rows['direction'], 'hits_power': rows['power'],
+          'hits_ray_index': tag & np.uint64(0xFFFFFFFFFFFF), 'hits_group': (tag >> np.uint64(48)) & np.uint64(0x7FFF),
+          'hits_entering': tag >> np.uint64(63)}
 
 
 def host_cores():
@@ -308,8 +336,9 @@ def run_trace_config(args, cfg_name, cfg, rank, local_rank, world, dist, torch):
     step(-1 - w)
   barrier()
   tr.reset()
-  tr.timingEnable(True)
-  tr.timingRead()
+  if args.full:
+    tr.timingEnable(True)
+    tr.timingRead()
   barrier()
   t0 = time.perf_counter()
   for s in range(args.steps):
@@ -319,7 +348,7 @@ def run_trace_config(args, cfg_name, cfg, rank, local_rank, world, dist, torch):
     parallel.reduceResults(tr, dist, torch)
   barrier()
   dt = time.perf_counter() - t0
-  kernel_ms, launches = tr.timingRead()
+  kernel_ms, launches = tr.timingRead() if args.full else (0.0, 0)
 
   if dist is not None:
     t = torch.tensor([dt], dtype=torch.float64, device='cpu' if REHEARSE else 'cuda')
@@ -339,12 +368,19 @@ def run_trace_config(args, cfg_name, cfg, rank, local_rank, world, dist, torch):
       np.savez(args.dump_results, hist=hist, counters=np.array([cnt[k] for k in sorted(cnt)], dtype=np.int64),
                names=np.array(sorted(cnt)))
     assert args.no_histogram or hist_total + cnt['hist_overflow'] == cnt['recorded_hits'], (hist_total, cnt)
+    if args.dump_outputs:
+      # the job's histogram and counters (all timed steps, after the reduce) and a sample of the last step's hit rows
+      arrays = {'counters': [cnt[k] for k in sorted(cnt)]}
+      if not args.no_histogram:
+        arrays['histogram'] = hist
+      if record_hits:
+        arrays.update(hit_row_outputs(tr))
+      dump_outputs(args.dump_outputs, arrays)
     kbar = cnt['segments'] / cnt['traced_rays']
     hbar = cnt['recorded_hits'] / cnt['traced_rays']
     bytes_per_ray = kbar * 2 * RAY_STATE_BYTES + hbar * HIT_BYTES
     avg_kernel_s = kernel_ms / 1e3 / max(1, launches)
     kernel_name = 'odw_spec_kernel' if compiled['mode'] else cfg['kernel']
-    pmc = pmc_figures(cfg_name, n_per, record_hits, kernel_name)
     out = {
         'metric': 'Monte-Carlo rays/sec (whole node), lensesAndMirrors.FCStd' if cfg_name == 'c3'
                   else f'Monte-Carlo rays/sec (whole node), {cfg["scene"]}.FCStd',
@@ -359,11 +395,13 @@ def run_trace_config(args, cfg_name, cfg, rank, local_rank, world, dist, torch):
                                       'note': 'hiprtc compile of the ray loop against the scene, before the timed region',
                                       **({'error': compiled['error']} if 'error' in compiled else {})},
                    'parallelism': f'ray-index sharding x{world}, one RCCL reduce'},
-        'roofline': roofline_block(kernel_name, avg_kernel_s, n_per, bytes_per_ray, pmc),
     }
-    if world == 1 and record_hits and cfg_name == 'c3' and not args.no_end_to_end:
+    if args.full:
+      pmc = pmc_figures(cfg_name, n_per, record_hits, kernel_name)
+      out['roofline'] = roofline_block(kernel_name, avg_kernel_s, n_per, bytes_per_ray, pmc)
+    if args.full and world == 1 and record_hits and cfg_name == 'c3' and not args.no_end_to_end:
       out['end_to_end'] = end_to_end(tr, n_per, max(2, args.steps))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline(proj, det)
   tr.close()
   return out
@@ -438,9 +476,10 @@ def run_sweep_config(args, cfg, rank, local_rank, world, dist, torch):
 
   def contexts():       # the tracer and the contexts the sweep keeps beside it (groups of radii take turns on them)
     return [tr] + list(getattr(tr, '_sweepLanes', None) or [])
-  for t in contexts():
-    t.timingEnable(True)
-    t.timingRead()
+  if args.full:
+    for t in contexts():
+      t.timingEnable(True)
+      t.timingRead()
   barrier()
   t0 = time.perf_counter()
   for _ in range(args.steps):
@@ -449,20 +488,32 @@ def run_sweep_config(args, cfg, rank, local_rank, world, dist, torch):
   dt = time.perf_counter() - t0
   # trace kernels of this rank, all contexts: a launch traces a GROUP of radii (batch launches); per radius = per 1e7 rays
   kernel_ms, launches = 0.0, 0
-  for t in contexts():
-    ms, n = t.timingRead()
-    kernel_ms += ms
-    launches += n
+  if args.full:
+    for t in contexts():
+      ms, n = t.timingRead()
+      kernel_ms += ms
+      launches += n
   radii_of_rank = len(sweep.shareOfRank(len(radii), rank, world)) * args.steps
   if dist is not None:
     t = torch.tensor([dt], dtype=torch.float64, device='cpu' if REHEARSE else 'cuda')
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+  if rank == 0 and args.dump_outputs:
+    # the table of the last sweep (all radii, after its all-reduce) and the rows [::n // 1000] rank 0 kept of its radii
+    kept = sorted(res.samples)
+    arrays = {'radii': res.values, 'traced_rays': [res.tracedRays], 'recorded_hits': [res.recordedHits],
+              'segments': [res.segments]}
+    arrays.update({name: col for name, col in res.columns.items()})
+    if kept:
+      arrays['sample_radius_index'] = np.concatenate([np.full(len(res.samples[k]['points']), k) for k in kept])
+      for key in ('points', 'directions', 'powers', 'isEntering'):
+        arrays['sample_' + key] = np.concatenate([res.samples[k][key] for k in kept])
+    dump_outputs(args.dump_outputs, arrays)
   # the batch launch by itself (after the timed region, nothing else on the GPU): one launch of up to 16 radii, three times,
   # the last two timed -- inside a sweep the kernel shares the GPU with the post-hoc chains of other groups, which stretches
   # its own time; `frac_kernel_alone` is the same instruction count against this time
   solo_ms = None
-  if rank == 0:
+  if rank == 0 and args.full:
     try:
       ks = radii[:min(16, len(radii))]
       prs = []
@@ -483,7 +534,7 @@ def run_sweep_config(args, cfg, rank, local_rank, world, dist, torch):
       print(f'[bench] the solo batch launch failed: {e}', file=sys.stderr)
   # the notebook's figure of merit on the notebook's sample size: calcFwhm of the ~1000 thinned rows per radius the
   # last sweep kept (host arithmetic of 64 small clouds, after the timed region; one more all-reduce of the column)
-  fwhm_1e3 = sweep.fwhmOfSamples(res, dist=dist, device=local_rank)
+  fwhm_1e3 = sweep.fwhmOfSamples(res, dist=dist, device=local_rank) if args.full else None
   out = None
   if rank == 0:
     total_rays = n_per * len(radii) * args.steps
@@ -494,7 +545,6 @@ def run_sweep_config(args, cfg, rank, local_rank, world, dist, torch):
     avg_kernel_s = kernel_ms / 1e3 / max(1, radii_of_rank)        # per radius (a launch holds several)
     info = tr.compiledInfo()             # the kernel the last radius ran
     kernel_name = 'odw_spec_kernel' if info['mode'] == 1 else cfg['kernel']
-    pmc = pmc_figures('c5', n_per, True, kernel_name)
     best_r, best_f = res.best('fwhm') if np.isfinite(res.columns['fwhm']).any() else (float('nan'), float('nan'))
     rms_r, rms_v = res.best('rms')
     out = {
@@ -516,26 +566,29 @@ def run_sweep_config(args, cfg, rank, local_rank, world, dist, torch):
                                               'skips such azimuth bins): with 1e7 hits the innermost radial bins are '
                                               'flat near the focus; the rms spot radius below stays defined',
                                  'rms_spot_mm': [float(v) for v in res.columns['rms']],
-                                 'best_radius_by_rms_mm': rms_r, 'best_rms_spot_mm': rms_v,
-                                 'fwhm_1e3_mm': [None if np.isnan(v) else float(v) for v in fwhm_1e3],
-                                 'best_radius_by_fwhm_1e3_mm': float(radii[int(np.nanargmin(fwhm_1e3))]) if np.isfinite(fwhm_1e3).any() else None,
-                                 'fwhm_1e3_at_best_mm': float(np.nanmin(fwhm_1e3)) if np.isfinite(fwhm_1e3).any() else None,
-                                 'fwhm_1e3_note': 'calcFwhm on points[::n // 1000] of every radius (the ~1e3 hits per run the notebook '
-                                                  'itself traces, cell 9): the estimator in its own regime; the rows are gathered '
-                                                  'inside the timed sweep, the 64 small fits run after it'}},
-        'roofline': roofline_block(kernel_name, avg_kernel_s, n_per, bytes_per_ray, pmc,
-                                   note=f'trace kernels of rank 0: {launches} batch launches for {radii_of_rank} radii, kernel time per radius '
-                                        '(1e7 rays), the ray pass of the launch included, measured while the post-hoc kernels of other groups share the GPU (the batch '
-                                        'kernel by itself: kernel_alone_ms / frac_kernel_alone); per step the host '
-                                        'also re-bakes the scenes and searches the detector plane per radius'),
+                                 'best_radius_by_rms_mm': rms_r, 'best_rms_spot_mm': rms_v}},
     }
+    if args.full:
+      out['config']['spot_size'].update({
+          'fwhm_1e3_mm': [None if np.isnan(v) else float(v) for v in fwhm_1e3],
+          'best_radius_by_fwhm_1e3_mm': float(radii[int(np.nanargmin(fwhm_1e3))]) if np.isfinite(fwhm_1e3).any() else None,
+          'fwhm_1e3_at_best_mm': float(np.nanmin(fwhm_1e3)) if np.isfinite(fwhm_1e3).any() else None,
+          'fwhm_1e3_note': 'calcFwhm on points[::n // 1000] of every radius (the ~1e3 hits per run the notebook '
+                           'itself traces, cell 9): the estimator in its own regime; the rows are gathered '
+                           'inside the timed sweep, the 64 small fits run after it'})
+      pmc = pmc_figures('c5', n_per, True, kernel_name)
+      out['roofline'] = roofline_block(kernel_name, avg_kernel_s, n_per, bytes_per_ray, pmc,
+                                       note=f'trace kernels of rank 0: {launches} batch launches for {radii_of_rank} radii, kernel time per radius '
+                                            '(1e7 rays), the ray pass of the launch included, measured while the post-hoc kernels of other groups share the GPU (the batch '
+                                            'kernel by itself: kernel_alone_ms / frac_kernel_alone); per step the host '
+                                            'also re-bakes the scenes and searches the detector plane per radius')
     if solo_ms:
       rf = out['roofline']
       rf['kernel_alone_ms'] = solo_ms
       rf['kernel_alone_note'] = 'one batch launch of up to 16 radii with nothing else on the GPU, per radius, after the timed region'
       if rf.get('frac') is not None:
         rf['frac_kernel_alone'] = rf['frac'] * rf['avg_kernel_ms'] / solo_ms
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
       proj = scenes.bakeProject(doc)
       out['cpu_baseline'] = cpu_baseline(proj, None, seconds=8.0)
   tr.close()
@@ -559,7 +612,12 @@ def main():
   ap.add_argument('--no-histogram', action='store_true', help='hit rows only (diagnostic, not the metric)')
   ap.add_argument('--dump-results', default=None, help='c3 / c4: rank 0 writes the job\'s histogram and counters (after the reduce) to this .npz')
   ap.add_argument('--no-extra', action='store_true',
-                  help='c3 only: leave out the c4 (3 steps) and c5 (4 sweeps) lines nested under "extra_configs"')
+                  help='c3 --full: leave out the c4 (3 steps) and c5 (4 sweeps) lines nested under "extra_configs"')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='rank 0 writes what the last timed step computed to DIR/<name>.npy (float64, < 64 MB in all)')
+  ap.add_argument('--full', action='store_true',
+                  help='also measure what the headline does not need, after the timed steps: roofline, end-to-end rate, CPU '
+                       'baseline, c3: the c4 / c5 lines under "extra_configs", c5: the solo batch launch and the 1e3-row FWHM')
   args = ap.parse_args()
   cfg = CONFIGS[args.config]
   if args.steps is None:
@@ -599,7 +657,7 @@ def main():
     out = run_sweep_config(args, cfg, rank, local_rank, world, dist, torch)
   else:
     out = run_trace_config(args, args.config, cfg, rank, local_rank, world, dist, torch)
-  if args.config == 'c3' and world == 1 and not args.no_extra and not args.no_hits and not args.rays_per_step:
+  if args.full and args.config == 'c3' and world == 1 and not args.no_extra and not args.no_hits and not args.rays_per_step:
     # the other two GPU configs of BASELINE.json in the same driver-timed record: c4 (hugeArray, 3 steps) and
     # c5 (the radius sweep, 4 sweeps after 2 untimed ones: the first sweep after the contexts are set up runs ~10 % slower than the
     # steady state, and single sweeps vary box to box), each measured exactly like its own `--config` line
@@ -610,6 +668,7 @@ def main():
       sub = copy.copy(args)
       sub.config, sub.steps, sub.warmup = name, steps, warmup
       sub.no_cpu_baseline = sub.no_end_to_end = True
+      sub.dump_outputs = None
       try:
         if name == 'c5':
           line = run_sweep_config(sub, CONFIGS[name], rank, local_rank, world, dist, torch)

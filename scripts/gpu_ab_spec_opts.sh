@@ -5,7 +5,7 @@ cd "$GRAFT_REPO_ROOT"
 cfg=$1; shift
 for round in 1 2; do
   for o in "$@"; do
-    ODW_SPEC_OPTS="$o" timeout -k 10 200 python bench.py --config $cfg --no-extra --no-cpu-baseline --no-end-to-end 2>/dev/null | python -c "
+    ODW_SPEC_OPTS="$o" timeout -k 10 200 python bench.py --config $cfg --no-extra --no-cpu-baseline --no-end-to-end --full 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$o', round(d['ms_per_step'],3), 'ms/step', round(d['roofline']['avg_kernel_ms'],3), 'kernel ms', d['roofline']['kernel'])"
   done
 done

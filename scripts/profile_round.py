@@ -3,7 +3,7 @@
 
   python scripts/profile_round.py r02_c3 [--config c3|c4] [--no-bench]
 
-1. `python bench.py --config C`                                      -> gpurun_out/<tag>_bench.json
+1. `python bench.py --config C --full`                               -> <tag>_bench.json in the output folder
 2. `rocprofv3 --kernel-trace --stats -- python3 bench.py --config C --steps 16 --warmup 4` -> <tag>_kernel_stats.csv
 3. `rocprofv3 --pmc <set> --kernel-trace -- python3 bench.py ...`    -> <tag>_pmc.json, one run per counter set
    (FETCH_SIZE and WRITE_SIZE alone, as MI355X_MICROARCH.md prescribes; no trace domains besides
@@ -46,7 +46,7 @@ env = dict(os.environ, TMPDIR='/tmp')
 C5_RADII, C5_SWEEPS = 64, 2
 KERNELS = [KERNEL_NAME] + (['odw_batch_rays_kernel'] if args.config == 'c5' and not args.script else [])
 BENCH = ['python3', os.path.join(ROOT, 'bench.py'), '--config', args.config, '--steps', '1' if args.config == 'c5' else '3', '--warmup', '1',
-         '--no-cpu-baseline', '--no-end-to-end', '--no-extra']
+         '--no-cpu-baseline', '--no-end-to-end', '--no-extra', '--full']
 if args.script:
   import shlex
   BENCH = ['python3', os.path.join(ROOT, args.script)] + shlex.split(args.script_args)
@@ -71,7 +71,7 @@ def tables(con):
 
 # 1. the bench line
 if not args.no_bench:
-  res = subprocess.run(['python3', os.path.join(ROOT, 'bench.py'), '--config', args.config, '--no-extra'], cwd=ROOT, env=env,
+  res = subprocess.run(['python3', os.path.join(ROOT, 'bench.py'), '--config', args.config, '--no-extra', '--full'], cwd=ROOT, env=env,
                        capture_output=True, text=True, check=True)
   line = [l for l in res.stdout.splitlines() if l.startswith('{')][-1]
   open(os.path.join(out, f'{tag}_bench.json'), 'w').write(line + '\n')

@@ -146,13 +146,13 @@ def test_bench_under_a_launcher_with_one_rank_uses_rccl(native_lib):
 
 
 def test_bench_config_lines_c4_and_c5(native_lib):
-  out = _line(_bench('--config', 'c4', '--steps', '2', '--warmup', '1', '--rays-per-step', '4e6', '--no-cpu-baseline'))
+  out = _line(_bench('--config', 'c4', '--steps', '2', '--warmup', '1', '--rays-per-step', '4e6', '--no-cpu-baseline', '--full'))
   assert out['config']['name'] == 'c4' and 'hugeArray' in out['metric'] and out['n_gpus'] == 1
   assert 2.5 < out['config']['segments_per_ray'] < 3.2 and out['roofline']['kernel'].startswith('odw_grid_kernel')
   # (a reduced workload has no committed counter pass: the instruction-issue fraction is not computed for it)
   assert out['roofline']['bound'] == 'valu_issue' and out['roofline']['frac'] is None
   assert 0 < out['roofline']['wavefront_equivalent_frac'] < 1
-  out = _line(_bench('--config', 'c5', '--radii', '6', '--rays-per-step', '2e5', '--no-cpu-baseline'))
+  out = _line(_bench('--config', 'c5', '--radii', '6', '--rays-per-step', '2e5', '--no-cpu-baseline', '--full'))
   spot = out['config']['spot_size']
   assert out['config']['name'] == 'c5' and out['scaling'] == 'strong' and len(spot['fwhm_mm']) == 6
   assert all(v is None or v > 0 for v in spot['fwhm_mm']) and any(v is not None for v in spot['fwhm_mm'])
@@ -163,10 +163,10 @@ def test_bench_config_lines_c4_and_c5(native_lib):
 
 
 def test_default_bench_line_carries_the_three_gpu_configs(native_lib):
-  """the driver's command (`python bench.py`, here with fewer steps): the c3 headline with a roofline that is a
+  """the driver's command with --full (`python bench.py --full`, here with fewer steps): the c3 headline with a roofline that is a
   bound -- calibrated VALU issue, no fraction above 1 -- and c4 / c5 nested under `extra_configs`, each with its
   own roofline block (profiles/pmc_current.json holds counters for exactly these workloads)"""
-  out = _line(_bench('--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-end-to-end'))
+  out = _line(_bench('--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-end-to-end', '--full'))
   assert out['config']['name'] == 'c3' and out['n_gpus'] == 1 and out['value'] > 5e9
   lines = dict(c3=out, **out['extra_configs'])
   assert set(lines) == {'c3', 'c4', 'c5'}
@@ -198,6 +198,37 @@ def test_default_bench_line_carries_the_three_gpu_configs(native_lib):
   assert 9.7 <= out['config']['c5_best_radius_by_fwhm_1e3_mm'] <= 10.3
 
 
+def test_plain_bench_line_and_dumped_outputs(native_lib, tmp_path):
+  """a plain run (no --full) times --steps steps and reports the headline only; --dump-outputs writes the same arrays in
+  two runs of the same arguments: the job's histogram and counters, a fixed sample of the last step's hit rows"""
+  import bench
+  from freecad.optics_design_workbench_amd._native import CNT_NAMES
+  small = ['--steps', '3', '--warmup', '1', '--rays-per-step', '2e6']
+  runs = []
+  for k in range(2):
+    d = tmp_path / f'run{k}'
+    out = _line(_bench(*small, '--dump-outputs', str(d)))
+    assert out['steps'] == 3 and out['value'] * out['ms_per_step'] * 1e-3 == pytest.approx(2e6, rel=1e-6)
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+      assert key in out, key
+    assert not {'roofline', 'extra_configs', 'cpu_baseline', 'end_to_end'} & set(out)
+    runs.append({f.name[:-4]: np.load(f) for f in d.iterdir()})
+  a, b = runs
+  assert set(a) >= {'histogram', 'counters', 'hits_point', 'hits_direction', 'hits_power', 'hits_ray_index'}
+  assert sum(v.nbytes for v in a.values()) < 64 << 20 and all(v.dtype == np.float64 for v in a.values())
+  names = sorted(CNT_NAMES)
+  assert a['counters'][names.index('traced_rays')] == 3 * 2e6 and a['histogram'].sum() > 0
+  assert 0 < len(a['hits_point']) < 2 * bench.DUMP_ROWS and np.all(np.diff(a['hits_ray_index']) >= 0)
+  for name in a:
+    assert np.array_equal(a[name], b[name]), name
+  # c5: the sweep's table
+  d = tmp_path / 'c5'
+  out = _line(_bench('--config', 'c5', '--radii', '4', '--rays-per-step', '1e5', '--dump-outputs', str(d)))
+  assert out['steps'] == 1 and 'roofline' not in out and 'fwhm_1e3_mm' not in out['config']['spot_size']
+  assert np.load(d / 'radii.npy').tolist() == np.linspace(9, 11, 4).tolist()
+  assert np.load(d / 'rms.npy').tolist() == out['config']['spot_size']['rms_spot_mm']
+
+
 @two_ranks
 def test_bench_on_two_gpus_reports_two_gpus(native_lib):
   """`bench.py --gpus 2` (starts its two ranks itself): n_gpus 2, twice the rays, counters and histogram of the whole
@@ -210,7 +241,7 @@ def test_bench_on_two_gpus_reports_two_gpus(native_lib):
   assert two['value'] > 1.2 * one['value'] * 0.5          # (no scaling claim here: the driver measures that)
   c4 = _line(_bench('--gpus', '2', '--config', 'c4', *small[:6], '--no-cpu-baseline'))
   assert c4['n_gpus'] == 2 and c4['config']['name'] == 'c4'
-  args = ['--config', 'c5', '--radii', '6', '--rays-per-step', '2e5', '--no-cpu-baseline']
+  args = ['--config', 'c5', '--radii', '6', '--rays-per-step', '2e5', '--no-cpu-baseline', '--full']
   t1 = _line(_bench('--gpus', '1', *args))['config']['spot_size']
   t2 = _line(_bench('--gpus', '2', *args))
   assert t2['n_gpus'] == 2 and t2['scaling'] == 'strong'
@@ -264,7 +295,7 @@ def test_c4_on_eight_gpus_equals_the_sum_of_eight_shards(native_lib, tmp_path):
 def test_c5_on_eight_gpus_equals_one_gpu(native_lib):
   """`bench.py --gpus 8 --config c5` (64 radii x 1e7 rays, eight radii per rank, one all-reduce of the table): the
   table of spot sizes is the 1-rank table bit for bit"""
-  args = ['--config', 'c5', '--steps', '1', '--warmup', '0', '--no-cpu-baseline']
+  args = ['--config', 'c5', '--steps', '1', '--warmup', '0', '--no-cpu-baseline', '--full']
   t8 = _line(_bench('--gpus', '8', *args, timeout=1500))
   t1 = _line(_bench('--gpus', '1', *args, timeout=1500))
   assert t8['n_gpus'] == 8 and t8['scaling'] == 'strong' and t8['config']['radii'] == 64
@@ -370,7 +401,7 @@ def test_rehearsal_four_ranks_on_one_gpu_equal_the_sum_of_their_shards(native_li
   assert [int(v) for v in job['counters']] == [cnt[k] for k in sorted(cnt)]
   assert np.array_equal(job['hist'].astype(np.int64), hist)
   # the sweep dealt out over three ranks: the 1-rank table bit for bit
-  args = ['--config', 'c5', '--radii', '7', '--rays-per-step', '2e5', '--no-cpu-baseline']
+  args = ['--config', 'c5', '--radii', '7', '--rays-per-step', '2e5', '--no-cpu-baseline', '--full']
   t1 = _line(_bench('--gpus', '1', *args))['config']['spot_size']
   t3 = _line(_bench('--gpus', '3', *args, env=env))
   assert t3['n_gpus'] == 3 and t3['scaling'] == 'strong' and 'rehearsal' in t3
@@ -420,7 +451,7 @@ def test_rehearsal_four_ranks_c4_and_the_whole_sweep(native_lib, tmp_path):
   if hist is not None:
     assert np.array_equal(job['hist'].astype(np.int64), hist)
   # the whole sweep (64 radii) over four ranks: sixteen values each, one all-reduce of the table
-  args = ['--config', 'c5', '--rays-per-step', '1e5', '--no-cpu-baseline']
+  args = ['--config', 'c5', '--rays-per-step', '1e5', '--no-cpu-baseline', '--full']
   t1 = _line(_bench('--gpus', '1', *args))
   t4 = _line(_bench('--gpus', '4', *args, env=env))
   assert t4['n_gpus'] == 4 and t4['scaling'] == 'strong' and 'rehearsal' in t4 and t4['config']['radii'] == 64

@@ -69,10 +69,10 @@ def test_errors(tmp_path):
 
 def test_reference_document_loads():
   """test/50-old-tests/replay.FCStd's source object is recognised (its
-  ReplayFromDir points into the author's home directory)"""
-  ref = '/root/reference/test/50-old-tests/replay.FCStd'
-  if not os.path.exists(ref):
-    pytest.skip('reference not mounted')
+  ReplayFromDir points into the author's home directory; the stored fixture
+  tests/golden/scenes/replay.FCStd keeps that document's objects)"""
+  from conftest import SCENES
+  ref = os.path.join(SCENES, 'replay.FCStd')
   from freecad.optics_design_workbench_amd.scene import open_fcstd
   doc = open_fcstd(ref)
   (src,) = bake.lightSources(doc)
