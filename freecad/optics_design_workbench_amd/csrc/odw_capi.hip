@@ -77,7 +77,7 @@ struct odw_ctx {
   // host copies needed for lazy (re)builds
   std::vector<double> h_prim_f64;
   std::vector<int32_t> h_prim_i32;
-  std::vector<int32_t> h_cond;            // prim | inside << 31
+  std::vector<int32_t> h_cond;            // prim | opens a clause << 30 | inside << 31
   std::vector<double> h_prim_hdr;         // 64-byte headers (boxes + the four integers), built with the BVH
   std::vector<char> h_dead;               // primitives no ray can meet (no face, or an empty box)
   std::vector<double> h_group_f64, h_group_gdir;
@@ -992,16 +992,31 @@ void compute_boxes(odw_ctx* ctx, std::vector<Box>& boxes, std::vector<char>& dea
   // Primitives without faces (pure operands) and faces that cannot exist get a box no ray meets.
   std::vector<Box> full = boxes;
   dead.assign(n, 0);
+  // A trimming list of several clauses bounds the face by the UNION over its clauses of (own box ^ that clause's
+  // must-be-inside operands): a literal of one clause alone does not bound it.  One clause: the cut as it always was.
   for (int p = 0; p < n; ++p) {
     const int cw = ctx->h_prim_i32[4 * p + 3], off = cw & 0xffffff, cnt = (cw >> 24) & 0xff;
-    for (int c = off; c < off + cnt && c < (int)ctx->h_cond.size(); ++c) {
-      if (ctx->h_cond[c] >= 0) continue;                       // must be OUTSIDE that one: no bound
-      const Box& o = full[ctx->h_cond[c] & 0x7fffffff];
-      for (int a = 0; a < 3; ++a) {
-        boxes[p].lo[a] = std::max(boxes[p].lo[a], o.lo[a]);
-        boxes[p].hi[a] = std::min(boxes[p].hi[a], o.hi[a]);
+    const int end = std::min(off + cnt, (int)ctx->h_cond.size());
+    Box u;
+    u.reset();
+    int clauses = 0;
+    for (int c0 = off; c0 < end;) {
+      int c1 = c0 + 1;
+      while (c1 < end && !cond_opens(ctx->h_cond[c1])) ++c1;
+      Box b = full[p];
+      for (int c = c0; c < c1; ++c) {
+        if (ctx->h_cond[c] >= 0) continue;                     // must be OUTSIDE that one: no bound
+        const Box& o = full[cond_operand(ctx->h_cond[c])];
+        for (int a = 0; a < 3; ++a) {
+          b.lo[a] = std::max(b.lo[a], o.lo[a]);
+          b.hi[a] = std::min(b.hi[a], o.hi[a]);
+        }
       }
+      if (clauses++ == 0) boxes[p] = b;                        // (an empty first clause stays empty unless another grows it)
+      if (b.lo[0] <= b.hi[0] && b.lo[1] <= b.hi[1] && b.lo[2] <= b.hi[2]) u.grow(b);
+      c0 = c1;
     }
+    if (clauses > 1 && u.lo[0] <= u.hi[0]) boxes[p] = u;
     const int facemask = (ctx->h_prim_i32[4 * p + 2] >> ODW_FACEMASK_SHIFT) & 0xff;
     dead[p] = facemask == 0 || boxes[p].lo[0] > boxes[p].hi[0] || boxes[p].lo[1] > boxes[p].hi[1] ||
               boxes[p].lo[2] > boxes[p].hi[2];
@@ -1751,6 +1766,22 @@ void odw_destroy(odw_ctx* ctx) {
   delete ctx;
 }
 
+// a condition as the kernels read it (odw_device.h: cond_operand, cond_opens, the sign = must be inside)
+static int32_t pack_cond(int32_t prim, int32_t inside) {
+  return (int32_t)((uint32_t)prim | ((uint32_t)(inside >> 1) & 1u) << 30 | ((uint32_t)inside & 1u) << 31);
+}
+
+// every list that opens a clause after its first word opens one with its first word too (offsets already checked)
+static bool clauses_marked(const int32_t* cond_off, int n, const std::vector<int32_t>& cond) {
+  for (int p = 0; p < n; ++p) {
+    const int off = cond_off[p], end = cond_off[p + 1];
+    if (end <= off || cond_opens(cond[off])) continue;
+    for (int c = off + 1; c < end; ++c)
+      if (cond_opens(cond[c])) return false;
+  }
+  return true;
+}
+
 // host half of odw_upload_scene: validation and the host copies of every table (no device call)
 static int scene_host_tables(odw_ctx* ctx, const odw_scene_desc* s) {
   if (!ctx || !s) return fail(ctx, ODW_ERR_INVALID, "odw_upload_scene: null argument");
@@ -1823,11 +1854,16 @@ static int scene_host_tables(odw_ctx* ctx, const odw_scene_desc* s) {
   }
   std::vector<int32_t> cond((size_t)std::max(1, s->n_conds), 0);
   for (int c = 0; c < s->n_conds; ++c) {
-    if (s->cond_prim[c] < 0 || s->cond_prim[c] >= n) return fail(ctx, ODW_ERR_INVALID, "condition primitive out of range");
+    if (s->cond_prim[c] < 0 || s->cond_prim[c] >= n || s->cond_prim[c] >= (1 << 30))
+      return fail(ctx, ODW_ERR_INVALID, "condition primitive out of range");
     if (s->prim_type[s->cond_prim[c]] == ODW_PRIM_TRIANGLE)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "trimming against a triangle (no inside/outside of a facet)");
-    cond[c] = s->cond_prim[c] | (s->cond_inside[c] ? (int32_t)0x80000000 : 0);
+    if (s->cond_inside[c] < 0 || s->cond_inside[c] > 3)
+      return fail(ctx, ODW_ERR_INVALID, "cond_inside: bit 0 inside, bit 1 opens a clause; nothing else");
+    cond[c] = pack_cond(s->cond_prim[c], s->cond_inside[c]);
   }
+  if (!clauses_marked(s->prim_cond_off, n, cond))
+    return fail(ctx, ODW_ERR_INVALID, "a trimming list of several clauses must mark its first condition too");
   ctx->h_cond = cond;
   std::vector<double> gf(ODW_MAX_GROUPS * 4, 0.0), gd(ODW_MAX_GROUPS * 3, 0.0);
   std::vector<int32_t> gi(ODW_MAX_GROUPS * 4, 0);
@@ -2210,10 +2246,15 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   }
   std::vector<int32_t> cond((size_t)std::max(1, s->n_conds), 0);
   for (int c = 0; c < s->n_conds; ++c) {
-    if (s->cond_prim[c] < 0 || s->cond_prim[c] >= n || s->prim_type[s->cond_prim[c]] == ODW_PRIM_TRIANGLE)
+    if (s->cond_prim[c] < 0 || s->cond_prim[c] >= n || s->cond_prim[c] >= (1 << 30) ||
+        s->prim_type[s->cond_prim[c]] == ODW_PRIM_TRIANGLE)
       return fail(ctx, ODW_ERR_INVALID, "surface source: condition primitive out of range");
-    cond[c] = s->cond_prim[c] | (s->cond_inside[c] ? (int32_t)0x80000000 : 0);
+    if (s->cond_inside[c] < 0 || s->cond_inside[c] > 3)
+      return fail(ctx, ODW_ERR_INVALID, "surface source: cond_inside: bit 0 inside, bit 1 opens a clause; nothing else");
+    cond[c] = pack_cond(s->cond_prim[c], s->cond_inside[c]);
   }
+  if (!clauses_marked(s->prim_cond_off, n, cond))
+    return fail(ctx, ODW_ERR_INVALID, "surface source: a trimming list of several clauses must mark its first condition too");
   static const int n_faces_of[7] = {6, 1, 3, 3, 1, 1, 0};     // (paraboloid faces do not emit: rejected below)
   std::vector<int32_t> fi((size_t)s->n_faces * 2);
   std::vector<double> fc((size_t)s->n_faces + 1, 0.0);

@@ -6,7 +6,9 @@
 //               tolerance for u, v, u+v; unused)
 //   prim_hdr : n_prims x 64 B     global bounding box (6 f64) + type, group, flags, conds (4 i32)
 //   prim_i32 : n_prims x 4  i32   type, group, flags|facemask<<8, cond_off|cnt<<24
-//   cond_i32 : n_conds      i32   prim | inside<<31
+//   cond_i32 : n_conds      i32   prim | opens_clause<<30 | inside<<31 (cond_operand / cond_opens below: a list is one
+//                                 clause, or several whose first words -- every one's -- carry bit 30; the
+//                                 candidate is kept if any clause holds)
 //   group_f64: 64 x 4 f64         ior, reflectivity, absorption length, grating lpm
 //   group_i32: 64 x 4 i32         optical type, record, grating type, grating order
 //   cdf tables: interleaved (cdf, edge) f64 pairs per knot, one 16-B load each
@@ -48,6 +50,10 @@ namespace odw {
 // tolerance rules accept lies in its solid's box): the next segment tests this solid's primitives only, and
 // falls back to all of them in the one case that finds nothing (a hit within distTol beyond an edge).
 #define ODW_FLAG_ISOLATED 0x4
+
+// a trimming condition word: the primitive it tests, whether it opens a clause (bit 31, the sign, is "must be inside")
+__host__ __device__ __forceinline__ constexpr int cond_operand(int cw) { return cw & 0x3fffffff; }
+__host__ __device__ __forceinline__ constexpr bool cond_opens(int cw) { return (cw & 0x40000000) != 0; }
 
 struct d3 {
   double x, y, z;

@@ -434,33 +434,66 @@ __device__ __forceinline__ void consider(const SceneView& sv, Query& q, double t
   if (!cand_any && !cand_oth) return;
   if (cond_cnt) {
     const d3 gp = q.start + q.dn * t;
+    // (a list of several clauses marks the first word of each, its first word included: `dnf` is wave-uniform.
+    //  A plain conjunction returns at its first failing literal as it always did; in a list of clauses the lanes
+    //  whose clause failed sit out the rest of it and take up the next -- `c` stays the same for every lane, the
+    //  table loads stay scalar)
+    const bool dnf = cond_opens(sv.cond_i32[cond_off]);
+    bool held = true;                             // every literal of the clause being read held so far
     for (int c = cond_off; c < cond_off + cond_cnt; ++c) {
       const int cw = sv.cond_i32[c];
-      const int qp = cw & 0x7fffffff;
+      if (dnf && c != cond_off && cond_opens(cw)) {
+        if (held) break;                          // the clause before held: keep the candidate
+        held = true;
+      }
+      if (!held) continue;
+      const int qp = cond_operand(cw);
       cf64 pf = sv.prim_f64 + (size_t)qp * 16;
       const double sd = prim_sdist<PARAB>(sv.prim_i32[4 * qp], pf + 12, xf_point(pf, gp));
-      if (cw < 0) { if (sd > q.tol) return; }     // must be inside
-      else { if (sd < -q.tol) return; }           // must be outside
+      if (cw < 0 ? sd > q.tol : sd < -q.tol) {    // must be inside / must be outside
+        if (!dnf) return;
+        held = false;
+      }
     }
+    if (!held) return;                            // (the last clause failed too)
   }
   if (cand_any) { q.any.t = t; q.any.prim = p; q.any.face = face; }
   if (cand_oth) { q.oth.t = t; q.oth.prim = p; q.oth.face = face; }
 }
 
 // the same for primitive PI of a compiled scene: group and trimming list are constants, the list is
-// unrolled, every operand's frame product skips its zero terms
+// unrolled, every operand's frame product skips its zero terms.  trim_all: the literals C..END-1 (one clause)
 template <bool PARAB, class SPEC, int C, int END>
-__device__ __forceinline__ bool trim_ok(const SceneView& sv, const Query& q, d3 gp) {
+__device__ __forceinline__ bool trim_all(const SceneView& sv, const Query& q, d3 gp) {
   if constexpr (C >= END) {
     return true;
   } else {
     constexpr int cw = SPEC::cond(C);
-    constexpr int qp = cw & 0x7fffffff;
+    constexpr int qp = cond_operand(cw);
     cf64 pf = sv.prim_f64 + (size_t)qp * 16;
     const double sd = prim_sdist<PARAB>(SPEC::type(qp), pf + 12, xf_point_nz<SPEC::xf(qp)>(pf, gp));
     if (cw < 0) { if (sd > q.tol) return false; }     // must be inside
     else { if (sd < -q.tol) return false; }           // must be outside
-    return trim_ok<PARAB, SPEC, C + 1, END>(sv, q, gp);
+    return trim_all<PARAB, SPEC, C + 1, END>(sv, q, gp);
+  }
+}
+// end of the clause that begins at C: the next word that opens one, or END
+template <class SPEC>
+__host__ __device__ constexpr int clause_end(int c, int end) {
+  int e = c + 1;
+  while (e < end && !cond_opens(SPEC::cond(e))) ++e;
+  return e;
+}
+// the list C..END-1: an OR of unrolled ANDs, resolved at compile time, left at the first clause that holds (a plain
+// conjunction is one clause: trim_all of the whole list, the code it always was)
+template <bool PARAB, class SPEC, int C, int END>
+__device__ __forceinline__ bool trim_ok(const SceneView& sv, const Query& q, d3 gp) {
+  constexpr int E = clause_end<SPEC>(C, END);
+  if constexpr (E >= END) {
+    return trim_all<PARAB, SPEC, C, END>(sv, q, gp);
+  } else {
+    if (trim_all<PARAB, SPEC, C, E>(sv, q, gp)) return true;
+    return trim_ok<PARAB, SPEC, E, END>(sv, q, gp);
   }
 }
 template <bool PARAB, class SPEC, int PI>
@@ -2088,14 +2121,20 @@ __global__ __launch_bounds__(256) void odw_emit_kernel(const DeviceEmitter E, ui
       // local -> global: x = R^T (p - t)
       const d3 q = mk(p.x - pf[3], p.y - pf[7], p.z - pf[11]);
       gp = xf_vec_t(pf, q);
+      // the trimming condition: kept if any clause holds (a clause: every literal up to the next word that opens one)
+      const bool dnf = pi[3] > 0 && cond_opens(E.cond_i32[pi[2]]);
       bool ok = true;
-      for (int c = pi[2]; c < pi[2] + pi[3] && ok; ++c) {
+      for (int c = pi[2]; c < pi[2] + pi[3] && (ok || dnf); ++c) {
         const int cw = E.cond_i32[c];
-        const int qp = cw & 0x7fffffff;
+        if (c != pi[2] && cond_opens(cw)) {
+          if (ok) break;                          // the clause before held
+          ok = true;
+        }
+        if (!ok) continue;
+        const int qp = cond_operand(cw);
         const double* of = E.prim_f64 + (size_t)qp * 16;
         const double sd = prim_sdist<true>(E.prim_i32[4 * qp], of + 12, xf_point(of, gp));
-        if (cw < 0) { if (sd > E.dist_tol) ok = false; }
-        else { if (sd < -E.dist_tol) ok = false; }
+        if (cw < 0 ? sd > E.dist_tol : sd < -E.dist_tol) ok = false;
       }
       if (!ok) continue;
       gn = xf_vec_t(pf, nl);

@@ -142,17 +142,25 @@ std::string spec_text(const odw_ctx* ctx) {
     xf[p] = w;
   }
   // primitives with the same box: equal sets {p} + {q : p must lie inside q} (compute_boxes cuts p's box by
-  // the boxes of those q).  box_of = the first such primitive, box_shared = another one refers to it.
+  // the boxes of those q), one set per clause of a trimming list of several (compute_boxes: the union over the
+  // clauses of such cuts -- equal sets of sets, equal boxes).  box_of = the first such primitive, box_shared =
+  // another one refers to it.
   std::vector<int> box_of(n), box_shared(n, 0);
   {
-    std::vector<std::vector<int>> inside(n);
+    std::vector<std::vector<std::vector<int>>> inside(n);
     for (int p = 0; p < n; ++p) {
-      inside[p].push_back(p);
       const int off = condw[p] & 0xffffff, cnt = (condw[p] >> 24) & 0xff;
-      for (int c = off; c < off + cnt && c < (int)ctx->h_cond.size(); ++c)
-        if (ctx->h_cond[c] < 0) inside[p].push_back(ctx->h_cond[c] & 0x7fffffff);
+      const int end = std::min(off + cnt, (int)ctx->h_cond.size());
+      inside[p].push_back({p});
+      for (int c = off; c < end; ++c) {
+        if (c != off && cond_opens(ctx->h_cond[c])) inside[p].push_back({p});
+        if (ctx->h_cond[c] < 0) inside[p].back().push_back(cond_operand(ctx->h_cond[c]));
+      }
+      for (std::vector<int>& set : inside[p]) {
+        std::sort(set.begin(), set.end());
+        set.erase(std::unique(set.begin(), set.end()), set.end());
+      }
       std::sort(inside[p].begin(), inside[p].end());
-      inside[p].erase(std::unique(inside[p].begin(), inside[p].end()), inside[p].end());
     }
     for (int p = 0; p < n; ++p) {
       box_of[p] = p;

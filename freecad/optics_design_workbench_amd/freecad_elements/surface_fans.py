@@ -179,7 +179,7 @@ def _boolean_faces(tree, container, dist_tol):
   """FaceViews of the result of Cut / Fuse / Common over primitives: every face of every operand that keeps a part
   of itself in the result, trimmed by the other operands.  OpenCASCADE hands the reference such a result as faces
   with the trimmed `ParameterRange` and an `isInside` that knows the trimming wires; here the trimming is the
-  conjunction of the operands' half-space conditions (geometry.flatten, the same conditions the tracer trims
+  disjunction of conjunctions of the operands' half-space conditions (geometry.flatten, the same conditions the tracer trims
   with), the parameter range is the extent of the part that survives (scanned, then each bound refined by
   bisection) and the area the sum of the area elements over the scan.  One view per operand face: OpenCASCADE
   splits a face whose remainder is not connected, the grid recipe then runs per piece -- here it runs once over
@@ -192,16 +192,16 @@ def _boolean_faces(tree, container, dist_tol):
         continue
       view = table[f]
 
-      def valid(u, v, x, view=view, conds=fp.conds):
+      def valid(u, v, x, view=view, clauses=fp.clauses):
         if not view.valid(u, v, x):
           return False
-        for other, inside in conds:
+        # (the trimming condition holds where any of its clauses does)
+        for conds in clauses:
           # (a point of the face that lies ON the other operand's boundary belongs to the result's edge)
-          if inside and not _inside_primitive(other, x, dist_tol):
-            return False
-          if not inside and _strictly_inside_primitive(other, x, dist_tol):
-            return False
-        return True
+          if all(_inside_primitive(other, x, dist_tol) if inside else not _strictly_inside_primitive(other, x, dist_tol)
+                 for other, inside in conds):
+            return True
+        return False
       u0, u1, v0, v1 = view.range
       found = True
       for _ in range(4):

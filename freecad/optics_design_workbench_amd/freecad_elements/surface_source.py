@@ -149,12 +149,7 @@ def bakeSurfaceSource(doc, obj):
                 faces.append((fp, f))
   if not faces and not facets:
     raise ValueError(f'surface source {obj.Name} has no ActiveSurfaces selected for emission')
-  cond_off, cond_prim, cond_inside = [0], [], []
-  for fp in prims:
-    for other, inside in fp.conds:
-      cond_prim.append(other.index)
-      cond_inside.append(1 if inside else 0)
-    cond_off.append(len(cond_prim))
+  cond_off, cond_prim, cond_inside = geometry.condTables(prims)
   srv = distributions.ScalarRandomVariable(
       **point_source.rvArgs(obj, obj.PowerDensity, variableDomain=point_source.parsedDomain(
           obj._props.get('ThetaDomain', '0, pi/4')), scalarRandomVar=True))

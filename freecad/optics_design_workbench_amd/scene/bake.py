@@ -306,12 +306,7 @@ def bakeScene(doc, source=None, surfaceFamily=None):
             prim_solid.append(solid_id)
           solid_id += 1
   n = len(prims)
-  cond_off, cond_prim, cond_inside = [0], [], []
-  for fp in prims:
-    for other, inside in fp.conds:
-      cond_prim.append(other.index)
-      cond_inside.append(1 if inside else 0)
-    cond_off.append(len(cond_prim))
+  cond_off, cond_prim, cond_inside = geometry.condTables(prims)
 
   def col(key, default, dtype=np.float64):
     return np.array([g._props.get(key, default) for g in groups], dtype=dtype)

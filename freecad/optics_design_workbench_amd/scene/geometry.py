@@ -6,7 +6,9 @@ simulation/raytracing_cache.py:92-111, used at freecad_elements/ray.py:345-411).
 Without FreeCAD the same faces are rebuilt from the parametric features:
 every face of a boolean result is a face of one operand restricted to the
 inside (Common), outside (Fuse, Cut base) or inside-with-flipped-normal (Cut
-tool) of the other operands.
+tool) of the other operands.  Nested booleans make that restriction a
+disjunction of conjunctions (inside a Fuse: inside any of its operands), which
+the trimming lists hold as clauses.
 """
 from dataclasses import dataclass, field
 
@@ -158,8 +160,8 @@ def solids_of(obj, with_own_placement=True, _depth=0, brepFacets=False):
   """-> list of CSG trees (one per shell) of `obj`, in the coordinates of
   obj's container.  `with_own_placement=False` drops obj.Placement (an
   App::Link with LinkTransform=false replaces it by its own).
-  Features the parametric recipe cannot express (partial revolutions, booleans of imported
-  shapes, nested disjunctions) fall back to the shape FreeCAD computed and stored with the
+  Features the parametric recipe cannot express (revolutions beyond half a turn, booleans of
+  tessellated shapes, trimming conditions beyond MAX_CLAUSES / MAX_LITERALS) fall back to the shape FreeCAD computed and stored with the
   object, as long as the project is as it was saved (a property written since then may have
   changed the shape; placements are applied here and do not count)."""
   try:
@@ -296,16 +298,20 @@ class FlatPrim:
   params: tuple
   to_world: Placement
   flip: bool
-  conds: list            # [(FlatPrim, want_inside)]
+  clauses: list          # [[(FlatPrim, want_inside)]]: the face exists where ANY clause holds (all of its literals)
   facemask: int
   source: str
   index: int = -1
 
 
+MAX_CLAUSES = 16        # clauses of one face's trimming condition
+MAX_LITERALS = 255      # conditions of one primitive (the 8-bit count of its cond word)
+
+
 def _leaves(node, acc, out):
   pl = acc * node.placement
   if node.op == 'prim':
-    fp = FlatPrim(node.kind, tuple(float(p) for p in node.params), pl, False, [],
+    fp = FlatPrim(node.kind, tuple(float(p) for p in node.params), pl, False, [[]],
                   ((1 << N_FACES[node.kind]) - 1) & node.facemask, node.source)
     node._flat = fp
     out.append(fp)
@@ -314,41 +320,96 @@ def _leaves(node, acc, out):
       _leaves(c, pl, out)
 
 
-def _inside_conj(node):
+# A trimming condition in disjunctive normal form: a list of clauses, each a list of literals
+# (FlatPrim, want_inside).  [[]] holds everywhere.  A list of ONE clause is the conjunction the flat
+# scene always held and is kept exactly as built (same literals, same order, repeats included: the
+# tables of such scenes do not change); lists of several clauses are simplified as they are built.
+def _simplified(clauses, source):
+  if len(clauses) <= 1:
+    return clauses
+  out = []
+  for cl in clauses:
+    seen, lits = set(), []
+    for fp, inside in cl:
+      if (id(fp), inside) not in seen:
+        seen.add((id(fp), inside))
+        lits.append((fp, inside))
+    if any((id(fp), not inside) in seen for fp, inside in lits):
+      continue                                             # p and not p: holds nowhere
+    out.append((frozenset(seen), lits))
+  kept = []
+  for i, (si, li) in enumerate(out):
+    # (a clause that another one implies adds nothing; of equal clauses the first stays)
+    if not any(sj < si or (sj == si and j < i) for j, (sj, _) in enumerate(out) if j != i):
+      kept.append(li)
+  if len(kept) > MAX_CLAUSES:
+    raise UnsupportedGeometry(f'{source}: a trimming condition of {len(kept)} clauses (more than {MAX_CLAUSES}) needs FreeCAD')
+  return kept
+
+
+def _product(lists, source):
+  """AND of conditions: every choice of one clause per list, concatenated in list order"""
+  out = [[]]
+  for clauses in lists:
+    out = _simplified([a + b for a in out for b in clauses], source)
+  return out
+
+
+def _inside_dnf(node):
   if node.op == 'prim':
-    return [(node._flat, True)]
+    return [[(node._flat, True)]]
   if node.op == 'common':
-    return [c for k in node.children for c in _inside_conj(k)]
+    return _product([_inside_dnf(k) for k in node.children], node.source)
   if node.op == 'cut':
-    return _inside_conj(node.children[0]) + _outside_conj(node.children[1])
-  raise UnsupportedGeometry(f'{node.source}: "inside a Fuse" is a disjunction; nested this way it needs FreeCAD')
-
-
-def _outside_conj(node):
-  if node.op == 'prim':
-    return [(node._flat, False)]
+    return _product([_inside_dnf(node.children[0]), _outside_dnf(node.children[1])], node.source)
   if node.op == 'fuse':
-    return [c for k in node.children for c in _outside_conj(k)]
-  raise UnsupportedGeometry(f'{node.source}: "outside a {node.op}" is a disjunction; nested this way it needs FreeCAD')
+    return _simplified([c for k in node.children for c in _inside_dnf(k)], node.source)
+  raise UnsupportedGeometry(f'{node.source}: "inside a {node.op}" is not a boolean of analytic solids')
 
 
-def _assign(node, conds, flip):
+def _outside_dnf(node):
   if node.op == 'prim':
-    node._flat.conds = list(conds)
+    return [[(node._flat, False)]]
+  if node.op == 'fuse':
+    return _product([_outside_dnf(k) for k in node.children], node.source)
+  if node.op == 'common':
+    return _simplified([c for k in node.children for c in _outside_dnf(k)], node.source)
+  if node.op == 'cut':
+    return _simplified(_outside_dnf(node.children[0]) + _inside_dnf(node.children[1]), node.source)
+  raise UnsupportedGeometry(f'{node.source}: "outside a {node.op}" is not a boolean of analytic solids')
+
+
+def _assign(node, clauses, flip):
+  if node.op == 'prim':
+    node._flat.clauses = [list(c) for c in clauses]
     node._flat.flip = flip
     return
   kids = node.children
   if node.op == 'common':
     for i, k in enumerate(kids):
-      extra = [c for j, o in enumerate(kids) if j != i for c in _inside_conj(o)]
-      _assign(k, conds + extra, flip)
+      _assign(k, _product([clauses] + [_inside_dnf(o) for j, o in enumerate(kids) if j != i], node.source), flip)
   elif node.op == 'fuse':
     for i, k in enumerate(kids):
-      extra = [c for j, o in enumerate(kids) if j != i for c in _outside_conj(o)]
-      _assign(k, conds + extra, flip)
+      _assign(k, _product([clauses] + [_outside_dnf(o) for j, o in enumerate(kids) if j != i], node.source), flip)
   elif node.op == 'cut':
-    _assign(kids[0], conds + _outside_conj(kids[1]), flip)
-    _assign(kids[1], conds + _inside_conj(kids[0]), not flip)
+    _assign(kids[0], _product([clauses, _outside_dnf(kids[1])], node.source), flip)
+    _assign(kids[1], _product([clauses, _inside_dnf(kids[0])], node.source), not flip)
+
+
+def condTables(prims):
+  """the trimming lists of `prims` (FlatPrims whose .index is their row) as the flat tables of the C ABI:
+  prim_cond_off (n + 1), cond_prim, cond_inside.  cond_inside bit 0: must be inside; bit 1: the literal opens a
+  clause -- set on the first literal of EVERY clause of a list of several, never in a list of one (a list without
+  marks is the single conjunction)"""
+  cond_off, cond_prim, cond_inside = [0], [], []
+  for fp in prims:
+    several = len(fp.clauses) > 1
+    for cl in fp.clauses:
+      for k, (other, inside) in enumerate(cl):
+        cond_prim.append(other.index)
+        cond_inside.append((1 if inside else 0) | (2 if several and k == 0 else 0))
+    cond_off.append(len(cond_prim))
+  return cond_off, cond_prim, cond_inside
 
 
 def is_convex(node):
@@ -452,7 +513,12 @@ def flatten(tree, acc=None):
   """CSG tree -> [FlatPrim] (every leaf once; conditions reference leaves)"""
   out = []
   _leaves(tree, acc or Placement.identity(), out)
-  _assign(tree, [], False)
+  _assign(tree, [[]], False)
+  for fp in out:
+    if not fp.clauses:                                     # (no clause can hold: the primitive keeps no face)
+      fp.clauses, fp.facemask = [[]], 0
+    if len(fp.clauses) > 1 and sum(len(c) for c in fp.clauses) > MAX_LITERALS:
+      raise UnsupportedGeometry(f'{fp.source}: a trimming condition of more than {MAX_LITERALS} literals needs FreeCAD')
   _prune_faces(out)
   return out
 
@@ -519,8 +585,9 @@ def _prune_faces(prims, slack=1e-3):
     return b
 
   for fp in prims:
-    must_be_in = [other for other, inside in fp.conds if inside]
-    if not must_be_in:                                     # (nothing to miss: every face it has stays)
+    # (a face can go only if EVERY clause has a must-be-inside operand whose box misses it)
+    must_be_in = [[other for other, inside in cl if inside] for cl in fp.clauses]
+    if not all(must_be_in):                                # (a clause with nothing to miss: every face it has stays)
       fp.facemask &= (1 << N_FACES[fp.kind]) - 1
       continue
     mask = 0
@@ -528,14 +595,16 @@ def _prune_faces(prims, slack=1e-3):
       if not (fp.facemask >> f) & 1:
         continue
       flo, fhi = world_aabb(fp.to_world, *face_local_bounds(fp.kind, fp.params, f))
-      keep = True
-      for other in must_be_in:
-        olo, ohi = box_of(other)
-        if np.any(flo > ohi + slack) or np.any(fhi < olo - slack):
-          keep = False
+      for ins in must_be_in:
+        keep = True
+        for other in ins:
+          olo, ohi = box_of(other)
+          if np.any(flo > ohi + slack) or np.any(fhi < olo - slack):
+            keep = False
+            break
+        if keep:
+          mask |= 1 << f
           break
-      if keep:
-        mask |= 1 << f
     fp.facemask = mask
 
 

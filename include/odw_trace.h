@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define ODW_ABI_VERSION 10
+#define ODW_ABI_VERSION 11
 
 /* ---- return codes ------------------------------------------------------ */
 enum {
@@ -120,7 +120,16 @@ typedef struct odw_scene_desc {
   const int32_t* prim_cond_off; /* [n_prims+1] CSG trimming conditions        */
   int32_t n_conds;
   const int32_t* cond_prim;     /* [n_conds] primitive the point is tested in */
-  const int32_t* cond_inside;   /* [n_conds] 1: must be inside, 0: outside    */
+                                /* (< 2^30)                                   */
+  const int32_t* cond_inside;   /* [n_conds] bit 0 -- 1: must be inside,      */
+                                /* 0: outside; bit 1: opens a clause (below)  */
+  /* A primitive's list prim_cond_off[p] .. prim_cond_off[p+1] is a trimming
+   * condition in disjunctive normal form: a candidate on the primitive is
+   * kept if ANY clause holds, a clause holds if ALL its conditions do.  A
+   * list without bit 1 anywhere is one clause (a plain conjunction).  A list
+   * of several clauses carries bit 1 on the first condition of EVERY clause,
+   * the first one included.  cond_inside outside 0..3, or bit 1 in a list
+   * whose first condition lacks it: ODW_ERR_INVALID.                         */
 
   int32_t n_groups;             /* <= ODW_MAX_GROUPS                          */
   const int32_t* group_type;    /* [n_groups] ODW_OPT_*                       */
@@ -251,7 +260,8 @@ typedef struct odw_surface_source_desc {
   const int32_t* prim_cond_off; /* [n_prims+1]                                */
   int32_t n_conds;
   const int32_t* cond_prim;     /* [n_conds] index into THIS primitive list   */
-  const int32_t* cond_inside;   /* [n_conds]                                  */
+  const int32_t* cond_inside;   /* [n_conds] bit 0 inside, bit 1 opens a      */
+                                /* clause: as in odw_scene_desc               */
   int32_t n_faces;
   const int32_t* face_prim;     /* [n_faces]                                  */
   const int32_t* face_id;       /* [n_faces] face bit position (see above)    */
