@@ -186,7 +186,7 @@ def lib():
     if not os.path.exists(LIB_PATH):
       raise NativeError(f'{LIB_PATH} is missing: run __graft_entry__.build() '
                         f'(or freecad.optics_design_workbench_amd._native.build()) first')
-    # ODW_TRACE_LIB: another build of the same library (kernel experiments, scripts/try_variants.sh)
+    # ODW_TRACE_LIB: another build of the same library (kernel experiments, scripts/build_variant.py)
     l = C.CDLL(os.environ.get('ODW_TRACE_LIB') or LIB_PATH)
     l.odw_last_error.restype = C.c_char_p
     l.odw_last_error.argtypes = [C.c_void_p]

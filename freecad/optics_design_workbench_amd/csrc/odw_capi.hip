@@ -31,14 +31,14 @@ using namespace odw;
 namespace {
 
 constexpr int kGuide = 1 << 16;
-// Hit-list slots a wave reserves per atomic, and the smallest list that gets the room for it (A/B: ODW_HIT_BLOCK,
-// ODW_HIT_BLOCK_MIN_ROWS).  Atomics on one address complete at about one per 3.6 ns on this chip whatever the number
+// Hit-list slots a wave reserves per atomic, and the smallest list that gets the room for it.
+// Atomics on one address complete at about one per 3.6 ns on this chip whatever the number
 // of waves, so a launch's length is bounded below by its atomic count: GettingStarted with a reservation per wave and
 // recording step takes 0.23 / 0.66 ms for 1e6 / 3e6 rays, with blocks of 512 slots 0.16 / 0.34 (128: 0.19 / 0.45,
 // 256: 0.17 / 0.36, 1024: 0.17 / 0.35, 4096: 0.33 / 0.68 -- the unused slots a wave tags at its end); at 1e8 rays
 // 128: 10.7 ms, 256: 6.41, 512: 6.10, 1024: 6.06, 2048: 6.04, 4096: 6.13 (profiles/r03/r03q_hit_blocks.log).
-static const uint32_t kHitBlock = [] { const char* e = getenv("ODW_HIT_BLOCK"); const int v = e ? atoi(e) : 0; return (uint32_t)(v >= 64 ? (v & ~63) : 512); }();
-static const uint64_t kHitBlockMinRows = [] { const char* e = getenv("ODW_HIT_BLOCK_MIN_ROWS"); return e ? (uint64_t)atoll(e) : (1ull << 16); }();
+constexpr uint32_t kHitBlock = 512;
+constexpr uint64_t kHitBlockMinRows = 1ull << 16;
 // room a list of `capacity` rows needs for reservations of `block` slots by `waves` waves: < 64 unused slots per
 // block change, and the last block of every wave
 static inline uint64_t hit_block_room(uint64_t capacity, uint64_t waves, uint64_t block) { return capacity * 64 / block + 64 + waves * block; }
@@ -51,8 +51,8 @@ constexpr int kSurfaceGuide = 1 << 10;  // per row of a surface sampler (tables 
 // (scripts/bench_lens_train.py, scripts/bench_crowded.py).  ODW_BVH_THRESHOLD (read when a context is created)
 // overrides it: the tests keep the grid kernel's generic variant covered with 16.
 constexpr int kBvhThreshold = 64;
-const int kBvhLeaf = [] { const char* e = getenv("ODW_BVH_LEAF"); const int v = e ? atoi(e) : 0; return v > 0 && v < 200 ? v : 8; }();   // largest leaf the SAH may form (measured: 8 >= 4 > 2 > 1 on meshes; round 5, mesh kernel at 1e6 facets: 8 / 6 / 4 / 3 / 2 / 1 = 7.70 / 7.73 / 7.84 / 7.95 / 8.16 / 9.04 ms -- candidates per segment 18 -> 8, node visits 11.7 -> 14.7)
-constexpr int kBvhSweepMax = 2048;       // nodes with more primitives use binned SAH
+constexpr int kBvhLeaf = 8;   // largest leaf the SAH may form (measured: 8 >= 4 > 2 > 1 on meshes; round 5, mesh kernel at 1e6 facets: 8 / 6 / 4 / 3 / 2 / 1 = 7.70 / 7.73 / 7.84 / 7.95 / 8.16 / 9.04 ms -- candidates per segment 18 -> 8, node visits 11.7 -> 14.7)
+constexpr int kBvhSweepMax = 256;        // nodes with more primitives use binned SAH
 
 std::string g_error;
 
@@ -386,26 +386,13 @@ struct BvhBuilder {
   std::vector<int> order;       // leaf primitive order
   std::vector<BvhNode> nodes;
   int max_depth = 0;
-  // from this depth on only median splits down to leaves of kBvhLeaf: whatever
-  // the SAH did above, the tree stays within the traversal stack
-  int balanced_depth;
 
-  // The heuristic goes on below balanced_depth wherever the levels that are left still hold a median-split subtree of
-  // the node's primitives (round 5; ODW_BVH_SAH_DEEP=0: medians from balanced_depth on, as before).  Ball lens of 1e6
-  // facets under the mesh kernel: 12.8 -> 7.2 candidate facets per segment, 6.02 -> 5.77 ms per 1e7 rays, build 0.8 -> 1.1 s
-  // (full sweeps only up to 256 primitives: above that, 32 bins).
-  bool deep_sah = true;
-  int sweep_max = kBvhSweepMax;
-
-  explicit BvhBuilder(const std::vector<Box>& b) : boxes(b) {
-    const double n = (double)std::max<size_t>(b.size(), 8);
-    balanced_depth = std::max(2, ODW_BVH_STACK - 2 - (int)std::ceil(std::log2(n / kBvhLeaf)) - 1);
-    const char* e = getenv("ODW_BVH_SAH_DEEP");
-    deep_sah = !(e && e[0] == '0');
-    if (deep_sah) sweep_max = 256;
-  }
+  // The heuristic goes on wherever the levels that are left still hold a median-split subtree of the node's primitives
+  // down to leaves of kBvhLeaf; below that, median splits keep the tree within the traversal stack (round 5: against
+  // medians from a fixed depth on, ball lens of 1e6 facets under the mesh kernel: 12.8 -> 7.2 candidate facets per
+  // segment, 6.02 -> 5.77 ms per 1e7 rays, build 0.8 -> 1.1 s; full sweeps only up to kBvhSweepMax primitives).
+  explicit BvhBuilder(const std::vector<Box>& b) : boxes(b) {}
   bool sah_ok(int depth, int m) const {
-    if (!deep_sah) return depth < balanced_depth;
     const int need = (int)std::ceil(std::log2(std::max(1.0, (double)m / kBvhLeaf)));
     return depth + need + 2 <= ODW_BVH_STACK - 3;
   }
@@ -435,7 +422,7 @@ struct BvhBuilder {
     if (m <= 1) return make_leaf();
     const bool sah = sah_ok(depth, m);
     if (!sah && m <= kBvhLeaf) return make_leaf();
-    if (m > sweep_max || !sah) return build_big(ids, depth, bb);
+    if (m > kBvhSweepMax || !sah) return build_big(ids, depth, bb);
     // SAH sweep
     double best_cost = INFINITY;
     int best_axis = -1, best_split = 0;
@@ -467,7 +454,7 @@ struct BvhBuilder {
   }
 
   // big nodes (meshes): binned SAH over 32 bins of the centroid range, O(m) per
-  // node; from balanced_depth on: median splits, which bound the remaining
+  // node; where sah_ok() says no: median splits, which bound the remaining
   // depth by log2(m / kBvhLeaf)
   Ref build_big(std::vector<int>& ids, int depth, const Box& bb) {
     const int m = (int)ids.size();
@@ -839,12 +826,11 @@ constexpr size_t kGridLdsBudget = 144 * 1024; // of the CU's 160 KB, one block p
 int build_grid(odw_ctx* ctx, const std::vector<Box>& boxes, const std::vector<char>& dead) {
   DeviceGrid& G = ctx->P.grid;
   std::memset(&G, 0, sizeof G);
-  static const bool off = getenv("ODW_NO_GRID") != nullptr;
   const int n = (int)boxes.size();
   std::vector<int> live;
   for (int p = 0; p < n; ++p)
     if (!dead[p]) live.push_back(p);
-  if (off || live.empty()) return ODW_OK;
+  if (live.empty()) return ODW_OK;
   Box all;
   all.reset();
   for (int p : live) all.grow(boxes[p]);
@@ -1038,8 +1024,7 @@ void compute_boxes(odw_ctx* ctx, std::vector<Box>& boxes, std::vector<char>& dea
       }
     }
     const double gap = 2.0 * slack;                             // 4 distTol
-    static const bool enabled = !(getenv("ODW_ISOLATED") && getenv("ODW_ISOLATED")[0] == '0');   // (A/B runs)
-    if (enabled && solid_box.size() <= 64 && solid_box.count(0x7fff) == 0)  // (0x7fff: solid ids that did not fit the word)
+    if (solid_box.size() <= 64 && solid_box.count(0x7fff) == 0)  // (0x7fff: solid ids that did not fit the word)
       for (int p = 0; p < n; ++p) {
         if (dead[p]) continue;
         const int sid = ctx->h_prim_i32[4 * p + 2] >> ODW_SOLID_SHIFT;
@@ -1134,7 +1119,7 @@ int build_bvh(odw_ctx* ctx) {
   ctx->P.scene.bvh_leaf = nullptr;
   ctx->P.scene.bvh_wide = nullptr;
   std::vector<float> recs;
-  // (read at every build: A/B runs and the test that holds the two kernels against each other)
+  // (read at every build: the test that holds the two kernels against each other)
   const bool mesh_kernel = !(getenv("ODW_MESH_KERNEL") && getenv("ODW_MESH_KERNEL")[0] == '0');
   std::vector<int> prim_solid((size_t)n);
   for (int p = 0; p < n; ++p) prim_solid[p] = ctx->h_prim_i32[4 * (size_t)p + 2] >> ODW_SOLID_SHIFT;
@@ -1272,7 +1257,7 @@ namespace {
 // results are those of the unsorted launch.  Cost: one generation pass for the keys + a radix sort of (key, number)
 // pairs (1e7 rays: ~0.8 ms against 10 - 17 ms of tracing); short launches and ODW_MESH_PRESORT=0 keep the plain order.
 int presort_rays(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed) {
-  // (read at every launch: A/B runs and the test that holds the two orders against each other)
+  // (read at every launch: the test that holds the two orders against each other)
   const bool off = getenv("ODW_MESH_PRESORT") && getenv("ODW_MESH_PRESORT")[0] == '0';
   const char* e_min = getenv("ODW_MESH_PRESORT_MIN");
   const uint64_t min_rays = e_min ? (uint64_t)atoll(e_min) : (1ull << 16);
@@ -1320,34 +1305,6 @@ int presort_rays(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed) {
   return ODW_OK;
 }
 
-#if ODW_GRID_SORTED
-// Grid launches of device-generated rays (diagnostic builds, -DODW_GRID_SORTED=1): hand-out order = sorted by the top `bits`
-// bits of the Morton key of the two uniform numbers a ray's direction is drawn from (odw_grid.hip: odw_ray_ukey_kernel;
-// Philox only).  ODW_GRID_PRESORT = bits; the rows of a ray depend on its number only.  See profiles/r05/README.md.
-int presort_rays_grid(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, int bits) {
-  if (bits <= 0 || n < (1ull << 16) || n > 0x7FFFFFFFull) return ODW_OK;
-  bits = std::min(bits, 32);
-  int rc;
-  for (int k = 0; k < 2; ++k) {
-    if ((rc = ensure(ctx, ctx->sort_keys[k], n * sizeof(uint32_t)))) return rc;
-    if ((rc = ensure(ctx, ctx->sort_vals[k], n * sizeof(uint32_t)))) return rc;
-  }
-  uint32_t* k_in = (uint32_t*)ctx->sort_keys[0].p;
-  uint32_t* k_out = (uint32_t*)ctx->sort_keys[1].p;
-  uint32_t* v_in = (uint32_t*)ctx->sort_vals[0].p;
-  uint32_t* v_out = (uint32_t*)ctx->sort_vals[1].p;
-  const unsigned kgrid = (unsigned)((n + 255) / 256);
-  size_t tmp_bytes = 0;
-  hipLaunchKernelGGL(odw_ray_ukey_kernel, dim3(kgrid), dim3(256), 0, ctx->stream, first, n, seed, k_in, v_in);
-  HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, k_in, k_out, v_in, v_out, (int)n, 32 - bits, 32, ctx->stream));
-  if ((rc = ensure(ctx, ctx->sort_tmp, tmp_bytes))) return rc;
-  HIPCHK(ctx, hipcub::DeviceRadixSort::SortPairs(ctx->sort_tmp.p, tmp_bytes, k_in, k_out, v_in, v_out, (int)n, 32 - bits, 32, ctx->stream));
-  ctx->P.ray_order = v_out;
-  ctx->ph_valid = false;           // (the sort buffers are shared with odw_hits_select)
-  return ODW_OK;
-}
-#endif
 
 int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32_t flags,
                  const double* ray_o, const double* ray_d, const double* ray_p) {
@@ -1418,7 +1375,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // persistent waves: one grid that fills the chip (4 blocks of 256 threads
   // per CU at 4 waves/SIMD, x2 so that a CU never waits for a block launch);
   // chunks of ODW_CHUNK rays are handed out dynamically inside the kernel
-  static const int grid_mult = [] { const char* e = getenv("ODW_GRID_MULT"); int v = e ? atoi(e) : 0; return v > 0 ? v : 8; }();
+  constexpr int grid_mult = 8;
   // big analytic scenes: grid kernel (no stochastic surfaces, no segment rows: those stay with the BVH kernels)
   // a scene compiled against its structure (odw_spec.hip): its own kernel, whatever else was built for it
   if (batch && ctx->spec_fn && !ctx->spec_batch_fn && !ctx->spec_batch_failed) {
@@ -1442,20 +1399,17 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // the ring kernels (grid, mesh: a ring fill is 64 rays whatever the chunk) 2048: 2.24 / 21.34, 512: 2.05 / 20.95,
   // 256: 1.96 / 20.86, and the mesh kernel at 1e7 rays and 6.5e4 facets 2048: 14.6, 256: 12.5, 64: 12.3.
   {
-    static const uint64_t forced = [] { const char* e = getenv("ODW_CHUNK_RAYS"); return e ? (uint64_t)atoll(e) : 0ull; }();   // (A/B runs)
     const bool ring = use_grid || (!use_spec && P.scene.n_nodes && P.scene.bvh_leaf && !(flags & ODW_TRACE_RECORD_SEGMENTS));
     const uint64_t waves = (uint64_t)ctx->n_cu * 16;
     const uint64_t want = ring ? std::max<uint64_t>(64, std::min<uint64_t>(256, n / (waves * 32)))
                                : std::max<uint64_t>(512, std::min<uint64_t>(1024, n / (waves * 4)));
-    P.chunk = (uint32_t)((forced ? std::max<uint64_t>(64, std::min<uint64_t>(ODW_CHUNK, forced)) : want) & ~(uint64_t)63);
+    P.chunk = (uint32_t)(want & ~(uint64_t)63);
   }
   uint64_t n_chunks = (n + P.chunk - 1) / P.chunk;
   if (batch) {
     // n = the rays of ONE scene; the launch hands out chunks_per_scene units per scene
     const uint64_t total = n * (uint64_t)ctx->batch_traced, waves = (uint64_t)ctx->n_cu * 16;
-    static const uint64_t forced = [] { const char* e = getenv("ODW_CHUNK_RAYS"); return e ? (uint64_t)atoll(e) : 0ull; }();
-    P.chunk = (uint32_t)((forced ? std::max<uint64_t>(64, std::min<uint64_t>(ODW_CHUNK, forced))
-                                 : std::max<uint64_t>(512, std::min<uint64_t>(1024, total / (waves * 4)))) & ~(uint64_t)63);
+    P.chunk = (uint32_t)(std::max<uint64_t>(512, std::min<uint64_t>(1024, total / (waves * 4))) & ~(uint64_t)63);
     const uint64_t cps = (n + P.chunk - 1) / P.chunk;
     if (cps * (uint64_t)ctx->batch_traced >= (1ull << 32)) return fail(ctx, ODW_ERR_INVALID, "odw_trace_batch: too many hand-out units");
     P.batch.rays = n;
@@ -1464,11 +1418,10 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     P.batch.n_scenes = (uint32_t)ctx->batch_traced;
     n_chunks = cps * (uint64_t)ctx->batch_traced;
     // the batch's rays once, for all its scenes (from three scenes on: the pass writes 24 bytes per ray -- 48 where the
-    // origins differ -- and every scene reads them; ODW_BATCH_SHARED_RAYS=0: every scene generates its own, =1: always)
+    // origins differ -- and every scene reads them; fewer scenes generate their own)
     P.batch.gen_dirs = P.batch.gen_origins = nullptr;
     P.batch.gen_stride = 0;
-    static const int shared_mode = [] { const char* e = getenv("ODW_BATCH_SHARED_RAYS"); return e ? atoi(e) : -1; }();
-    if (shared_mode != 0 && (ctx->batch_traced >= 3 || shared_mode == 1)) {
+    if (ctx->batch_traced >= 3) {
       const bool one_origin = ctx->h_source.finite_focal && ctx->h_source.focal_length == 0.0;
       const uint64_t gs = (n + 31) / 32 * 32;
       const size_t bytes = (size_t)(gs * (one_origin ? 3 : 6) + 4) * sizeof(double);
@@ -1486,10 +1439,10 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   }
   // Batch launches share the GPU with the post-hoc chains of other contexts (a sweep keeps several groups in flight): three
   // blocks per CU instead of all four leave a quarter of every SIMD's registers to their kernels and to the runtime's copy
-  // kernels, which otherwise wait until a persistent block retires, i.e. for the whole launch (ODW_BATCH_GRID_MULT; measured
-  // on the 64 x 1e7 sweep with 16 hardware queues: 98 ms -> 86 ms per sweep)
-  static const int batch_mult = [] { const char* e = getenv("ODW_BATCH_GRID_MULT"); int v = e ? atoi(e) : 0; return v > 0 ? v : 3; }();
-  const uint64_t cap = (uint64_t)ctx->n_cu * (batch ? std::min(batch_mult, grid_mult) : grid_mult);
+  // kernels, which otherwise wait until a persistent block retires, i.e. for the whole launch (measured on the 64 x 1e7
+  // sweep with 16 hardware queues: 98 ms -> 86 ms per sweep)
+  constexpr int batch_mult = 3;
+  const uint64_t cap = (uint64_t)ctx->n_cu * (batch ? batch_mult : grid_mult);
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_chunks + 3) / 4, cap));
   const uint64_t grid_blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_chunks + ODW_GRID_WAVES - 1) / ODW_GRID_WAVES, (uint64_t)ctx->n_cu));
   // scenes with facets: the mesh kernel (same exclusions)
@@ -1520,26 +1473,10 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   }
   const bool stoch = ctx->n_samplers > 0;
   P.ray_order = nullptr;
-  P.interact_min = 1;
-  P.refill_min = 0;
   if (use_mesh && !explicit_rays) {
     int rc = presort_rays(ctx, first, n, seed);       // (inside the timed window: part of the launch's cost)
     if (rc) return rc;
   }
-#if ODW_GRID_SORTED
-  if (use_grid) {
-    // (diagnostic builds only; read at every launch: A/B runs)
-    const char* e_bits = getenv("ODW_GRID_PRESORT");
-    const char* e_gate = getenv("ODW_GRID_GATE");
-    const char* e_refill = getenv("ODW_GRID_REFILL");
-    P.refill_min = e_refill ? (uint32_t)std::max(1, std::min(64, atoi(e_refill))) : 1u;
-    if (!explicit_rays && e_bits) {
-      int rc = presort_rays_grid(ctx, first, n, seed, atoi(e_bits));
-      if (rc) return rc;
-      if (P.ray_order && e_gate) P.interact_min = (uint32_t)std::max(1, std::min(64, atoi(e_gate)));
-    }
-  }
-#endif
   if (use_spec) {
     int rc = spec_launch(ctx, grid, batch);
     if (rc) return rc;
@@ -1549,28 +1486,20 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   } else if (use_grid) {
     const dim3 gb((unsigned)grid_blocks);
     const size_t glds = P.grid.lds_bytes;
-#define ODW_GRID_LAUNCH(S, L, O)                                                                                 \
+#define ODW_GRID_LAUNCH(S, L)                                                                                    \
     do {                                                                                                       \
       /* (once per device and instantiation: a second context on another GPU of the process needs its own) */  \
       static uint64_t attr_set = 0;                                                                            \
       const uint64_t dev_bit = 1ull << (ctx->device & 63);                                                     \
       if (!(attr_set & dev_bit)) {                                                                             \
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&odw_grid_kernel<S, L, O>),              \
+        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&odw_grid_kernel<S, L>),                 \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));   /* + 4.5 KB static */ \
         attr_set |= dev_bit;                                                                                   \
       }                                                                                                        \
-      hipLaunchKernelGGL((odw_grid_kernel<S, L, O>), gb, dim3(ODW_GRID_THREADS), glds, ctx->stream, P);        \
+      hipLaunchKernelGGL((odw_grid_kernel<S, L>), gb, dim3(ODW_GRID_THREADS), glds, ctx->stream, P);           \
     } while (0)
-#if ODW_GRID_SORTED
-    if (P.ray_order) {
-      if (P.grid.spheres) { if (P.grid.in_lds) ODW_GRID_LAUNCH(true, true, true); else ODW_GRID_LAUNCH(true, false, true); }
-      else { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true, true); else ODW_GRID_LAUNCH(false, false, true); }
-    } else
-#endif
-    {
-      if (P.grid.spheres) { if (P.grid.in_lds) ODW_GRID_LAUNCH(true, true, false); else ODW_GRID_LAUNCH(true, false, false); }
-      else { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true, false); else ODW_GRID_LAUNCH(false, false, false); }
-    }
+    if (P.grid.spheres) { if (P.grid.in_lds) ODW_GRID_LAUNCH(true, true); else ODW_GRID_LAUNCH(true, false); }
+    else { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true); else ODW_GRID_LAUNCH(false, false); }
 #undef ODW_GRID_LAUNCH
   } else if (use_mesh) {
     const size_t mlds = (size_t)ODW_MESH_STACK * ODW_MESH_THREADS * 2 * sizeof(int) +
@@ -1867,7 +1796,7 @@ static int scene_host_tables(odw_ctx* ctx, const odw_scene_desc* s) {
   ctx->h_cond = cond;
   std::vector<double> gf(ODW_MAX_GROUPS * 4, 0.0), gd(ODW_MAX_GROUPS * 3, 0.0);
   std::vector<int32_t> gi(ODW_MAX_GROUPS * 4, 0);
-  ctx->lean = getenv("ODW_NO_LEAN") == nullptr;
+  ctx->lean = true;
   for (int g = 0; g < s->n_groups; ++g)
     if (s->group_type[g] == ODW_OPT_GRATING || !(s->group_abslen[g] == INFINITY)) ctx->lean = false;
   for (int g = 0; g < s->n_groups; ++g) {
@@ -2568,7 +2497,7 @@ int odw_batch_reserve(odw_ctx* ctx, int32_t n_scenes, uint64_t rays_per_scene, u
     if (!rc) rc = ensure(ctx, ctx->batch_hit_count, S * 4 * sizeof(uint64_t));
   }
   if (!rc) rc = phb_reserve(ctx, (int)S, rays_per_scene, slots);
-  if (!rc && rows_per_scene && rays_per_scene <= (1ull << 28) && !(getenv("ODW_BATCH_PTS") && getenv("ODW_BATCH_PTS")[0] == '0'))
+  if (!rc && rows_per_scene && rays_per_scene <= (1ull << 28))
     rc = ensure(ctx, ctx->phb_pts, S * slots * 3 * sizeof(double));
   // (the rays generated once per launch, DeviceBatch.gen_dirs: with origins, whatever the source will be)
   if (!rc && S >= 3) rc = ensure(ctx, ctx->batch_rays_buf, (size_t)((rays_per_scene + 31) / 32 * 32 * 6 + 4) * sizeof(double));
@@ -2611,9 +2540,8 @@ int odw_trace_batch(odw_ctx* ctx, uint64_t first_ray, uint64_t rays_per_scene, u
       if (rc) return rc;
       HIPCHK(ctx, hipMemsetAsync(ctx->phb_row_of.p, 0xff, S * rays_pad * sizeof(uint32_t), ctx->stream));
       ctx->batch_marked = true;
-      // (the points alone, by slot: 24 bytes more per row; ODW_BATCH_PTS=0: the projection reads the rows)
-      static const bool pts_off = [] { const char* e = getenv("ODW_BATCH_PTS"); return e && e[0] == '0'; }();
-      ctx->batch_pts = !pts_off && ensure(ctx, ctx->phb_pts, S * slots * 3 * sizeof(double)) == ODW_OK;
+      // (the points alone, by slot: 24 bytes more per row; without them the projection reads the rows)
+      ctx->batch_pts = ensure(ctx, ctx->phb_pts, S * slots * 3 * sizeof(double)) == ODW_OK;
     }
   }
   // the value tables of scene 0 stand where the kernels' pointers point; scene s lies s strides further

@@ -40,22 +40,6 @@ namespace odw {
                                  // 8: 39.8, 16: 41.5 per 1.25e8 hugeArray rays -- a pop costs ~30 instructions, a lane
                                  // that waits for seven others idles through whole cell steps)
 #endif
-#ifndef ODW_GRID_CUT_REG
-#define ODW_GRID_CUT_REG 1       // where the walk ends (nearest + 2 distTol, the length limit) kept in a register pair, renewed when the nearest changes
-#endif
-#ifndef ODW_GRID_EXACT_WALK
-#define ODW_GRID_EXACT_WALK 0    // A/B (round 4): exact sphere roots and consider() inside the cell step, no resolve queue
-#endif
-#ifndef ODW_GRID_LEAN_TEST
-#define ODW_GRID_LEAN_TEST 1     // the walk's sphere test reads centre and radius only (A/B: 0 = the record's group / solid word too)
-#endif
-#ifndef ODW_GRID_SORTED
-#define ODW_GRID_SORTED 0        // A/B (round 5, profiles/r05/README.md): 1 = also build the kernels that hand the launch's rays out sorted by
-#endif                           // where they point (ODW_GRID_PRESORT = key bits) and let a wave's lanes interact together (ODW_GRID_GATE):
-                                 // hugeArray 20.3 ms -> kernel 17.6 - 18.6 + key pass and radix sort 2.2 - 3.9 = 20.8 - 21.5 ms; not kept
-#ifndef ODW_GRID_RCP
-#define ODW_GRID_RCP frcp1          // (A/B: frcp = two Newton steps)
-#endif
 #define ODW_GRID_THREADS 1024
 #define ODW_GRID_WAVES (ODW_GRID_THREADS / 64)
 #define ODW_GRID_WAVE_WORDS 32   // per wave: event counters (0..7), diagnostics (8..27), hit-block state (28..31)
@@ -100,7 +84,7 @@ __device__ __forceinline__ int grid_slab(const double* b, int n, double v) {
 // lanes add with ds_add_u32 (a handful of events per ray)
 #define ODW_GCOUNT(k) atomicAdd(&wave_cnt[(k)], 1u)
 
-template <bool SPHERES, bool IN_LDS, bool SORTED>
+template <bool SPHERES, bool IN_LDS>
 __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceParams P) {
   extern __shared__ double grid_lds[];
   const DeviceScene& sc = P.scene;
@@ -182,9 +166,6 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
   double tx = INFINITY, ty = INFINITY, tz = INFINITY, ivx = 0, ivy = 0, ivz = 0;
   double cut = 0;        // min(length limit, nearest + 2 distTol): cells that begin beyond it are not visited (ray.py:432, 440)
   int cell = 0;
-  // (index order: the constants; a sorted launch reads its thresholds from the arguments -- A/B runs)
-#define refill_min (SORTED ? P.refill_min : (uint32_t)ODW_GRID_REFILL_MIN)
-#define interact_min (SORTED ? P.interact_min : 1u)
 
   // leave the cell through the nearest plane (the axis by selects, the next plane by ONE read of the
   // contiguous plane tables), or end the walk: beyond nearest + 2 distTol (ray.py:432, 440), or out of the grid
@@ -193,8 +174,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
 #define ODW_WALK_ADVANCE()                                                                   \
   do {                                                                                       \
     const double t_exit_ = fmin_raw(tx, fmin_raw(ty, tz));                                   \
-    const double cut_ = ODW_GRID_CUT_REG ? cut : fmin_raw(q.tmax, q.any.t + 2.0 * q.tol);   \
-    if (!(t_exit_ <= cut_)) {                                                                \
+    if (!(t_exit_ <= cut)) {                                                                 \
       walking = false;                                                                       \
     } else {                                                                                 \
       const bool ax_ = tx <= ty && tx <= tz;                                                 \
@@ -228,7 +208,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
     // ---- A: new rays for idle lanes, from the wave's ring ------------------------------------------
     const uint64_t idle = __ballot(!alive);
     if (idle == ~0ull && drained && ring_n == 0) break;    // nothing live, nothing left
-    if (idle && !(drained && ring_n == 0) && (idle == ~0ull || (uint32_t)__popcll(idle) >= refill_min)) {
+    if (idle && !(drained && ring_n == 0) && (idle == ~0ull || (uint32_t)__popcll(idle) >= ODW_GRID_REFILL_MIN)) {
       if (ring_n == 0) {
         // fill: the whole wave generates the next (up to) 64 rays of its chunk, one per lane
         if (next >= chunk_end) {
@@ -245,8 +225,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
         const uint32_t fill = avail < ODW_GRID_RING ? (uint32_t)avail : (uint32_t)ODW_GRID_RING;
         ODW_GSTAT(0, __ballot(lane < fill));
         if (lane < fill) {
-          // (position next + lane of the hand-out order is ray number r: odw_capi.hip, presort_rays)
-          const uint64_t r = SORTED ? (uint64_t)P.ray_order[next + lane] : next + lane;
+          const uint64_t r = next + lane;
           d3 o, d;
           if (P.ray_origins) {
             o = mk(P.ray_origins[r], P.ray_origins[P.ray_stride + r], P.ray_origins[2 * P.ray_stride + r]);
@@ -260,7 +239,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
           // and not at the set-up of the first segment, which shares its run with lanes that go on from a hit
           uint32_t first_cell = 0xffffffffu;
           {
-            const double jx = ODW_GRID_RCP(d.x), jy = ODW_GRID_RCP(d.y), jz = ODW_GRID_RCP(d.z);
+            const double jx = frcp1(d.x), jy = frcp1(d.y), jz = frcp1(d.z);
             bool in = true;
             double t0 = 0.0, t1 = q.tmax;
 #define ODW_CLIP(O, D, INV, LO, HI)                                          \
@@ -284,7 +263,6 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
           double* slot = ring + 7 * lane;
           slot[0] = o.x; slot[1] = o.y; slot[2] = o.z; slot[3] = d.x; slot[4] = d.y; slot[5] = d.z;
           reinterpret_cast<uint32_t*>(slot + 6)[0] = first_cell;
-          if (SORTED) reinterpret_cast<uint32_t*>(slot + 6)[1] = (uint32_t)r;  // (a sorted launch holds < 2^31 rays)
         }
         // (one wave: its LDS operations complete in program order; this only keeps the compiler from
         //  moving the reads below above the writes)
@@ -303,7 +281,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
         point = mk(slot[0], slot[1], slot[2]);
         dir = mk(slot[3], slot[4], slot[5]);
         cell = (int)reinterpret_cast<const uint32_t*>(slot + 6)[0];       // (-1: the ray misses the grid)
-        i = SORTED ? (uint64_t)reinterpret_cast<const uint32_t*>(slot + 6)[1] : ring_base + s;
+        i = ring_base + s;
         power = P.ray_origins ? (P.ray_powers ? P.ray_powers[i] : 1.0) : as_const(P.source)->power;
         seq = 0; nint = 0; medium = -1; skip = -1; skip_rec = -1;
         alive = true; fresh = true; walking = false; pending = false;
@@ -332,7 +310,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
         if (mask != 0ull) {
           // (one Newton step, 2^-50: the plane distances of the walk decide the order of the cells and where it ends,
           //  against boxes that carry 2 distTol of slack -- as the inverse direction of the flat kernels' box tests)
-          ivx = ODW_GRID_RCP(dir.x); ivy = ODW_GRID_RCP(dir.y); ivz = ODW_GRID_RCP(dir.z);
+          ivx = frcp1(dir.x); ivy = frcp1(dir.y); ivz = frcp1(dir.z);
           // A ray that goes on from a hit starts in the cell its walk stopped in: the walk ends in the cell whose
           // exit lies beyond the hit (+ 2 distTol), so the hit point is in it or within the tolerance of it.  If it
           // is a hair outside, the plane distance of that axis comes out negative (or the cell is entered at once)
@@ -356,11 +334,9 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
       if (wb == 0ull) break;
       // stop stepping once few lanes walk if lanes wait: for resolution / interaction, or -- enough of
       // them -- for a new ray
-      // (a sorted launch whose lanes interact together: lanes that wait for the others are no reason to stop stepping,
-      //  lanes that wait for their cell to be resolved are)
       if (it > 0 && __popcll(wb) < ODW_GRID_STEP_MIN &&
-          (__ballot(alive && !walking && (interact_min <= 1u || pending || fresh)) != 0ull ||
-           (!(drained && ring_n == 0) && (uint32_t)__popcll(__ballot(!alive)) >= refill_min)))
+          (__ballot(alive && !walking) != 0ull ||
+           (!(drained && ring_n == 0) && (uint32_t)__popcll(__ballot(!alive)) >= ODW_GRID_REFILL_MIN)))
         break;
       ODW_GSTAT(2, wb);
       if (walking) {
@@ -373,30 +349,6 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
         for (uint32_t k = 0; k < count; ++k) {
           if (SPHERES) {
             // cheap test: does the line meet the sphere (discriminant), not behind the ray
-#if ODW_GRID_EXACT_WALK
-            // A/B (round 4): the exact roots and consider() inside the cell step, no resolve queue -- the lanes whose
-            // line meets the sphere run them under a divergent branch while the others wait
-            double2 r0, r1, r2;
-            if (IN_LDS) {
-              const double2* rec = reinterpret_cast<const double2*>(grid_lds + item_off) + 3 * (size_t)(first + k);
-              r0 = rec[0]; r1 = rec[1]; r2 = rec[2];
-            } else {
-              const double2* rec = reinterpret_cast<const double2*>(GD.items) + 3 * (size_t)(first + k);
-              r0 = rec[0]; r1 = rec[1]; r2 = rec[2];
-            }
-            const uint64_t bits = (uint64_t)__double_as_longlong(r2.x);
-            const int prim = (int)(uint32_t)bits, gs = (int)(uint32_t)(bits >> 32);
-            const d3 oc = point - mk(r0.x, r0.y, r1.x);
-            const double bh = dot(oc, dir), cc = dot(oc, oc) - r1.y * r1.y;
-            if (((mask >> (gs & 0xff)) & 1) && (gs >> 8) != skip && bh * bh - cc >= 0 && (bh < 0 || cc < 0)) {
-              double ta, tb;
-              if (quad_roots_unit(bh, cc, ta, tb) == 2) {
-                const double bt = ta > q.tol ? ta : (tb > q.tol ? tb : INFINITY);
-                consider(sv, q, bt, prim, (int)(first + k), gs & 0xff, 0, 0);
-                cut = fmin_raw(q.tmax, q.any.t + 2.0 * q.tol);
-              }
-            }
-#elif ODW_GRID_LEAN_TEST
             // geometry only, from the first 32 bytes of the record (centre, radius); the sphere the ray has just left
             // is known by its record (skip_rec: the interaction keeps the record's index).  Whether the group is
             // relevant, and the solid rule for a sphere listed in a second cell, are asked when the cell is resolved
@@ -418,21 +370,6 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
               const double bh2 = dot(oc2, dir), cc2 = dot(oc2, oc2) - r1.y * r1.y;
               maybe |= (int)(first + k) != skip_rec && bh2 * bh2 - cc2 >= 0 && (bh2 < 0 || cc2 < 0);
             }
-#endif
-#else
-            double2 r0, r1, r2;
-            if (IN_LDS) {
-              const double2* rec = reinterpret_cast<const double2*>(grid_lds + item_off) + 3 * (size_t)(first + k);
-              r0 = rec[0]; r1 = rec[1]; r2 = rec[2];
-            } else {
-              const double2* rec = reinterpret_cast<const double2*>(GD.items) + 3 * (size_t)(first + k);
-              r0 = rec[0]; r1 = rec[1]; r2 = rec[2];
-            }
-            const uint32_t gs = (uint32_t)((uint64_t)__double_as_longlong(r2.x) >> 32);
-            const d3 oc = point - mk(r0.x, r0.y, r1.x);
-            const double bh = dot(oc, dir), cc = dot(oc, oc) - r1.y * r1.y;
-            // (outside the sphere and moving away from its centre: both roots negative)
-            maybe |= ((mask >> (gs & 0xff)) & 1) && (int)(gs >> 8) != skip && bh * bh - cc >= 0 && (bh < 0 || cc < 0);
 #endif
           } else {
             int p;
@@ -456,16 +393,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
     ODW_GTIME(2);
     // ---- D: resolution and interaction of the lanes whose walk has stopped -----------------------------
     ODW_GSTAT(3, __ballot(alive && !walking && !fresh));
-    // Rays handed out in sorted order (ray_order): the lanes of a wave hold neighbouring rays; the interaction may wait
-    // until interact_min lanes are through with their walk (or nobody walks or waits for a resolve any more), so that the
-    // wave sets out on the next segment together (as odw_mesh_kernel does).  Index order: every lane goes on at once.
-    bool go = true;
-    if (SORTED && interact_min > 1u) {
-      const uint64_t busy = __ballot(walking || (alive && pending));
-      const uint64_t done = __ballot(alive && !walking && !fresh && !pending);
-      go = busy == 0ull || (uint32_t)__popcll(done) >= interact_min;
-    }
-    if (alive && !walking && !fresh && (pending || go)) {
+    if (alive && !walking && !fresh) {
       if (pending) {
         // the exact tests of the cell the walk stands in (every primitive listed there), then on or stop
         pending = false;
@@ -514,7 +442,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
         cut = fmin_raw(q.tmax, q.any.t + 2.0 * q.tol);
         ODW_WALK_ADVANCE();
       }
-      if (!walking && go) {
+      if (!walking) {
         ODW_GSTAT(5, __ballot(1));
         if (q.any.prim == 0x7fffffff) {
           ODW_GCOUNT(ODW_CNT_ESCAPED);
@@ -619,8 +547,6 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
     ODW_GTIME(3);
   }
 #undef ODW_WALK_ADVANCE
-#undef refill_min
-#undef interact_min
   // slots of the last block this wave never filled (as in odw_trace_kernel)
   const uint32_t hit_used = hit_state[2];
   const uint64_t hit_base = ((uint64_t)hit_state[1] << 32) | hit_state[0];
@@ -645,30 +571,5 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
     if (s) atomicAdd(P.out.counters + threadIdx.x, (unsigned long long)s);
   }
 }
-
-#if ODW_GRID_SORTED
-// ---- the order rays are handed out in (TraceParams.ray_order), grid launches ------------------------------------------
-// key of ray r = the two uniform numbers its direction is drawn from (azimuth and polar inverse CDFs are monotone in
-// them), 16 bits each, Morton order: Philox alone, no table inversion, no sin / cos.  Sorted by its top bits, the rays of
-// a wave leave the source side by side (equal-probability patches of the beam).
-__device__ __forceinline__ uint32_t grid_spread16(uint32_t v) {        // abcd -> 0a0b0c0d
-  v &= 0xffffu;
-  v = (v | (v << 8)) & 0x00ff00ffu;
-  v = (v | (v << 4)) & 0x0f0f0f0fu;
-  v = (v | (v << 2)) & 0x33333333u;
-  v = (v | (v << 1)) & 0x55555555u;
-  return v;
-}
-__global__ __launch_bounds__(256) void odw_ray_ukey_kernel(uint64_t first, uint64_t n, uint64_t seed,
-                                                           uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const uint64_t ray = first + r;
-  uint32_t c0 = (uint32_t)ray, c1 = (uint32_t)(ray >> 32), c2 = 0u, c3 = 0u;
-  philox4x32_10(c0, c1, c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32));      // (ray_uniforms: u_phi from c0, u_t from c2)
-  keys[r] = grid_spread16(c0 >> 16) | (grid_spread16(c2 >> 16) << 1);
-  vals[r] = (uint32_t)r;
-}
-#endif
 
 }  // namespace odw

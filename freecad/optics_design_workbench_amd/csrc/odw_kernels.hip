@@ -367,43 +367,21 @@ __device__ __forceinline__ int quad_roots_unit(double bh, double c, double& t0, 
 // waves, cache and scheduling effects included).  1 box tests, 2 sphere roots, 3 cylinder / cone side and caps, 4 box
 // faces, 5 trimming tests, 6 normal at the hit, 7 mirror / Snell, 8 ray generation, 9 inverse direction of a segment,
 // 12 sphere (whole candidate pass); grid kernel (library builds, scripts/build_variant.py): 21 the walk's sphere test,
-// 23 the exact roots of a resolved cell.  scripts/gpu_double_profile.sh runs the compiled kernel's.
+// 23 the exact roots of a resolved cell.  ODW_SPEC_OPTS=-DODW_DOUBLE=k builds the compiled kernel's.
 #ifndef ODW_DOUBLE
 #define ODW_DOUBLE 0
 #endif
 __device__ __forceinline__ double opq(double x) { asm volatile("" : "+v"(x)); return x; }
 
-// A/B (round 4): conditions without short-circuit evaluation (compares and scalar ands in a row instead of nests of
-// exec-mask branches with their copies) -- bit 0 box faces, 1 the pick among a primitive's candidates, 2 cylinder side
-// and caps, 3 better()
-#ifndef ODW_SPEC_KEY
-#define ODW_SPEC_KEY 1           // (A/B: 0 = primitive and face as two members of a running minimum)
-#endif
-#ifndef ODW_SPEC_LEANCONS
-#define ODW_SPEC_LEANCONS 1       // (A/B: 0 = every candidate slot of a trimmed primitive goes through consider_spec)
-#endif
-#ifndef ODW_SPEC_CUT
-#define ODW_SPEC_CUT 1            // (A/B: 0 = the end of the search computed anew before every box test)
-#endif
-#ifndef ODW_OTH_LAZY
-#define ODW_OTH_LAZY 1           // (A/B: 0 = the second running minimum kept for every candidate)
-#endif
-#ifndef ODW_FLAT_NOBRANCH
-#define ODW_FLAT_NOBRANCH 15
-#endif
 // ------------------------------------------------------------------------
 struct Best {
   double t;
   int prim, face;
 };
+// (conditions here and in intersect_prim() are written without short-circuit evaluation: compares and scalar ands in a
+//  row instead of nests of exec-mask branches with their copies -- round 4)
 __device__ __forceinline__ bool better(double t, int p, int f, const Best& b) {
-#if ODW_FLAT_NOBRANCH & 8
   return (bool)((int)(t < b.t) | ((int)(t == b.t) & ((int)(p < b.prim) | ((int)(p == b.prim) & (int)(f < b.face)))));
-#else
-  if (t != b.t) return t < b.t;
-  if (p != b.prim) return p < b.prim;
-  return f < b.face;
-#endif
 }
 
 struct Query {
@@ -411,7 +389,7 @@ struct Query {
   double tol, tmax;   // distTol, maxRayLength + distTol
   int medium;
   bool in_medium;     // (compiled kernels) some lane of the wave is inside a medium: the second running minimum is kept
-  double cut;         // (compiled kernels, ODW_SPEC_CUT) min(tmax, nearest + 2 tol): where the search ends, renewed when the nearest changes
+  double cut;         // (compiled kernels) min(tmax, nearest + 2 tol): where the search ends, renewed when the nearest changes
   Best any, oth;
 };
 
@@ -430,7 +408,7 @@ __device__ __forceinline__ void consider(const SceneView& sv, Query& q, double t
   if (!(t > q.tol && t < q.tmax)) return;
   const bool cand_any = better(t, p, face, q.any);
   // (in vacuum the second running minimum would be the first all along: see consider_spec)
-  const bool cand_oth = (!ODW_OTH_LAZY || q.medium >= 0) && (group != q.medium) && better(t, p, face, q.oth);
+  const bool cand_oth = (q.medium >= 0) && (group != q.medium) && better(t, p, face, q.oth);
   if (!cand_any && !cand_oth) return;
   if (cond_cnt) {
     const d3 gp = q.start + q.dn * t;
@@ -499,22 +477,17 @@ __device__ __forceinline__ bool trim_ok(const SceneView& sv, const Query& q, d3 
 template <bool PARAB, class SPEC, int PI>
 __device__ __forceinline__ void consider_spec(const SceneView& sv, Query& q, double t, int face) {
   if (!(t > q.tol && t < q.tmax)) return;
-#if ODW_SPEC_KEY
   // (compiled kernels keep (primitive, face) as ONE word, primitive << 8 | face, in the `face` member: the order of the
   //  pairs is the order of the words -- one integer comparison per running minimum instead of three, one select less
   //  per update; nearest() takes the word apart once per segment)
   const int key = (PI << 8) | face;
 #define ODW_BETTER(B) ((bool)((int)(t < (B).t) | ((int)(t == (B).t) & (int)(key < (B).face))))
-#else
-  const int key = face;
-#define ODW_BETTER(B) better(t, PI, face, B)
-#endif
   const bool cand_any = ODW_BETTER(q.any);
   // (a ray in vacuum: every candidate's group differs from its medium, `oth` would be `any` all along and the rule at
   //  the end of nearest() returns `any` either way -- a wave whose lanes are all in vacuum leaves the second minimum
   //  alone: a uniform branch around its comparison and its selects)
   bool cand_oth = false;
-  if (!ODW_OTH_LAZY || q.in_medium) cand_oth = (SPEC::group(PI) != q.medium) && (!ODW_OTH_LAZY || q.medium >= 0) && ODW_BETTER(q.oth);
+  if (q.in_medium) cand_oth = (SPEC::group(PI) != q.medium) && (q.medium >= 0) && ODW_BETTER(q.oth);
 #undef ODW_BETTER
   if (!cand_any && !cand_oth) return;
   if constexpr (SPEC::cond_cnt(PI) > 0) {
@@ -523,13 +496,8 @@ __device__ __forceinline__ void consider_spec(const SceneView& sv, Query& q, dou
     if (!trim_ok<PARAB, SPEC, SPEC::cond_off(PI), SPEC::cond_off(PI) + SPEC::cond_cnt(PI)>(sv, q, q.start + q.dn * opq(t))) return;
 #endif
   }
-#if ODW_SPEC_KEY
-  if (cand_any) { q.any.t = t; q.any.face = key; if (ODW_SPEC_CUT) q.cut = fmin(q.tmax, t + 2.0 * q.tol); }
+  if (cand_any) { q.any.t = t; q.any.face = key; q.cut = fmin(q.tmax, t + 2.0 * q.tol); }
   if (cand_oth) { q.oth.t = t; q.oth.face = key; }
-#else
-  if (cand_any) { q.any.t = t; q.any.prim = PI; q.any.face = face; }
-  if (cand_oth) { q.oth.t = t; q.oth.prim = PI; q.oth.face = face; }
-#endif
 }
 
 // up to four candidate (t, face) pairs of one primitive, kept in registers
@@ -555,9 +523,6 @@ __device__ __forceinline__ void cand_min2(Cands& c, double t, int f) {
   c.f0 = lt0 ? f : c.f0;
 }
 
-#ifndef ODW_CYL_SIDE_SKIP
-#define ODW_CYL_SIDE_SKIP 1      // (A/B: 0 = every cylinder side by its quadratic)
-#endif
 #ifndef ODW_TORUS_PLAIN
 #define ODW_TORUS_PLAIN 96     // plain distance steps before the curvature bound joins in
 #endif
@@ -650,13 +615,9 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     } else {
     double bt = INFINITY;
     int bf = 0;
-    // (ODW_FLAT_NOBRANCH: the six conditions of a face as one expression without short-circuit evaluation -- six
-    //  compares and five scalar ands in a row instead of a nest of exec-mask branches with their copies)
-#if ODW_FLAT_NOBRANCH & 1
+    // (the six conditions of a face as one expression without short-circuit evaluation -- six compares and five
+    //  scalar ands in a row instead of a nest of exec-mask branches with their copies)
 #define ODW_BOX_OK(A, B, C, D, E, F) (bool)((int)(A) & (int)(B) & (int)(C) & (int)(D) & (int)(E) & (int)(F))
-#else
-#define ODW_BOX_OK(A, B, C, D, E, F) ((A) && (B) && (C) && (D) && (E) && (F))
-#endif
 #define ODW_BOX_FACE(T, FACE, P1, D1, S1, P2, D2, S2)                                         \
     {                                                                                         \
       const double t_ = (T);                                                                  \
@@ -700,7 +661,7 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     // lane of a wave: two plane distances and two squared radii (14 instructions) instead of discriminant, square root,
     // reciprocal and roots (~55).  The margin (1e-9 of R^2: the roots then lie >= 5e-10 R beyond the planes) is far above
     // the roots' rounding; anything closer, a ray parallel to the caps (NaN), cones and paraboloids take the quadratic.
-    constexpr bool side_skip = ODW_CYL_SIDE_SKIP && (SPEC::enabled || !PARAB);
+    constexpr bool side_skip = SPEC::enabled || !PARAB;
     bool side = (fmask & 1) != 0;
     double invz = 0.0;
     if ((fmask & 6) || (side_skip && type == ODW_PRIM_CYLINDER && side)) invz = frcp(d.z);
@@ -717,25 +678,15 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
                                 o.x * d.x + o.y * d.y - k * rz * d.z - f2 * d.z,
                                 o.x * o.x + o.y * o.y - rz * rz - 2.0 * f2 * o.z, t0, t1);
       const double z0 = o.z + t0 * d.z, z1 = o.z + t1 * d.z;
-#if ODW_FLAT_NOBRANCH & 4
       c.t0 = (bool)((int)(nr >= 1) & (int)(z0 >= -tol) & (int)(z0 <= H + tol) & (int)((R1 + k * z0) >= -tol)) ? t0 : c.t0;
       c.t1 = (bool)((int)(nr == 2) & (int)(z1 >= -tol) & (int)(z1 <= H + tol) & (int)((R1 + k * z1) >= -tol)) ? t1 : c.t1;
-#else
-      if (nr >= 1 && z0 >= -tol && z0 <= H + tol && (R1 + k * z0) >= -tol) c.t0 = t0;
-      if (nr == 2 && z1 >= -tol && z1 <= H + tol && (R1 + k * z1) >= -tol) c.t1 = t1;
-#endif
     }
     if (fmask & 6) {
       const double ta = (0.0 - o.z) * invz, tb = (H - o.z) * invz;
       const double xa = o.x + ta * d.x, ya = o.y + ta * d.y;
       const double xb = o.x + tb * d.x, yb = o.y + tb * d.y;
-#if ODW_FLAT_NOBRANCH & 4
       { const bool w_ = (bool)((int)((fmask & 2) != 0) & (int)(R1 > 0) & (int)(xa * xa + ya * ya <= (R1 + tol) * (R1 + tol))); c.t2 = w_ ? ta : c.t2; c.f2 = w_ ? 1 : c.f2; }
       { const bool w_ = (bool)((int)((fmask & 4) != 0) & (int)(R2 > 0) & (int)(xb * xb + yb * yb <= (R2 + tol) * (R2 + tol))); c.t3 = w_ ? tb : c.t3; c.f3 = w_ ? 2 : c.f3; }
-#else
-      if ((fmask & 2) && R1 > 0 && xa * xa + ya * ya <= (R1 + tol) * (R1 + tol)) { c.t2 = ta; c.f2 = 1; }
-      if ((fmask & 4) && R2 > 0 && xb * xb + yb * yb <= (R2 + tol) * (R2 + tol)) { c.t3 = tb; c.f3 = 2; }
-#endif
     }
   } else {  // torus
     if (!(fmask & 1)) return;
@@ -841,11 +792,7 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     // untrimmed: only the nearest admissible candidate can win
     double bt = INFINITY;
     int bf = 0;
-#if ODW_FLAT_NOBRANCH & 2
 #define ODW_PICK(T, F) { const bool w_ = (bool)((int)((T) > tol) & ((int)((T) < bt) | ((int)((T) == bt) & (int)((F) < bf)))); bt = w_ ? (T) : bt; bf = w_ ? (F) : bf; }
-#else
-#define ODW_PICK(T, F) if ((T) > tol && ((T) < bt || ((T) == bt && (F) < bf))) { bt = (T); bf = (F); }
-#endif
     ODW_PICK(c.t0, c.f0)
     ODW_PICK(c.t1, c.f1)
     ODW_PICK(c.t2, c.f2)
@@ -858,13 +805,13 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     // (faces that the boolean left nothing of produce no candidate: their slots are not looked at)
     constexpr int fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
     constexpr bool quadric = SPEC::type(PI) == ODW_PRIM_CYLINDER || SPEC::type(PI) == ODW_PRIM_CONE || SPEC::type(PI) == ODW_PRIM_PARABOLOID;
-    if constexpr (!ODW_SPEC_LEANCONS || !quadric || (fm & 1) != 0) {
+    if constexpr (!quadric || (fm & 1) != 0) {
       consider_spec<PARAB, SPEC, PI>(sv, q, c.t0, c.f0);
       consider_spec<PARAB, SPEC, PI>(sv, q, c.t1, c.f1);
     }
     if constexpr (SPEC::type(PI) != ODW_PRIM_SPHERE) {
-      if constexpr (!ODW_SPEC_LEANCONS || !quadric || (fm & 2) != 0) consider_spec<PARAB, SPEC, PI>(sv, q, c.t2, c.f2);
-      if constexpr (!ODW_SPEC_LEANCONS || !quadric || (fm & 4) != 0) consider_spec<PARAB, SPEC, PI>(sv, q, c.t3, c.f3);
+      if constexpr (!quadric || (fm & 2) != 0) consider_spec<PARAB, SPEC, PI>(sv, q, c.t2, c.f2);
+      if constexpr (!quadric || (fm & 4) != 0) consider_spec<PARAB, SPEC, PI>(sv, q, c.t3, c.f3);
     }
   } else {
 #pragma unroll 1
@@ -999,7 +946,7 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
       if constexpr (SPEC::box_of(PI) != PI) {
         in_box = boxhit[SPEC::box_of(PI)];
       } else {
-        const double cut = (ODW_SPEC_CUT && ODW_SPEC_KEY) ? q.cut : fmin(q.tmax, q.any.t + 2.0 * q.tol);
+        const double cut = q.cut;
         in_box = ray_box(sv.prim_hdr + 8 * PI, oi, inv, cut);
 #if ODW_DOUBLE == 1
         in_box = in_box & ray_box(sv.prim_hdr + 8 * PI, mk(opq(oi.x), oi.y, oi.z), inv, cut);
@@ -1020,7 +967,7 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
     } else if constexpr (SPEC::box_of(PI) == PI) {
       // (skipped for this lane -- not relevant, or the convex solid just left --, but a later primitive may
       //  ask for this box: its own test then)
-      boxhit[PI] = SPEC::box_shared(PI) ? ray_box(sv.prim_hdr + 8 * PI, oi, inv, (ODW_SPEC_CUT && ODW_SPEC_KEY) ? q.cut : fmin(q.tmax, q.any.t + 2.0 * q.tol)) : false;
+      boxhit[PI] = SPEC::box_shared(PI) ? ray_box(sv.prim_hdr + 8 * PI, oi, inv, q.cut) : false;
     }
   }
 }
@@ -1176,7 +1123,7 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
       }
     }
   }
-  if constexpr (SPEC::enabled && ODW_SPEC_KEY) {
+  if constexpr (SPEC::enabled) {
     // (consider_spec keeps primitive << 8 | face in the `face` member)
     if (q.any.face == 0x7fffffff) return -1;
     const bool use_oth_ = q.oth.face != 0x7fffffff && q.oth.t < q.any.t + 2.0 * q.tol;

@@ -38,12 +38,6 @@ namespace odw {
 #define ODW_MESH_WAVES 3         // waves per SIMD the register allocation aims at (LDS per block: stacks 24 KB + rings 14 KB;
                                  // 4: the hot loops spill -- 16.5 against 11.55 ms)
 #endif
-#ifndef ODW_MESH_CAND_TRIPS
-#define ODW_MESH_CAND_TRIPS 0    // trips of four records per lane and leaf round; 0: all of the visit's candidates at once.
-                                 // (round 3: 0: 13.1 / 18.3 / 25.1 ms per 1e7 rays at 4e3 / 6.5e4 / 1e6 facets, 3: 12.9 / 16.9 /
-                                 //  24.4 -- a lane with 40 candidates held the lanes with 8; with sorted rays the lanes of a wave
-                                 //  hold about the same number: 0: 7.65 / 11.55, 3: 7.95 / 12.4, 4: 7.93 / 12.0, 6: 8.36 / 12.4)
-#endif
 #ifndef ODW_MESH_CONES
 #define ODW_MESH_CONES 1         // rays inside a strictly convex tessellated solid drop the slots whose facets all face them
                                  // (1e7 rays, 4e3 / 6.5e4 / 1e6 facets, ms: 4.13 / 4.98 / 7.47 without, 3.77 / 4.34 / 5.96 with:
@@ -83,21 +77,14 @@ namespace odw {
 #define ODW_MCOUNT(k) atomicAdd(&wave_cnt[(k)], 1u)
 
 // what a lane does at the end of a segment (ray.py:120-268): absorption along the segment, normal, hit row, the new
-// direction, the solid a convex facet lets the ray leave.  A function of its own so that it can be kept out of line
-// (ODW_MESH_INTERACT_INLINE=0; kargs: the kernel's argument segment, as record_hit_flat) -- measured in round 5
-// (1e7 rays, 4e3 / 6.5e4 / 1e6 facets, ms): inlined 4.11 / 4.93 / 7.36 with 47 spilled registers, out of line 4.47 / 5.28 /
-// 7.70 with 22 (the call moves ~50 registers per segment and lane, the spills it saves were not in the hot loops); out of
-// line at four waves per SIMD (ODW_MESH_WAVES=4, still 96 spilled) 5.47 / 6.45 / 9.12.
-#ifndef ODW_MESH_INTERACT_INLINE
-#define ODW_MESH_INTERACT_INLINE 1
-#endif
+// direction, the solid a convex facet lets the ray leave.  A function of its own (kargs: the kernel's argument segment,
+// as record_hit_flat), inlined -- measured out of line in round 5 (1e7 rays, 4e3 / 6.5e4 / 1e6 facets, ms): inlined
+// 4.11 / 4.93 / 7.36 with 47 spilled registers, out of line 4.47 / 5.28 / 7.70 with 22 (the call moves ~50 registers per
+// segment and lane, the spills it saves were not in the hot loops); out of line at four waves per SIMD
+// (ODW_MESH_WAVES=4, still 96 spilled) 5.47 / 6.45 / 9.12.
 struct MeshRay { d3 point, dir; double power; int medium, seq, skip, inside; bool alive; };
 template <bool STOCH>
-#if ODW_MESH_INTERACT_INLINE
 __device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
 MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, int seq, int nint, uint64_t i, double t_hit, int prim,
                       int face, uint32_t* wave_cnt, volatile uint32_t* hit_state, const double* group_f64, const int32_t* group_i32,
                       const double* group_gdir) {
@@ -209,14 +196,10 @@ MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, 
   return r;
 }
 
-// an analytic primitive listed in a leaf (a screen behind the mesh), out of line for the same reason: intersect_prim<>
-// holds every kind of primitive, the quartic of the torus included
+// an analytic primitive listed in a leaf (a screen behind the mesh), a function of its own for the same reason:
+// intersect_prim<> holds every kind of primitive, the quartic of the torus included
 struct MeshBest { Best any, oth; };
-#if ODW_MESH_INTERACT_INLINE
 __device__ __forceinline__
-#else
-__device__ __noinline__
-#endif
 MeshBest mesh_intersect_prim(ckargs kargs, d3 start, d3 dn, double tol, double tmax, int medium, Best any, Best oth, int p) {
   const uint64_t a_ = (uint64_t)(uintptr_t)kargs;
   const uint64_t u_ = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a_ >> 32)) << 32) |
@@ -589,13 +572,7 @@ __global__ __launch_bounds__(ODW_MESH_THREADS, ODW_MESH_WAVES) void odw_mesh_ker
         return U >= -ea && V >= -ea && U + V <= ad + 2.0f * ea;
       };
       uint64_t pass = 0;
-#if ODW_MESH_CAND_TRIPS > 0
-      // at most ODW_MESH_CAND_TRIPS trips per round: a lane with many candidates goes on in the next round and does
-      // not hold the lanes with few (they walk or interact meanwhile)
-      for (int trip = 0; cand && trip < ODW_MESH_CAND_TRIPS; ++trip) {
-#else
       while (cand) {
-#endif
         // four records per trip: twelve loads in flight before the first is used (the trip is a round trip to the
         // cache: fewer, fuller trips)
         int kk[4];

@@ -732,7 +732,7 @@ int odw_hits_select(odw_ctx* ctx, int32_t group, uint64_t* n_rows, uint64_t* n_l
     const unsigned kgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((used + 255) / 256, (uint64_t)ctx->n_cu * 8));
     size_t tmp_bytes = 0;
     // first the route without a sort (ph_mark_kernel): it gives up when a ray has two selected rows
-    static const bool sort_only = getenv("ODW_SELECT_SORT") != nullptr;        // (A/B runs)
+    static const bool sort_only = getenv("ODW_SELECT_SORT") != nullptr;        // (tests: the sort route by itself)
     const bool bounded = ctx->hit_ray_end && ctx->hit_ray_end < (1ull << 48) && ctx->hit_ray_begin < ctx->hit_ray_end;
     const uint64_t ray0 = bounded ? ctx->hit_ray_begin : 0, n_rays = bounded ? ctx->hit_ray_end - ray0 : 0;
     if (!sort_only && n_rays && n_rays <= (1ull << 28)) {
@@ -774,8 +774,7 @@ int odw_hits_select(odw_ctx* ctx, int32_t group, uint64_t* n_rows, uint64_t* n_l
       }
       HIPCHK(ctx, hipMemsetAsync(ctx->ph_small.p, 0, 2 * sizeof(uint64_t), ctx->stream));      // the counts again, with the sort
     }
-    static const bool keys64 = getenv("ODW_SELECT_KEYS64") != nullptr;        // (A/B runs)
-    if (bits + 1 <= 32 && !keys64) {
+    if (bits + 1 <= 32) {
       uint32_t* k32_in = (uint32_t*)k_in;
       uint32_t* k32_out = (uint32_t*)k_out;
       hipLaunchKernelGGL(ph_keys_kernel<uint32_t>, dim3(kgrid), dim3(256), 0, ctx->stream, (const odw_hit*)ctx->hits.p, used,
@@ -822,10 +821,9 @@ int odw_hits_columns(odw_ctx* ctx, double* points, double* directions, double* p
   if (m > capacity) return fail(ctx, ODW_ERR_CAPACITY, "odw_hits_columns: output arrays too small");
   // Page-locked destinations (odw_host_alloc: the run loop's arrays) are written by the kernel itself, across PCIe:
   // no staging buffer, no copy commands -- five copies of 30 - 100 MB through one copy engine moved 30 GB/s, the kernel's
-  // stores fill the link (ODW_COLUMNS_DIRECT=0: the staged route, also taken for pageable destinations)
+  // stores fill the link (pageable destinations take the staged route)
   {
-    static const bool direct_off = [] { const char* e = getenv("ODW_COLUMNS_DIRECT"); return e && e[0] == '0'; }();
-    bool direct = !direct_off;
+    bool direct = true;
     void* dev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     void* host[5] = {points, directions, powers, is_entering, ray_index};
     for (int k = 0; k < 5 && direct; ++k) {

@@ -353,7 +353,7 @@ def _run_overlapped(store, tr, baked, rpi, raysPerLaunch, seed, enabled, compile
   are known at launch time, so the run traces exactly what the one-launch-at-a-time loop traces."""
   from concurrent.futures import ThreadPoolExecutor
   src, scene, bsrc, lim = baked
-  n_lanes = max(2, int(os.environ.get('ODW_RUN_LANES', '3')))
+  n_lanes = 3
   lanes = [tr] + [Tracer(tr.device, referenceStrict=tr.referenceStrict) for _ in range(n_lanes - 1)]
   store_lock = threading.Lock()
   try:

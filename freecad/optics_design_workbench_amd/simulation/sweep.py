@@ -226,7 +226,6 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
   batch_ok = [True]
   samples = {}
   tail_size = [None]
-  taper = int(os.environ.get('ODW_SWEEP_TAPER', '0'))
 
   def measureInto(t, scene, k):
     t_m = time.perf_counter() if clock is not None else 0.0
@@ -394,8 +393,8 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
     order = []                           # contexts in the order their groups were launched
     pos, turn = 0, 0
     # host work nobody waits for is done when the GPU has been fed: the fits of a group whose answers are all on the host
-    # (its context is free at once), and the bake of the group that goes next (ODW_SWEEP_DEFER=0: both where they used to be)
-    defer = os.environ.get('ODW_SWEEP_DEFER', '1') != '0' and all(hasattr(measures[name], 'batched') for name in names)
+    # (its context is free at once), and the bake of the group that goes next
+    defer = all(hasattr(measures[name], 'batched') for name in names)
     deferred = []                        # (ks, batch) whose fits are still to do
     ahead = [None]                       # (ks, baked) of the next group, baked in an idle moment
 
@@ -410,13 +409,13 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
       busy[lane] = dict(ks=ks, batch=DeviceHitsBatch.begin(t, len(ks)), capacity=capacity)
       order.append(lane)
 
-    def sampledGroups(wait_lane=None):
+    def sampledGroups():
       """contexts whose sample has arrived: counters checked (a segment without room: traced again), planes searched
       together, the rest of the chain enqueued"""
       ready = []
       for lane in list(order):
         g = busy[lane]
-        if g['batch']._stage == 'begun' and g['batch'].sampled(wait=(lane == wait_lane)):
+        if g['batch']._stage == 'begun' and g['batch'].sampled():
           t = lanes[lane]
           cnt = t.counters()
           Tracer.raiseForRayErrors(cnt)
@@ -437,11 +436,11 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
           busy[lane]['batch'].enqueueMeasure(keep=int(keepSample or 0), **(request or {}))
       return bool(ready)
 
-    def measuredGroups(wait_lane=None):
+    def measuredGroups():
       done = False
       for lane in list(order):
         g = busy[lane]
-        if g['batch']._stage == 'measuring' and g['batch'].measured(wait=(lane == wait_lane)):
+        if g['batch']._stage == 'measuring' and g['batch'].measured():
           if defer and g['batch'].detached():
             deferred.append((g['ks'], g['batch']))
           else:
@@ -457,15 +456,12 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
       if ahead[0] is not None:
         out, ahead[0] = ahead[0], None
         return out
-      # (the first groups are small, so that chains start early; the last ones shrink, so that the contexts end together.
-      #  ODW_SWEEP_TAPER = d > 0: every group of the tail takes 1 / d of what is left; 0: the tail in equal groups -- measured
-      #  better: small launches are worse launches)
+      # (the first groups are small, so that chains start early; the last ones shrink, so that the contexts end together:
+      #  the tail in equal groups -- measured better than groups that take a share of what is left each: small launches are
+      #  worse launches)
       left = len(mine) - pos
-      if group_size > 2 and left < group_size * len(lanes):
-        if taper > 0:
-          tail_size[0] = max(2, -(-left // taper))
-        elif tail_size[0] is None:
-          tail_size[0] = max(2, -(-left // len(lanes)))
+      if group_size > 2 and left < group_size * len(lanes) and tail_size[0] is None:
+        tail_size[0] = max(2, -(-left // len(lanes)))
       size = group_size if group_size <= 2 else min(group_size, 2 << turn if turn < 3 else group_size, tail_size[0] or group_size)
       ks = mine[pos:pos + size]
       turn += 1
@@ -514,15 +510,8 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
         # piece blocks the thread while a younger chain's sample lies ready -- its plane search, its measure and the launch
         # that needs its context all start late: sweeps of 65 instead of 59 ms, every other one, measured.)
         t_w = time.perf_counter()
-        if os.environ.get('ODW_SWEEP_WAIT_OLDEST') == '1':
-          lane = order[0]
-          if busy[lane]['batch']._stage == 'begun':
-            sampledGroups(wait_lane=lane)
-          else:
-            measuredGroups(wait_lane=lane)
-        else:
-          while not (measuredGroups() or sampledGroups()):
-            time.sleep(2e-5)
+        while not (measuredGroups() or sampledGroups()):
+          time.sleep(2e-5)
         mark('wait', t_w)
 
   # Batch launches (Tracer.setSceneBatch / traceBatch): the values a context gets at a time are baked together and traced
@@ -545,8 +534,6 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
     # (ranks that share one device -- a node rehearsed on one GPU -- share its memory too, and ask at the same moment)
     budget /= max(1, int(os.environ.get('ODW_RANKS_PER_DEVICE', '1')))
     group_size = max(1, min(group_size, int(budget / len(lanes) // per_value)))
-  if os.environ.get('ODW_SWEEP_BATCH'):
-    group_size = max(1, int(os.environ['ODW_SWEEP_BATCH'])) if group_size > 1 else 1
   switch_interval = sys.getswitchinterval()
   if group_size <= 1 and len(lanes) > 1:
     # values one by one: measuring threads, one per context (batch launches are driven as chains from this thread alone)
@@ -555,7 +542,7 @@ def parameterSweep(doc, setValue, values, *, rays, measure=calcFwhm, seed=DEFAUL
   if pool is not None:
     # (threads that alternate between short library calls and a few lines of Python hand the interpreter lock to
     #  each other all the time; with the default 5 ms a thread that comes back from a 20 us call can wait that long)
-    sys.setswitchinterval(float(os.environ.get('ODW_SWITCH_INTERVAL', '2e-4')))
+    sys.setswitchinterval(2e-4)
   try:
     if group_size > 1:
       sweepBatched(group_size)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """another build of the HIP library with extra compiler flags, for A/B runs on the GPU box:
    python scripts/build_variant.py <name> [-DFLAG=VALUE ...]   ->  build/libodw_<name>.so
-(picked up through ODW_TRACE_LIB, scripts/try_variants.sh runs bench.py with every build/libodw_*.so)"""
+(picked up through ODW_TRACE_LIB: ODW_TRACE_LIB=build/libodw_<name>.so python bench.py)"""
 import os
 import subprocess
 import sys

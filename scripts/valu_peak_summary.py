@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""profiles/r03/valu_peak.json from the outputs of scripts/gpu_r3_valu.sh (gpurun_out/r03/):
+"""profiles/r03/valu_peak.json from the outputs of the round-3 runs of scripts/valu_peak and scripts/valu_sel:
 the instruction-class costs of the vector ALU of gfx950 at 4 waves per SIMD, 256-thread blocks, every CU busy
 (scripts/valu_peak.hip, scripts/valu_sel.hip), with the SQ counters of the same streams beside them.
 
