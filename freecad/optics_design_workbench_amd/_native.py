@@ -22,10 +22,11 @@ LIB_PATH = os.path.join(CSRC, 'libodw_trace.so')
 _SOURCES = ['odw_capi.hip', 'odw_kernels.hip', 'odw_grid.hip', 'odw_mesh.hip', 'odw_posthoc.hip', 'odw_posthoc_batch.hip', 'odw_spec.hip', 'odw_device.h']
 _HEADER = os.path.normpath(os.path.join(_HERE, '..', '..', 'include', 'odw_trace.h'))
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 CNT_NAMES = ['traced_rays', 'recorded_hits', 'segments', 'escaped', 'died', 'capped',
              'hist_overflow', 'hits_dropped', 'grating_in_medium']
-TRACE_RECORD_HITS, TRACE_HISTOGRAM, TRACE_RECORD_SEGMENTS = 1, 2, 4
+TRACE_RECORD_HITS, TRACE_HISTOGRAM, TRACE_RECORD_SEGMENTS, TRACE_POWER_HISTOGRAM = 1, 2, 4, 8
+POWER_QUANTUM_BITS = 32                   # ODW_POWER_QUANTUM_BITS: a hit's weight is rint(clamp(power, 0, 2^20) * 2^32)
 FLAG_FLIP_NORMAL, FLAG_CONVEX = 1, 2      # ODW_FLAG_* of prim_flags (include/odw_trace.h)
 COMPILE_OFF, COMPILE_STRUCTURE, COMPILE_AUTO = 0, 1, 2
 COMPILE_MODES = {None: 0, False: 0, 'off': 0, 0: 0, 'structure': 1, 1: 1, True: 1, 'auto': 2, 2: 2}
@@ -45,7 +46,8 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_compile_scene', 'odw_compiled_info', 'odw_compile_check', 'odw_build_check', 'odw_hits_columns',
            'odw_upload_scene_batch', 'odw_trace_batch', 'odw_batch_select', 'odw_batch_rows',
            'odw_plane_screen_batch', 'odw_archive_append', 'odw_archive_select', 'odw_archive_reset', 'odw_batch_hits_select', 'odw_batch_hits_sample', 'odw_batch_hits_project', 'odw_batch_hits_bin',
-           'odw_batch_reserve', 'odw_batch_hits_begin', 'odw_batch_hits_sampled', 'odw_batch_hits_measure', 'odw_batch_hits_measured']
+           'odw_batch_reserve', 'odw_batch_hits_begin', 'odw_batch_hits_sampled', 'odw_batch_hits_measure', 'odw_batch_hits_measured',
+           'odw_enable_power_histogram', 'odw_fetch_power_histogram', 'odw_device_power_histogram', 'odw_hits_bin_power', 'odw_compiled_power_info']
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)

@@ -8,6 +8,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <atomic>
 #include <array>
 #include <cmath>
 #include <cstdio>
@@ -109,6 +110,7 @@ struct odw_ctx {
   DeviceDetector h_det;
   DevBuf hits, hit_count, chunk_counter;
   // ONE block holds what ranks sum: [kResultsHead words: the ODW_CNT_COUNT counters, padded] [n_bins histogram words]
+  // [power_on: n_bins words of the power plane]
   // -- a multi-GPU job reduces it with a single collective (odw_device_results); `counters` and `hist` are views into it
   DevBuf results, hist, counters;
   DevBuf segs, seg_count;                  // RecordRays segment list
@@ -138,6 +140,7 @@ struct odw_ctx {
   DeviceEmitter h_emitter;
   bool emitter_active = false;   // the most recently uploaded source is a surface source
   uint64_t hit_capacity = 0, n_bins = 0;   // hit_capacity: rows the caller asked for
+  bool power_on = false;                   // odw_enable_power_histogram: n_bins words of hit weights directly behind the histogram
   uint64_t hit_slots = 0;                  // rows allocated (capacity + slack for block reservations)
   // batch launches (odw_upload_scene_batch / odw_trace_batch): the value tables of batch_n scenes of one structure side by
   // side, one segment of the batch's hit list and one pair of counters per scene.  odw_batch_select makes a segment the
@@ -156,6 +159,10 @@ struct odw_ctx {
   std::string batch_spec_text;             // the structure all scenes of the batch share (compiled kernels)
   hipFunction_t spec_batch_fn = nullptr;   // the scene-compiled kernel's BATCH variant (bound on the first batch launch)
   bool spec_batch_failed = false;          // ... could not be built for the bound structure: generic kernels for its batches
+  hipFunction_t spec_power_fn = nullptr;   // ... and its POWER variant (the detector's power plane; bound on the first weighted launch)
+  bool spec_power_failed = false;          // ... was asked for and is not to be asked for again for this binding (could not be built)
+  const std::atomic<bool>* spec_power_wait = nullptr;   // ODW_COMPILE_AUTO: "done" of the variant's compilation under way (the job
+                                           // stays in the process-wide table): weighted launches look at this flag only
   DevBuf own_hits, own_hit_count;
   uint64_t own_capacity = 0, own_slots = 0, own_ray_begin = 0, own_ray_end = 0;
   // a run's rows kept in HBM beyond the launches that recorded them (odw_archive_append / odw_archive_select)
@@ -285,8 +292,9 @@ void release(DevBuf& b) {
 constexpr size_t kResultsHead = 16;      // words in front of the histogram (128 B: the bins keep their alignment)
 static_assert(ODW_CNT_COUNT <= kResultsHead, "counters must fit the head of the results block");
 
-// the results block for a histogram of n_bins bins; the counters survive a reallocation
-int ensure_results(odw_ctx* ctx, uint64_t n_bins);
+// the results block for n_words words behind the counters (a histogram of that many bins, or a histogram and its power
+// plane); the counters and the first keep_words of those words survive a reallocation
+int ensure_results(odw_ctx* ctx, uint64_t n_words, uint64_t keep_words = 0);
 // ctx->hits / hit_count are views of a batch segment (odw_batch_select): give the context its own list back
 void batch_unselect(odw_ctx* ctx);
 // room for the post-hoc chain of a batch (odw_posthoc_batch.hip)
@@ -1335,6 +1343,8 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       return fail(ctx, ODW_ERR_INVALID, "ODW_TRACE_RECORD_SEGMENTS: ray index or max_intersections beyond the row tag");
   }
   if ((flags & ODW_TRACE_HISTOGRAM) && !ctx->P.det_enabled) flags &= ~ODW_TRACE_HISTOGRAM;
+  // (the kernels add to the words behind the histogram under this flag: never without a plane there)
+  if (!(flags & ODW_TRACE_HISTOGRAM) || !ctx->power_on) flags &= ~(uint32_t)ODW_TRACE_POWER_HISTOGRAM;
   TraceParams& P = ctx->P;
   const bool batch = ctx->batch_launch;
   std::memset(&P.batch, 0, sizeof P.batch);
@@ -1343,7 +1353,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     if (P.scene.n_nodes || P.grid.nx > 0 || ctx->n_samplers > 0 || explicit_rays || (flags & ODW_TRACE_RECORD_SEGMENTS))
       return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: batches are traced by the flat kernels (analytic scenes of up to 64 "
                                             "primitives, no stochastic surfaces, no segment rows)");
-    flags &= ~(uint32_t)ODW_TRACE_HISTOGRAM;          // (one histogram cannot serve several scenes)
+    flags &= ~(uint32_t)(ODW_TRACE_HISTOGRAM | ODW_TRACE_POWER_HISTOGRAM);   // (one histogram cannot serve several scenes)
   }
   P.first_ray = first;
   P.n_rays = n;
@@ -1378,19 +1388,37 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   constexpr int grid_mult = 8;
   // big analytic scenes: grid kernel (no stochastic surfaces, no segment rows: those stay with the BVH kernels)
   // a scene compiled against its structure (odw_spec.hip): its own kernel, whatever else was built for it
+  const bool pw = (flags & ODW_TRACE_POWER_HISTOGRAM) != 0;     // the <..., POWER = true> instantiation of whichever kernel runs
+  if (pw && ctx->spec_fn && !ctx->spec_power_fn && !ctx->spec_power_failed &&
+      !(ctx->spec_power_wait && !ctx->spec_power_wait->load())) {
+    // the compiled kernel's POWER variant: bound on the first weighted launch of the structure (a compilation of its own,
+    // cached like the other).  ODW_COMPILE_STRUCTURE: that launch waits for it.  ODW_COMPILE_AUTO: the structure has earned
+    // its compilation already (its single-scene kernel is bound), so the variant's starts at once on a thread, weighted
+    // launches run the generic POWER kernel and look at the job's flag only, and the first one after it has finished binds
+    // it.  One attempt per binding: a variant that cannot be built is not asked for again, and its failure does not become
+    // the error of a launch that succeeds on the generic kernel
+    const std::string keep_err = ctx->err;
+    const bool waited = ctx->spec_power_wait != nullptr;
+    ctx->spec_power_wait = nullptr;
+    if (spec_bind(ctx, kSpecPower) != ODW_OK || (!ctx->spec_power_fn && (waited || !ctx->spec_power_wait))) {
+      ctx->spec_power_fn = nullptr;
+      ctx->spec_power_failed = true;
+      ctx->err = keep_err;
+    }
+  }
   if (batch && ctx->spec_fn && !ctx->spec_batch_fn && !ctx->spec_batch_failed) {
     // the compiled kernel's BATCH variant: bound on the first batch launch of the structure (a compilation of its own,
     // cached like the other; odw_compile_scene's mode decides, as for single launches).  A variant that cannot be built
     // is not tried again for this binding, and its failure does not become the error of a launch that succeeds on the
     // generic kernel
     const std::string keep_err = ctx->err;
-    if (spec_bind(ctx, true) != ODW_OK) {
+    if (spec_bind(ctx, kSpecBatch) != ODW_OK) {
       ctx->spec_batch_fn = nullptr;
       ctx->spec_batch_failed = true;
       ctx->err = keep_err;
     }
   }
-  const bool use_spec = (batch ? ctx->spec_batch_fn != nullptr : ctx->spec_fn != nullptr) && ctx->spec_lean == ctx->lean &&
+  const bool use_spec = (batch ? ctx->spec_batch_fn != nullptr : pw ? ctx->spec_power_fn != nullptr : ctx->spec_fn != nullptr) && ctx->spec_lean == ctx->lean &&
                         ctx->spec_stoch == (ctx->n_samplers > 0) && !(flags & ODW_TRACE_RECORD_SEGMENTS);
   const bool use_grid = !use_spec && P.grid.nx > 0 && ctx->n_samplers == 0 && !(flags & ODW_TRACE_RECORD_SEGMENTS);
   // Rays per hand-out unit.  A launch should hold many chunks per resident wave: with about one each -- 1e7 rays in
@@ -1478,7 +1506,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     if (rc) return rc;
   }
   if (use_spec) {
-    int rc = spec_launch(ctx, grid, batch);
+    int rc = spec_launch(ctx, grid, batch ? ctx->spec_batch_fn : pw ? ctx->spec_power_fn : ctx->spec_fn);
     if (rc) return rc;
   } else if (batch) {
     if (ctx->lean) hipLaunchKernelGGL((odw_trace_kernel<false, false, false, true, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
@@ -1486,42 +1514,52 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   } else if (use_grid) {
     const dim3 gb((unsigned)grid_blocks);
     const size_t glds = P.grid.lds_bytes;
-#define ODW_GRID_LAUNCH(S, L)                                                                                    \
+#define ODW_GRID_LAUNCH_(S, L, W)                                                                                 \
     do {                                                                                                       \
       /* (once per device and instantiation: a second context on another GPU of the process needs its own) */  \
       static uint64_t attr_set = 0;                                                                            \
       const uint64_t dev_bit = 1ull << (ctx->device & 63);                                                     \
       if (!(attr_set & dev_bit)) {                                                                             \
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&odw_grid_kernel<S, L>),                 \
+        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&odw_grid_kernel<S, L, W>),              \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));   /* + 4.5 KB static */ \
         attr_set |= dev_bit;                                                                                   \
       }                                                                                                        \
-      hipLaunchKernelGGL((odw_grid_kernel<S, L>), gb, dim3(ODW_GRID_THREADS), glds, ctx->stream, P);           \
+      hipLaunchKernelGGL((odw_grid_kernel<S, L, W>), gb, dim3(ODW_GRID_THREADS), glds, ctx->stream, P);        \
     } while (0)
+#define ODW_GRID_LAUNCH(S, L) do { if (pw) ODW_GRID_LAUNCH_(S, L, true); else ODW_GRID_LAUNCH_(S, L, false); } while (0)
     if (P.grid.spheres) { if (P.grid.in_lds) ODW_GRID_LAUNCH(true, true); else ODW_GRID_LAUNCH(true, false); }
     else { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true); else ODW_GRID_LAUNCH(false, false); }
 #undef ODW_GRID_LAUNCH
+#undef ODW_GRID_LAUNCH_
   } else if (use_mesh) {
     const size_t mlds = (size_t)ODW_MESH_STACK * ODW_MESH_THREADS * 2 * sizeof(int) +
                         (size_t)ODW_MESH_BLOCK_WAVES * (ODW_MESH_WAVE_WORDS * sizeof(uint32_t) + ODW_MESH_RING_DOUBLES * sizeof(double));
-    if (stoch) hipLaunchKernelGGL(odw_mesh_kernel<true>, dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
-    else hipLaunchKernelGGL(odw_mesh_kernel<false>, dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
+#define ODW_TRACE_LAUNCH(lds_bytes, ...)                                                                                          \
+    do {                                                                                                                        \
+      if (pw) hipLaunchKernelGGL((odw_trace_kernel<__VA_ARGS__, false, true>), dim3(grid), dim3(256), lds_bytes, ctx->stream, P); \
+      else hipLaunchKernelGGL((odw_trace_kernel<__VA_ARGS__, false, false>), dim3(grid), dim3(256), lds_bytes, ctx->stream, P);   \
+    } while (0)
+    if (stoch) { if (pw) hipLaunchKernelGGL((odw_mesh_kernel<true, true>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
+                 else hipLaunchKernelGGL((odw_mesh_kernel<true, false>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P); }
+    else { if (pw) hipLaunchKernelGGL((odw_mesh_kernel<false, true>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
+           else hipLaunchKernelGGL((odw_mesh_kernel<false, false>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P); }
   } else if (flags & ODW_TRACE_RECORD_SEGMENTS) {
     if (P.scene.n_nodes) {
-      if (stoch) hipLaunchKernelGGL((odw_trace_kernel<true, true, true>), dim3(grid), dim3(256), lds, ctx->stream, P);
-      else hipLaunchKernelGGL((odw_trace_kernel<true, false, true>), dim3(grid), dim3(256), lds, ctx->stream, P);
+      if (stoch) ODW_TRACE_LAUNCH(lds, true, true, true, false);
+      else ODW_TRACE_LAUNCH(lds, true, false, true, false);
     } else {
-      if (stoch) hipLaunchKernelGGL((odw_trace_kernel<false, true, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
-      else hipLaunchKernelGGL((odw_trace_kernel<false, false, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
+      if (stoch) ODW_TRACE_LAUNCH(0, false, true, true, false);
+      else ODW_TRACE_LAUNCH(0, false, false, true, false);
     }
   } else if (P.scene.n_nodes) {
-    if (stoch) hipLaunchKernelGGL((odw_trace_kernel<true, true, false>), dim3(grid), dim3(256), lds, ctx->stream, P);
-    else hipLaunchKernelGGL((odw_trace_kernel<true, false, false>), dim3(grid), dim3(256), lds, ctx->stream, P);
+    if (stoch) ODW_TRACE_LAUNCH(lds, true, true, false, false);
+    else ODW_TRACE_LAUNCH(lds, true, false, false, false);
   } else {
-    if (stoch) hipLaunchKernelGGL((odw_trace_kernel<false, true, false>), dim3(grid), dim3(256), 0, ctx->stream, P);
-    else if (ctx->lean) hipLaunchKernelGGL((odw_trace_kernel<false, false, false, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
-    else hipLaunchKernelGGL((odw_trace_kernel<false, false, false>), dim3(grid), dim3(256), 0, ctx->stream, P);
+    if (stoch) ODW_TRACE_LAUNCH(0, false, true, false, false);
+    else if (ctx->lean) ODW_TRACE_LAUNCH(0, false, false, false, true);
+    else ODW_TRACE_LAUNCH(0, false, false, false, false);
   }
+#undef ODW_TRACE_LAUNCH
   HIPCHK(ctx, hipGetLastError());
   if (ctx->timing) {
     HIPCHK(ctx, hipEventRecord(ev.second, ctx->stream));
@@ -1555,7 +1593,7 @@ int odw_abi_version(void) { return ODW_ABI_VERSION; }
 const char* odw_last_error(const odw_ctx* ctx) { return ctx ? ctx->err.c_str() : g_error.c_str(); }
 
 namespace {
-int ensure_results(odw_ctx* ctx, uint64_t n_bins) {
+int ensure_results(odw_ctx* ctx, uint64_t n_bins, uint64_t keep_words) {
   const size_t bins = n_bins > 2 ? (size_t)n_bins : 2;
   const size_t need = (kResultsHead + bins) * sizeof(uint64_t);
   if (!ctx->results.p || ctx->results.bytes < need) {
@@ -1564,7 +1602,8 @@ int ensure_results(odw_ctx* ctx, uint64_t n_bins) {
     fresh.bytes = need;
     if (ctx->results.p) {            // a launch may still be writing the old block; its counters move over
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-      HIPCHK(ctx, hipMemcpyAsync(fresh.p, ctx->results.p, kResultsHead * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
+      const size_t keep = std::min((size_t)(kResultsHead + keep_words) * sizeof(uint64_t), ctx->results.bytes);
+      HIPCHK(ctx, hipMemcpyAsync(fresh.p, ctx->results.p, keep, hipMemcpyDeviceToDevice, ctx->stream));
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
       release(ctx->results);
     } else {
@@ -1886,6 +1925,12 @@ int odw_compiled_info(odw_ctx* ctx, int32_t* bound, double* compile_seconds, int
   if (bound) *bound = (ctx->spec_fn && !ctx->spec_dirty && !ctx->bvh_dirty) ? ctx->compile_mode : 0;
   if (compile_seconds) *compile_seconds = ctx->spec_seconds;
   if (cache_hit) *cache_hit = ctx->spec_cache_hit;
+  return ODW_OK;
+}
+
+int odw_compiled_power_info(odw_ctx* ctx, int32_t* bound) {
+  if (!ctx || !bound) return fail(ctx, ODW_ERR_INVALID, "odw_compiled_power_info: bad argument");
+  *bound = (ctx->spec_fn && ctx->spec_power_fn && !ctx->spec_dirty && !ctx->bvh_dirty) ? ctx->compile_mode : 0;
   return ODW_OK;
 }
 
@@ -2290,6 +2335,7 @@ int odw_set_detector(odw_ctx* ctx, const odw_detector_desc* det) {
   if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_detector: null ctx");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   DeviceDetector& d = ctx->h_det;
+  ctx->power_on = false;                 // (the power plane belongs to one detector: enabled again after every call)
   if (!det) { d.enabled = 0; ctx->P.det_enabled = 0; ctx->n_bins = 0; return ODW_OK; }
   if (det->nx <= 0 || det->ny <= 0 || !(det->x_hi > det->x_lo) || !(det->y_hi > det->y_lo))
     return fail(ctx, ODW_ERR_INVALID, "odw_set_detector: bad window");
@@ -2743,7 +2789,7 @@ int odw_reset_results(odw_ctx* ctx) {
   HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, ODW_CNT_COUNT * sizeof(uint64_t), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->hit_count.p, 0, 2 * sizeof(uint64_t), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->seg_count.p, 0, sizeof(uint64_t), ctx->stream));
-  if (ctx->n_bins) HIPCHK(ctx, hipMemsetAsync(ctx->hist.p, 0, ctx->n_bins * sizeof(uint64_t), ctx->stream));
+  if (ctx->n_bins) HIPCHK(ctx, hipMemsetAsync(ctx->hist.p, 0, ctx->n_bins * (ctx->power_on ? 2 : 1) * sizeof(uint64_t), ctx->stream));
   return ODW_OK;
 }
 
@@ -2983,6 +3029,39 @@ int odw_fetch_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins) {
   return ODW_OK;
 }
 
+int odw_enable_power_histogram(odw_ctx* ctx, int on) {
+  if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: null ctx");
+  if (!on) { ctx->power_on = false; return ODW_OK; }
+  if (!ctx->P.det_enabled || ctx->n_bins == 0) return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: odw_set_detector first");
+  if (ctx->n_bins >= (1ull << 31)) return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: a power plane takes fewer than 2^31 bins");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // a running launch may still write the old block
+  int rc = ensure_results(ctx, 2 * ctx->n_bins, ctx->n_bins);
+  if (rc) return rc;
+  HIPCHK(ctx, hipMemsetAsync((uint64_t*)ctx->hist.p + ctx->n_bins, 0, ctx->n_bins * sizeof(uint64_t), ctx->stream));
+  ctx->power_on = true;
+  return ODW_OK;
+}
+
+int odw_fetch_power_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins) {
+  if (!ctx || !out) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_power_histogram: bad argument");
+  if (!ctx->power_on) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_power_histogram: no power plane (odw_enable_power_histogram)");
+  if (n_bins != ctx->n_bins || n_bins == 0) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_power_histogram: bin count mismatch");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<uint64_t> counts(n_bins);
+  HIPCHK(ctx, hipMemcpyAsync(counts.data(), ctx->hist.p, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out, (uint64_t*)ctx->hist.p + n_bins, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  // a bin of >= 2^32 hits may hold more than 2^64 quanta: its sum may have wrapped, nothing is handed out
+  for (uint64_t k = 0; k < n_bins; ++k)
+    if (counts[k] >> 32) {
+      std::memset(out, 0, n_bins * sizeof(uint64_t));
+      return fail(ctx, ODW_ERR_CAPACITY, "odw_fetch_power_histogram: bin " + std::to_string(k) + " holds " + std::to_string(counts[k]) +
+                  " hits (>= 2^32): its power sum may have wrapped");
+    }
+  return ODW_OK;
+}
+
 int odw_sample(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, uint64_t seed, double* theta_out,
                double* phi_out) {
   if (!ctx || !theta_out || !phi_out) return fail(ctx, ODW_ERR_INVALID, "odw_sample: bad argument");
@@ -3005,7 +3084,7 @@ int odw_sample(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, uint64_t seed,
 int odw_device_results(odw_ctx* ctx, void** dptr, uint64_t* n_words, uint64_t* hist_offset_words) {
   if (!ctx || !dptr || !n_words || !hist_offset_words) return fail(ctx, ODW_ERR_INVALID, "odw_device_results: bad argument");
   *dptr = ctx->results.p;
-  *n_words = kResultsHead + ctx->n_bins;
+  *n_words = kResultsHead + ctx->n_bins * (ctx->power_on ? 2 : 1);
   *hist_offset_words = kResultsHead;
   return ODW_OK;
 }
@@ -3014,6 +3093,14 @@ int odw_device_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_bins) {
   if (!ctx || !dptr || !n_bins) return fail(ctx, ODW_ERR_INVALID, "odw_device_histogram: bad argument");
   *dptr = ctx->n_bins ? ctx->hist.p : nullptr;
   *n_bins = ctx->n_bins;
+  return ODW_OK;
+}
+
+int odw_device_power_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_bins) {
+  if (!ctx || !dptr || !n_bins) return fail(ctx, ODW_ERR_INVALID, "odw_device_power_histogram: bad argument");
+  const bool on = ctx->power_on && ctx->n_bins;
+  *dptr = on ? (void*)((uint64_t*)ctx->hist.p + ctx->n_bins) : nullptr;
+  *n_bins = on ? ctx->n_bins : 0;
   return ODW_OK;
 }
 

@@ -84,7 +84,7 @@ __device__ __forceinline__ int grid_slab(const double* b, int n, double v) {
 // lanes add with ds_add_u32 (a handful of events per ray)
 #define ODW_GCOUNT(k) atomicAdd(&wave_cnt[(k)], 1u)
 
-template <bool SPHERES, bool IN_LDS>
+template <bool SPHERES, bool IN_LDS, bool POWER = false>     // POWER: the detector's power plane (record_hit)
 __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceParams P) {
   extern __shared__ double grid_lds[];
   const DeviceScene& sc = P.scene;
@@ -490,7 +490,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
           const int gtype = group_i32[4 * g];
           if (group_i32[4 * g + 1]) {
             ODW_GCOUNT(ODW_CNT_RECORDED_HITS);
-            record_hit<true, 1, true>(P, P.first_ray + i, g, point, dir, power, entering, wave_cnt, hit_state);
+            record_hit<true, 1, true, POWER>(P, P.first_ray + i, g, point, dir, power, entering, wave_cnt, hit_state);
           }
           if (gtype == ODW_OPT_MIRROR) {
             dir = mirror(dir, n);

@@ -1334,8 +1334,22 @@ __device__ __forceinline__ bool hist_window_add(uint32_t* win, int ix, int iy, i
   atomicAdd(win + 4 + dx * ODW_HIST_WIN + dy, 1u);
   return true;
 }
+// The power plane (ODW_TRACE_POWER_HISTOGRAM, include/odw_trace.h): nx * ny u64 sums of hit weights directly behind
+// the count histogram.  A weight is the hit's power in fixed point -- llrint(clamp(power, 0, 2^20) * 2^32), NaN -> 0 --:
+// integer sums, so the plane does not depend on the order hits arrive in, on how rays are split into launches or on
+// the number of GPUs (a float atomic would).  One u64 atomic in HBM per weighted hit, no LDS window (a u64 window of
+// ODW_HIST_WIN^2 bins is another 62 KB per block).
+// POWER is a template parameter of every kernel family, not a branch on P.flags: the ray loops sit at the edge of
+// spilling, and any code added to record_hit -- even a call to a function out of line, whose register use the
+// callers' allocation follows -- moved spills and scratch bytes of the existing kernels (measured: profiles/power_maps.md).
+// Launches without the flag run the instantiations <..., POWER = false>, which are the kernels as they were, register
+// for register; the host picks <..., true> exactly when the flag is set and a plane lies behind the bins.
+__device__ __forceinline__ unsigned long long power_quanta(double power) {
+  const double c = power > 0.0 ? fmin(power, ODW_POWER_MAX) : 0.0;     // (NaN > 0 is false)
+  return (unsigned long long)(long long)rint(c * (double)(1ull << ODW_POWER_QUANTUM_BITS));   // (exact product; nearest, ties to even)
+}
 // PT: TraceParams, or TraceParams in the constant address space (the kernel's argument segment)
-template <bool BLOCKS, int CS = 256, bool CA = false, class PT>
+template <bool BLOCKS, int CS = 256, bool CA = false, bool POWER = false, class PT>
 __device__ __forceinline__ void record_hit(const PT& P, uint64_t ray, int group, d3 p, d3 d,
                                            double power, bool entering, uint32_t* cnt,
                                            volatile uint32_t* hit_state, uint32_t* win = nullptr) {
@@ -1421,6 +1435,8 @@ __device__ __forceinline__ void record_hit(const PT& P, uint64_t ray, int group,
         const int ix = (int)fx, iy = (int)fy;
         if (!(win && hist_window_add(win, ix, iy, det->nx, det->ny)))
           atomicAdd(P.out.hist + ((size_t)ix * (size_t)det->ny + (size_t)iy), 1ull);
+        if constexpr (POWER)        // (n_bins < 2^31: odw_enable_power_histogram)
+          atomicAdd(P.out.hist + ((size_t)(det->nx * det->ny) + (size_t)(ix * det->ny + iy)), power_quanta(power));
       } else if (CA)
         atomicAdd(&cnt[ODW_CNT_HIST_OVERFLOW * CS], 1u);
       else
@@ -1434,6 +1450,7 @@ __device__ __forceinline__ void record_hit(const PT& P, uint64_t ray, int group,
 // VGPRs with the histogram window, measured).  kargs: the kernel's argument segment (TraceParams is
 // the kernels' only argument; the pointer is taken in the kernel, a callee cannot ask for it).
 typedef const TraceParams ODW_CONST* ckargs;
+template <bool POWER>
 __device__ __noinline__ void record_hit_flat(ckargs kargs, uint64_t ray, int group, d3 p, d3 d, double power,
                                              bool entering, uint32_t* cnt, uint32_t* hit_state, uint32_t* win) {
   // (arguments arrive in vector registers: the pointer is wave-uniform, say so -- scalar loads again)
@@ -1441,7 +1458,7 @@ __device__ __noinline__ void record_hit_flat(ckargs kargs, uint64_t ray, int gro
   // (the builtin returns int: without the casts the low word is sign-extended over the high one)
   const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)) << 32) |
                      (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
-  record_hit<true>(*(ckargs)(uintptr_t)u, ray, group, p, d, power, entering, cnt, hit_state, win);
+  record_hit<true, 256, false, POWER>(*(ckargs)(uintptr_t)u, ray, group, p, d, power, entering, cnt, hit_state, win);
 }
 
 // RecordRays (generic_source.py:78-118): one row per segment Ray.traceRay yields.  Only a
@@ -1483,7 +1500,7 @@ __device__ __noinline__ RayInit generate_ray(const DeviceSource* sp, uint64_t ra
 // vacuum / grating, medium and sequence state (ray.py:91-281).  The generic kernels pass the group's
 // words as read from the tables; a compiled scene passes constants and the branches fold.
 // n: surface normal along the travel direction; cnt: the thread's column of event counters.
-template <bool BVH, bool STOCH, bool LEAN>
+template <bool BVH, bool STOCH, bool LEAN, bool POWER = false>
 __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, ci32 group_i32, cf64 group_gdir, int g,
                                          int gtype, bool record, d3 n, bool entering, uint64_t ray, int nint,
                                          uint32_t* cnt, uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power,
@@ -1492,8 +1509,8 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
     cnt[ODW_CNT_RECORDED_HITS * 256] += 1u;
     // (block reservations and the histogram window only in the flat kernels: in the BVH kernels
     // their state costs more registers / LDS than the atomics cost time)
-    if (BVH) record_hit<false>(P, ray, g, point, dir, power, entering, cnt, hit_state);
-    else record_hit_flat((ckargs)__builtin_amdgcn_kernarg_segment_ptr(), ray, g, point, dir, power, entering, cnt,
+    if (BVH) record_hit<false, 256, false, POWER>(P, ray, g, point, dir, power, entering, cnt, hit_state);
+    else record_hit_flat<POWER>((ckargs)__builtin_amdgcn_kernarg_segment_ptr(), ray, g, point, dir, power, entering, cnt,
                          hit_state, win);   // (interact is inlined into the kernel: the pointer is the kernel's)
   }
   if (gtype == ODW_OPT_MIRROR) {
@@ -1558,7 +1575,7 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
 
 // the hit is on primitive PI of a compiled scene: its type, frame pattern, flags, group and the group's
 // optical type / recording switch are constants
-template <bool STOCH, bool LEAN, class SPEC, int PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, int PI>
 __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                          cf64 group_gdir, int face, uint64_t ray, int nint, uint32_t* cnt,
                                          uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
@@ -1578,7 +1595,7 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
 #endif
   const bool entering = dot(dir, n) < 0;
   if (entering) n = n * -1.0;
-  interact<false, STOCH, LEAN>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
+  interact<false, STOCH, LEAN, POWER>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
                                nint, cnt, hit_state, win, point, dir, power, medium, seq, alive);
   // n points along the incoming travel direction: out of the solid when leaving it, into it when entering
   const double out = entering ? -dot(dir, n) : dot(dir, n);
@@ -1587,12 +1604,12 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   if constexpr ((flags & ODW_FLAG_ISOLATED) != 0) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else only = -1;
 }
-template <bool STOCH, bool LEAN, class SPEC, int... PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, int... PI>
 __device__ __forceinline__ void spec_hits(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                           cf64 group_gdir, int prim, int face, uint64_t ray, int nint, uint32_t* cnt,
                                           uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
                                           int& skip, int& only, bool& alive, IndexList<int, PI...>) {
-  (void)((prim == PI ? (spec_hit<STOCH, LEAN, SPEC, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
+  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
                                                   point, dir, power, medium, seq, skip, only, alive), true)
                      : false) || ...);
 }
@@ -1654,7 +1671,7 @@ template <> struct HitBlockState<false> {
 // LEAN: the scene has no grating group and no finite absorption length (the host checks): their code
 // -- line_grating's chain of IEEE divisions and square roots, exp() -- is left out of the binary
 // BATCH (flat kernels): scenes of one structure side by side in one launch (DeviceBatch)
-template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false>
+template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   static_assert(!BATCH || (!BVH && !SEG), "batch launches: flat kernels, no segment rows");
   extern __shared__ int bvh_stack[];  // ODW_BVH_STACK x 256 ints (BVH variant only)
@@ -1837,7 +1854,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       uint32_t* cnt = cnt_lds + threadIdx.x;
       uint32_t* hit_state = hit_lds + (threadIdx.x >> 6) * 4;
       if constexpr (SPEC::enabled) {
-        spec_hits<STOCH, LEAN, SPEC>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
+        spec_hits<STOCH, LEAN, POWER, SPEC>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
                               hist_win, point, dir, power, medium, seq, skip, only, alive, __make_integer_seq<IndexList, int, SPEC::N>{});
       } else {
       cf64 pf = sv.prim_f64 + (size_t)prim * 16;
@@ -1855,7 +1872,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       const bool entering = dot(dir, n) < 0;
       if (entering) n = n * -1.0;
       const int g = pi[1];
-      interact<BVH, STOCH, LEAN>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
+      interact<BVH, STOCH, LEAN, POWER>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
                                  entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive);
       // outward normal of the solid = n against the travel direction when entering; for a facet of a convex
       // tessellated solid the FACET's own normal decides (the interpolated one of smooth shading can point out of
@@ -1914,9 +1931,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   }
 }
 
-template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, bool BATCH = false>
+template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, bool BATCH = false, bool POWER = false>
 __global__ __launch_bounds__(256, BVH ? ODW_WAVES_PER_SIMD_BVH : ODW_WAVES_PER_SIMD) void odw_trace_kernel(const TraceParams P) {
-  trace_body<BVH, STOCH, SEG, LEAN, NoSpec, BATCH>(P);
+  trace_body<BVH, STOCH, SEG, LEAN, NoSpec, BATCH, POWER>(P);
 }
 
 #ifdef ODW_SPEC_HEADER
@@ -1932,8 +1949,11 @@ __global__ __launch_bounds__(256, BVH ? ODW_WAVES_PER_SIMD_BVH : ODW_WAVES_PER_S
 #ifndef ODW_SPEC_BATCH
 #define ODW_SPEC_BATCH false
 #endif
+#ifndef ODW_SPEC_POWER
+#define ODW_SPEC_POWER false
+#endif
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(const TraceParams P) {
-  trace_body<false, ODW_SPEC_STOCH, false, ODW_SPEC_LEAN, Spec, ODW_SPEC_BATCH>(P);
+  trace_body<false, ODW_SPEC_STOCH, false, ODW_SPEC_LEAN, Spec, ODW_SPEC_BATCH, ODW_SPEC_POWER>(P);
 }
 #endif
 

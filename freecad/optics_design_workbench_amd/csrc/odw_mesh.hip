@@ -83,7 +83,7 @@ namespace odw {
 // segment and lane, the spills it saves were not in the hot loops); out of line at four waves per SIMD
 // (ODW_MESH_WAVES=4, still 96 spilled) 5.47 / 6.45 / 9.12.
 struct MeshRay { d3 point, dir; double power; int medium, seq, skip, inside; bool alive; };
-template <bool STOCH>
+template <bool STOCH, bool POWER>
 __device__ __forceinline__
 MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, int seq, int nint, uint64_t i, double t_hit, int prim,
                       int face, uint32_t* wave_cnt, volatile uint32_t* hit_state, const double* group_f64, const int32_t* group_i32,
@@ -125,7 +125,7 @@ MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, 
         const int gtype = group_i32[4 * g];
         if (group_i32[4 * g + 1]) {
           ODW_MCOUNT(ODW_CNT_RECORDED_HITS);
-          record_hit<true, 1, true>(P, P.first_ray + i, g, point, dir, power, entering, wave_cnt, hit_state);
+          record_hit<true, 1, true, POWER>(P, P.first_ray + i, g, point, dir, power, entering, wave_cnt, hit_state);
         }
         if (gtype == ODW_OPT_MIRROR) {
           const d3 ideal = mirror(dir, n);
@@ -220,7 +220,7 @@ MeshBest mesh_intersect_prim(ckargs kargs, d3 start, d3 dn, double tol, double t
 }
 
 // STOCH: the scene has stochastic surfaces (scatter() after the ideal mirror / Snell direction, as in interact<>)
-template <bool STOCH>
+template <bool STOCH, bool POWER = false>     // POWER: the detector's power plane (record_hit)
 __global__ __launch_bounds__(ODW_MESH_THREADS, ODW_MESH_WAVES) void odw_mesh_kernel(const TraceParams P) {
   extern __shared__ double mesh_lds[];
   const DeviceScene& sc = P.scene;
@@ -637,7 +637,7 @@ __global__ __launch_bounds__(ODW_MESH_THREADS, ODW_MESH_WAVES) void odw_mesh_ker
         alive = false;
       } else {
         const bool use_oth = q.oth.prim != 0x7fffffff && q.oth.t < q.any.t + 2.0 * q.tol;
-        const MeshRay r = mesh_interact<STOCH>((ckargs)__builtin_amdgcn_kernarg_segment_ptr(), point, dir, power, medium, seq, nint, i,
+        const MeshRay r = mesh_interact<STOCH, POWER>((ckargs)__builtin_amdgcn_kernarg_segment_ptr(), point, dir, power, medium, seq, nint, i,
                                                use_oth ? q.oth.t : q.any.t, use_oth ? q.oth.prim : q.any.prim,
                                                use_oth ? q.oth.face : q.any.face, wave_cnt, hit_state, group_f64, group_i32, group_gdir);
         point = r.point; dir = r.dir; power = r.power; medium = r.medium; seq = r.seq; skip = r.skip; inside = r.inside; alive = r.alive;

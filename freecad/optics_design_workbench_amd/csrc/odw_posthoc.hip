@@ -485,12 +485,16 @@ size_t ph_bin_lds_bytes(int na, int nb, uint64_t lds_bins, bool polar) {
   return bytes + 16;
 }
 
-template <bool LDS_COUNTS>
+// POWER (odw_hits_bin_power): binned row j also adds the weight of its hit -- power_quanta(hits[sel[j]].power), the fixed
+// point of include/odw_trace.h -- to power[same bin]: u64 atomics in HBM (integer sums: whatever the order)
+template <bool LDS_COUNTS, bool POWER = false>
 __global__ __launch_bounds__(256) void ph_bin_kernel(const double* __restrict__ X, const double* __restrict__ Y,
                                                      uint64_t m, double ox, double oy, int polar,
                                                      const double* __restrict__ edges_a, int na,
                                                      const double* __restrict__ edges_b, int nb,
-                                                     const PhbBinAccel* __restrict__ accel, unsigned long long* __restrict__ counts) {
+                                                     const PhbBinAccel* __restrict__ accel, unsigned long long* __restrict__ counts,
+                                                     const odw_hit* __restrict__ hits = nullptr, const uint32_t* __restrict__ sel = nullptr,
+                                                     unsigned long long* __restrict__ power = nullptr) {
   extern __shared__ double ph_bin_lds[];          // [edges | counts | guide], sized by the caller (ph_bin_lds_bytes)
   const bool edges_in_lds = na + nb <= kPhLdsEdges;
   const int nbins = (na - 1) * (nb - 1);
@@ -525,6 +529,7 @@ __global__ __launch_bounds__(256) void ph_bin_kernel(const double* __restrict__ 
       const int k = ia * (nb - 1) + ib;
       if (LDS_COUNTS) atomicAdd(&s_counts[k], 1u);
       else atomicAdd(counts + k, 1ull);
+      if (POWER) atomicAdd(power + k, power_quanta(hits[sel[j]].power));
     }
   }
   if (LDS_COUNTS) {
@@ -964,22 +969,26 @@ int odw_hits_range(odw_ctx* ctx, int32_t polar, const double* origin, double* ra
   return ODW_OK;
 }
 
-int odw_hits_bin(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
-                 const double* edges_b, int32_t n_b, uint64_t* counts) {
-  if (!ctx || !origin || !edges_a || !edges_b || !counts || n_a < 2 || n_b < 2)
-    return fail(ctx, ODW_ERR_INVALID, "odw_hits_bin: bad argument");
-  for (int k = 1; k < n_a; ++k) if (!(edges_a[k] >= edges_a[k - 1])) return fail(ctx, ODW_ERR_INVALID, "odw_hits_bin: edges must increase monotonically");
-  for (int k = 1; k < n_b; ++k) if (!(edges_b[k] >= edges_b[k - 1])) return fail(ctx, ODW_ERR_INVALID, "odw_hits_bin: edges must increase monotonically");
-  int rc = ph_need_projection(ctx, "odw_hits_bin");
+namespace {
+// odw_hits_bin (power == nullptr) and odw_hits_bin_power: the same edges, tables and bin rule; the weighted call runs the
+// kernel's POWER variant, which also adds every binned row's weight to the plane behind the counts
+int ph_bin_run(odw_ctx* ctx, const std::string& who, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
+               const double* edges_b, int32_t n_b, uint64_t* counts, uint64_t* power, bool weighted) {
+  if (!ctx || !origin || !edges_a || !edges_b || !counts || (weighted && !power) || n_a < 2 || n_b < 2)
+    return fail(ctx, ODW_ERR_INVALID, who + ": bad argument");
+  for (int k = 1; k < n_a; ++k) if (!(edges_a[k] >= edges_a[k - 1])) return fail(ctx, ODW_ERR_INVALID, who + ": edges must increase monotonically");
+  for (int k = 1; k < n_b; ++k) if (!(edges_b[k] >= edges_b[k - 1])) return fail(ctx, ODW_ERR_INVALID, who + ": edges must increase monotonically");
+  int rc = ph_need_projection(ctx, who.c_str());
   if (rc) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const uint64_t m = ctx->ph_n;
   const uint64_t nbins = (uint64_t)(n_a - 1) * (uint64_t)(n_b - 1);
+  const uint64_t words = weighted ? 2 * nbins : nbins;            // [counts | power]
   if ((rc = upload(ctx, ctx->ph_edges, edges_a, (size_t)n_a * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->ph_edges_b, (size_t)n_b * sizeof(double)))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->ph_edges_b.p, edges_b, (size_t)n_b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  if ((rc = ensure(ctx, ctx->ph_counts, nbins * sizeof(uint64_t)))) return rc;
-  HIPCHK(ctx, hipMemsetAsync(ctx->ph_counts.p, 0, nbins * sizeof(uint64_t), ctx->stream));
+  if ((rc = ensure(ctx, ctx->ph_counts, words * sizeof(uint64_t)))) return rc;
+  HIPCHK(ctx, hipMemsetAsync(ctx->ph_counts.p, 0, words * sizeof(uint64_t), ctx->stream));
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)ctx->n_cu * 8));
   // polar bins without arctan2 / the search over all edges where the tables apply (ODW_BIN_PLAIN=1: the plain kernel; tests
   // hold the two against each other and against numpy)
@@ -993,19 +1002,34 @@ int odw_hits_bin(odw_ctx* ctx, int32_t polar, const double* origin, const double
       accel = (const PhbBinAccel*)ctx->ph_accel.p;
     }
   }
-  const size_t lds = ph_bin_lds_bytes(n_a, n_b, nbins <= (uint64_t)kPhLdsBins ? nbins : 0, polar != 0);
-  if (nbins <= (uint64_t)kPhLdsBins)
-    hipLaunchKernelGGL((ph_bin_kernel<true>), dim3(grid), dim3(256), lds, ctx->stream, (const double*)ctx->ph_x.p,
-                       (const double*)ctx->ph_y.p, m, origin[0], origin[1], (int)polar, (const double*)ctx->ph_edges.p,
-                       (int)n_a, (const double*)ctx->ph_edges_b.p, (int)n_b, accel, (unsigned long long*)ctx->ph_counts.p);
-  else
-    hipLaunchKernelGGL((ph_bin_kernel<false>), dim3(grid), dim3(256), lds, ctx->stream, (const double*)ctx->ph_x.p,
-                       (const double*)ctx->ph_y.p, m, origin[0], origin[1], (int)polar, (const double*)ctx->ph_edges.p,
-                       (int)n_a, (const double*)ctx->ph_edges_b.p, (int)n_b, accel, (unsigned long long*)ctx->ph_counts.p);
+  unsigned long long* d_counts = (unsigned long long*)ctx->ph_counts.p;
+  const odw_hit* rows = (const odw_hit*)ctx->hits.p;             // (the rows and the selection odw_hits_project read)
+  const uint32_t* sel = (const uint32_t*)ctx->sort_vals[1].p;
+  const bool in_lds = nbins <= (uint64_t)kPhLdsBins;
+  const size_t lds = ph_bin_lds_bytes(n_a, n_b, in_lds ? nbins : 0, polar != 0);
+#define ODW_PH_BIN(L, W)                                                                                                          \
+  hipLaunchKernelGGL((ph_bin_kernel<L, W>), dim3(grid), dim3(256), lds, ctx->stream, (const double*)ctx->ph_x.p,                  \
+                     (const double*)ctx->ph_y.p, m, origin[0], origin[1], (int)polar, (const double*)ctx->ph_edges.p, (int)n_a,   \
+                     (const double*)ctx->ph_edges_b.p, (int)n_b, accel, d_counts, rows, sel, d_counts + nbins)
+  if (weighted) { if (in_lds) ODW_PH_BIN(true, true); else ODW_PH_BIN(false, true); }
+  else { if (in_lds) ODW_PH_BIN(true, false); else ODW_PH_BIN(false, false); }
+#undef ODW_PH_BIN
   HIPCHK(ctx, hipGetLastError());
-  HIPCHK(ctx, hipMemcpyAsync(counts, ctx->ph_counts.p, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(counts, d_counts, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (weighted) HIPCHK(ctx, hipMemcpyAsync(power, d_counts + nbins, nbins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return ODW_OK;
+}
+}  // namespace
+
+int odw_hits_bin(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
+                 const double* edges_b, int32_t n_b, uint64_t* counts) {
+  return ph_bin_run(ctx, "odw_hits_bin", polar, origin, edges_a, n_a, edges_b, n_b, counts, nullptr, false);
+}
+
+int odw_hits_bin_power(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
+                       const double* edges_b, int32_t n_b, uint64_t* counts, uint64_t* power) {
+  return ph_bin_run(ctx, "odw_hits_bin_power", polar, origin, edges_a, n_a, edges_b, n_b, counts, power, true);
 }
 
 // max and min of point . normal per candidate normal (odw_plane_screen)

@@ -354,12 +354,20 @@ void spec_wait_at_exit() {
 // earn its compilation: once ctx->spec_hot_rays rays were traced with its structure on generic kernels (by all
 // contexts of the process together), a thread compiles,
 // and the first launch after it has finished binds the result (the rows are the same either way, bit for bit).
-// batch: the kernel's BATCH variant (scenes of one structure side by side, odw_trace_batch) -> ctx->spec_batch_fn; it is
-// bound on the first batch launch, while the single-scene kernel of the same structure is bound (its mode decides)
-int spec_bind(odw_ctx* ctx, bool batch = false) {
-  if (batch) {
+// variant kSpecBatch: the kernel's BATCH variant (scenes of one structure side by side, odw_trace_batch) -> ctx->spec_batch_fn;
+// it is bound on the first batch launch, while the single-scene kernel of the same structure is bound (its mode decides).
+// variant kSpecPower: the POWER variant (launches that fill the detector's power plane) -> ctx->spec_power_fn, likewise.
+enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2 };
+int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
+  const bool batch = variant != kSpecSingle;      // (a variant rides on the single-scene kernel's bookkeeping)
+  if (variant == kSpecBatch) {
     ctx->spec_batch_fn = nullptr;
+  } else if (variant == kSpecPower) {
+    ctx->spec_power_fn = nullptr;
   } else {
+    ctx->spec_power_fn = nullptr;
+    ctx->spec_power_failed = false;
+    ctx->spec_power_wait = nullptr;
     ctx->spec_dirty = false;
     ctx->spec_fn = nullptr;
     ctx->spec_batch_fn = nullptr;
@@ -373,7 +381,7 @@ int spec_bind(odw_ctx* ctx, bool batch = false) {
   hipDeviceProp_t prop;
   HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
   const std::string arch = prop.gcnArchName;
-  const std::string text = spec_text(ctx) + (batch ? "#define ODW_SPEC_BATCH true\n" : "");
+  const std::string text = spec_text(ctx) + (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n" : variant == kSpecPower ? "#define ODW_SPEC_POWER true\n" : "");
   const char* xo = getenv("ODW_SPEC_OPTS");
   const std::string jkey = arch + "|" + (xo ? xo : "") + "|" + text;
   const std::string key = std::to_string(ctx->device) + "|" + jkey;
@@ -395,9 +403,11 @@ int spec_bind(odw_ctx* ctx, bool batch = false) {
           // not hot yet, or hot: start the thread
           // (the BATCH variant rides on the single-scene kernel's bookkeeping: its own key must not replace that one's)
           if (!batch) { ctx->spec_pending = true; ctx->spec_key = jkey; }
-          if (G.rays[jkey] < ctx->spec_hot_rays) return ODW_OK;
+          // (the POWER variant is asked for while the single-scene kernel of the structure is bound: hot already)
+          if (variant != kSpecPower && G.rays[jkey] < ctx->spec_hot_rays) return ODW_OK;
           auto job = std::make_shared<SpecJob>();
           G.jobs[jkey] = job;
+          if (variant == kSpecPower) ctx->spec_power_wait = &job->done;      // (jobs are never erased from the table)
           static std::once_flag once;
           std::call_once(once, [] { (void)hiprtc(); atexit(spec_wait_at_exit); });
           G.running.fetch_add(1);
@@ -411,6 +421,7 @@ int spec_bind(odw_ctx* ctx, bool batch = false) {
         }
       } else if (!jt->second->done.load()) {
         if (!batch) { ctx->spec_pending = true; ctx->spec_key = jkey; }
+        if (variant == kSpecPower) ctx->spec_power_wait = &jt->second->done;
         return ODW_OK;                                      // still compiling: generic kernels meanwhile
       } else {
         std::shared_ptr<SpecJob> job = jt->second;
@@ -452,7 +463,7 @@ int spec_bind(odw_ctx* ctx, bool batch = false) {
     ctx->spec_cache_hit = 1;
   }
   if (batch) {
-    ctx->spec_batch_fn = it->second.fn;
+    (variant == kSpecBatch ? ctx->spec_batch_fn : ctx->spec_power_fn) = it->second.fn;
     return ODW_OK;
   }
   ctx->spec_fn = it->second.fn;
@@ -475,11 +486,11 @@ void spec_note_launch(odw_ctx* ctx, uint64_t n_rays) {
   if (jt == G.jobs.end() || jt->second->done.load()) ctx->spec_dirty = true;
 }
 
-int spec_launch(odw_ctx* ctx, unsigned grid, bool batch) {
+int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn) {
   TraceParams P = ctx->P;
   size_t size = sizeof P;
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &P, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-  HIPCHK(ctx, hipModuleLaunchKernel(batch ? ctx->spec_batch_fn : ctx->spec_fn, grid, 1, 1, 256, 1, 1, 0, ctx->stream, nullptr, config));
+  HIPCHK(ctx, hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, ctx->stream, nullptr, config));
   return ODW_OK;
 }
 

@@ -28,6 +28,7 @@ class Histogram:
                origin=None, **kwargs):
     self._planeNormal = planeNormal
     self._xInPlaneVec = xInPlaneVec
+    self.powerQuanta = None
     self._origin = np.array([np.median(X), np.median(Y)]) if origin is None else origin
     X = X - self._origin[0]
     Y = Y - self._origin[1]
@@ -52,10 +53,12 @@ class Histogram:
       raise ValueError(f'found invalid binCoord mode {binCoords!r}, expect one of "cartesian" or "polar"')
 
   @classmethod
-  def fromBinned(cls, hist, binX, binY, planeNormal, xInPlaneVec, origin, binCoords):
+  def fromBinned(cls, hist, binX, binY, planeNormal, xInPlaneVec, origin, binCoords, powerQuanta=None):
     """a Histogram around counts that were binned elsewhere (on the device, `DeviceHits.histogram`)
-    with this class' rules: same attributes as after __init__"""
+    with this class' rules: same attributes as after __init__.  powerQuanta: the raw uint64 plane behind a
+    power-weighted `hist` (`DeviceHits.histogram(weights='powers')`: hist = powerQuanta * 2^-32), else None"""
     self = cls.__new__(cls)
+    self.powerQuanta = None if powerQuanta is None else np.asarray(powerQuanta, dtype=np.uint64)
     self._planeNormal, self._xInPlaneVec, self._origin = planeNormal, xInPlaneVec, np.asarray(origin)
     self._binCoords = binCoords
     self.hist, self.binX, self.binY = np.asarray(hist, dtype=np.float64), np.asarray(binX), np.asarray(binY)

@@ -182,6 +182,9 @@ class Hits:
 
   def histogram(self, planeNormal=None, xInPlaneVec=None, key='points', **kwargs):
     x, y, n, ex = self._flat(key, planeNormal, xInPlaneVec)
+    # weights='powers': a string names a column of the hit dictionary (arrays pass through to numpy.histogram2d)
+    if isinstance(kwargs.get('weights'), str):
+      kwargs['weights'] = np.asarray(self.hits[kwargs['weights']])
     return Histogram(x, y, planeNormal=n, xInPlaneVec=ex, **kwargs)
 
   def plot(self, hueKey=None, hueLabel=None, planeNormal=None, xInPlaneVec=None, plotKey='points', **kwargs):

@@ -257,10 +257,26 @@ class DeviceHits:
     if radius is not None:
       _radius_bins(kwargs, radius, polar=polar)
     bins = kwargs.pop('bins', 10)
+    # weights='powers': the power plane of the same bins (`odw_hits_bin_power`), every row weighing rint(power * 2^32)
+    # quanta -- integer sums on the device.  Any other weights (an array, another column): TypeError, the caller's
+    # cue to bin the host arrays (`RunHits.histogram`)
+    weighted = isinstance(kwargs.get('weights'), str) and kwargs['weights'] == 'powers'
+    if weighted:
+      kwargs.pop('weights')
     if kwargs:
       raise TypeError(f'DeviceHits.histogram: unsupported arguments {sorted(kwargs)}')
     edges = self._edges(bins, polar, origin)
     counts = np.zeros((len(edges[0]) - 1) * (len(edges[1]) - 1), dtype=np.uint64)
+    if weighted:
+      pu = C.POINTER(C.c_uint64)
+      quanta = np.zeros_like(counts)
+      tr._chk(tr._lib.odw_hits_bin_power(tr._ctx, C.c_int32(1 if polar else 0), origin.ctypes.data_as(pd),
+                                         edges[0].ctypes.data_as(pd), C.c_int32(len(edges[0])), edges[1].ctypes.data_as(pd),
+                                         C.c_int32(len(edges[1])), counts.ctypes.data_as(pu), quanta.ctypes.data_as(pu)),
+              'odw_hits_bin_power')
+      quanta = quanta.reshape(len(edges[0]) - 1, len(edges[1]) - 1)
+      return Histogram.fromBinned(quanta.astype(np.float64) * 2.0 ** -_native.POWER_QUANTUM_BITS, edges[0], edges[1],
+                                  planeNormal, xInPlaneVec, origin, 'polar' if polar else 'cartesian', powerQuanta=quanta)
     tr._chk(tr._lib.odw_hits_bin(tr._ctx, C.c_int32(1 if polar else 0), origin.ctypes.data_as(pd),
                                  edges[0].ctypes.data_as(pd), C.c_int32(len(edges[0])), edges[1].ctypes.data_as(pd),
                                  C.c_int32(len(edges[1])), counts.ctypes.data_as(C.POINTER(C.c_uint64))), 'odw_hits_bin')

@@ -27,8 +27,11 @@ def shardFirst(step, rank, world, n_per, warm=False):
 
 
 def reduceResults(tracer, dist, torch, dst=0):
-  """sum counters + histogram of every rank into rank `dst`'s device buffers with ONE reduce: the library keeps
-  both in one block of int64 words (`Tracer.resultsView`, odw_device_results), of which this is a zero-copy view"""
+  """sum counters + histogram -- and the power plane, where `Tracer.setDetector(..., power=True)` keeps one -- of every
+  rank into rank `dst`'s device buffers with ONE reduce: the library keeps them in one block of int64 words, [counters |
+  bins | power plane] (`Tracer.resultsView`, odw_device_results), of which this is a zero-copy view.  All three are
+  integer sums (the power plane in quanta of 2^-32 of the source power): the result does not depend on the number of
+  ranks.  Every rank must have the same detector and the same `power` setting (the same block length)."""
   tracer.sync()
   view, _ = tracer.resultsView()
   if hasattr(view, '__cuda_array_interface__'):

@@ -13,7 +13,8 @@ import weakref
 import numpy as np
 
 from .. import _native
-from .._native import CNT_NAMES, HIT_DTYPE, SEGMENT_DTYPE, TRACE_HISTOGRAM, TRACE_RECORD_HITS, TRACE_RECORD_SEGMENTS
+from .._native import (CNT_NAMES, HIT_DTYPE, POWER_QUANTUM_BITS, SEGMENT_DTYPE, TRACE_HISTOGRAM, TRACE_POWER_HISTOGRAM, TRACE_RECORD_HITS,
+                       TRACE_RECORD_SEGMENTS)
 
 
 # Contexts that are still open when the interpreter ends are closed in ITS order, at the start of its shutdown (atexit),
@@ -136,6 +137,7 @@ class Tracer:
     _native.check(None, self._lib.odw_create(self.device, C.byref(self._ctx)), 'odw_create')
     _LIVE.add(self)
     self._det = None
+    self._power = False
     self._keep = {}
     # ODW_COMPILE=structure: every tracer of the process compiles its scenes (test campaigns)
     if os.environ.get('ODW_COMPILE'):
@@ -203,12 +205,16 @@ class Tracer:
 
   def compiledInfo(self):
     """dict(mode: 0 generic (in 'auto' mode: not compiled yet) / 1 structure / 2 auto -- of the kernel the next eligible launch runs,
-    seconds: compile time of it (0 from a cache), cache: 0 compiled now / 1 process / 2 disk)"""
+    seconds: compile time of it (0 from a cache), cache: 0 compiled now / 1 process / 2 disk,
+    power: the same as `mode` for launches that fill the power plane -- they run a variant of the compiled kernel of
+    their own, bound by the first such launch (`odw_compiled_power_info`))"""
     f = self._lib.odw_compiled_info
     f.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     b, sec, hit = C.c_int32(0), C.c_double(0), C.c_int32(0)
     self._chk(f(self._ctx, C.byref(b), C.byref(sec), C.byref(hit)), 'odw_compiled_info')
-    return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value))
+    pw = C.c_int32(0)
+    self._chk(self._lib.odw_compiled_power_info(self._ctx, C.byref(pw)), 'odw_compiled_power_info')
+    return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value))
 
   def setSurfaceSeed(self, seed):
     """Philox key of the stochastic-surface draws in traceRays launches"""
@@ -244,8 +250,12 @@ class Tracer:
     self._chk(self._lib.odw_set_limits(self._ctx, C.byref(d)), 'odw_set_limits')
     self.limits = lim
 
-  def setDetector(self, det):
-    """det: dict(group, origin, ex, ey, x_lo, x_hi, y_lo, y_hi, nx, ny) or None"""
+  def setDetector(self, det, power=False):
+    """det: dict(group, origin, ex, ey, x_lo, x_hi, y_lo, y_hi, nx, ny) or None
+    power: keep a power plane beside the counts (`odw_enable_power_histogram`): every binned hit also adds its power,
+    in fixed point (rint(power * 2^32) as uint64 -- integer sums, independent of launch order and GPU count), to
+    `powerHistogram()`; launches with `histogram=True` then fill both planes"""
+    self._power = False
     if det is None:
       self._chk(self._lib.odw_set_detector(self._ctx, None), 'odw_set_detector')
       self._det = None
@@ -259,6 +269,9 @@ class Tracer:
     d.nx, d.ny = int(det['nx']), int(det['ny'])
     self._chk(self._lib.odw_set_detector(self._ctx, C.byref(d)), 'odw_set_detector')
     self._det = dict(det)
+    if power:
+      self._chk(self._lib.odw_enable_power_histogram(self._ctx, C.c_int(1)), 'odw_enable_power_histogram')
+      self._power = True
 
   def reserveHits(self, capacity):
     self._chk(self._lib.odw_reserve_hits(self._ctx, C.c_uint64(int(capacity))), 'odw_reserve_hits')
@@ -268,10 +281,10 @@ class Tracer:
     self._chk(self._lib.odw_reserve_segments(self._ctx, C.c_uint64(int(capacity))), 'odw_reserve_segments')
 
   # -- tracing --------------------------------------------------------------
-  @staticmethod
-  def _flags(record_hits, histogram, record_segments=False):
+  def _flags(self, record_hits, histogram, record_segments=False):
     return ((TRACE_RECORD_HITS if record_hits else 0) | (TRACE_HISTOGRAM if histogram else 0)
-            | (TRACE_RECORD_SEGMENTS if record_segments else 0))
+            | (TRACE_RECORD_SEGMENTS if record_segments else 0)
+            | (TRACE_POWER_HISTOGRAM if histogram and self._power else 0))
 
   def trace(self, first, n, seed, record_hits=True, histogram=True, record_segments=False):
     """asynchronous: rays first..first+n-1 of Philox stream `seed`"""
@@ -539,6 +552,22 @@ class Tracer:
                                             C.c_uint64(nb)), 'odw_fetch_histogram')
     return out.reshape(self._det['nx'], self._det['ny'])
 
+  def powerHistogramRaw(self):
+    """the power plane as the library keeps it: uint64 (nx, ny), bin = sum over its hits of rint(power * 2^32).  Raises
+    without `setDetector(..., power=True)`, and NativeError (capacity) when a bin holds 2^32 hits or more -- its sum may
+    have wrapped.  Explicit rays with powers above 1 (`traceRays`): the bound is hits of a bin x largest power < 2^32."""
+    if self._det is None or not self._power:
+      raise ValueError('no power plane: setDetector(det, power=True)')
+    nb = self._det['nx'] * self._det['ny']
+    out = np.zeros(nb, dtype=np.uint64)
+    self._chk(self._lib.odw_fetch_power_histogram(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                  C.c_uint64(nb)), 'odw_fetch_power_histogram')
+    return out.reshape(self._det['nx'], self._det['ny'])
+
+  def powerHistogram(self):
+    """power per detector bin, float64 (nx, ny), in units of the source's power: `powerHistogramRaw() * 2^-32`"""
+    return self.powerHistogramRaw().astype(np.float64) * 2.0 ** -POWER_QUANTUM_BITS
+
   def sample(self, first, n, seed):
     t = np.empty(int(n))
     phi = np.empty(int(n))
@@ -554,14 +583,23 @@ class Tracer:
     self._chk(self._lib.odw_device_histogram(self._ctx, C.byref(p), C.byref(n)), 'odw_device_histogram')
     return _CudaArrayView(p.value, n.value, '<i8', self)
 
+  def powerHistogramView(self):
+    """the power plane in HBM (raw quanta)"""
+    if not self._power:
+      raise ValueError('no power plane: setDetector(det, power=True)')
+    p, n = C.c_void_p(), C.c_uint64(0)
+    self._chk(self._lib.odw_device_power_histogram(self._ctx, C.byref(p), C.byref(n)), 'odw_device_power_histogram')
+    return _CudaArrayView(p.value, n.value, '<i8', self)
+
   def countersView(self):
     p, n = C.c_void_p(), C.c_uint64(0)
     self._chk(self._lib.odw_device_counters(self._ctx, C.byref(p), C.byref(n)), 'odw_device_counters')
     return _CudaArrayView(p.value, n.value, '<i8', self)
 
   def resultsView(self):
-    """counters and histogram as ONE int64 vector in HBM (`odw_device_results`): what a multi-GPU job sums with a
-    single reduce.  -> (view, offset of the first histogram bin in words)"""
+    """counters and histogram -- and, with `setDetector(..., power=True)`, the power plane directly behind the
+    histogram's nx * ny bins -- as ONE int64 vector in HBM (`odw_device_results`): what a multi-GPU job sums with a
+    single reduce (the plane's uint64 quanta add as int64 words do).  -> (view, offset of the first histogram bin in words)"""
     p, n, off = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
     self._chk(self._lib.odw_device_results(self._ctx, C.byref(p), C.byref(n), C.byref(off)), 'odw_device_results')
     return _CudaArrayView(p.value, n.value, '<i8', self), int(off.value)

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define ODW_ABI_VERSION 11
+#define ODW_ABI_VERSION 12
 
 /* ---- return codes ------------------------------------------------------ */
 enum {
@@ -350,6 +350,24 @@ enum {
 #define ODW_TRACE_RECORD_HITS 0x1 /* append odw_hit rows                      */
 #define ODW_TRACE_HISTOGRAM   0x2 /* bin into the detector histogram          */
 #define ODW_TRACE_RECORD_SEGMENTS 0x4 /* append odw_segment rows (RecordRays) */
+#define ODW_TRACE_POWER_HISTOGRAM 0x8 /* with ODW_TRACE_HISTOGRAM and an enabled power plane
+                                       * (odw_enable_power_histogram): a binned hit also adds
+                                       * its weight to the power plane; ignored otherwise      */
+
+/* The weight of a hit (v12), wherever hits are summed by power -- the power plane of the
+ * detector (odw_enable_power_histogram) and of the post-hoc binning (odw_hits_bin_power):
+ *   q = llrint(clamp(power, 0, 2^20) * 2^ODW_POWER_QUANTUM_BITS), NaN -> 0,
+ * rounded to nearest, ties to even.  power * 2^32 is exact in float64, so
+ * numpy.rint(power * 2.0**32).astype(numpy.uint64) is q bit for bit.  Planes are uint64
+ * sums of q -- integer sums, the same whatever the order of arrival, the split into
+ * launches or the number of GPUs --; the value in units of source power is
+ * plane * 2^-ODW_POWER_QUANTUM_BITS as float64.
+ * Capacity: a bin wraps after 2^64 quanta.  With powers <= 1 (a source of power 1: surfaces
+ * and media only take power away) that cannot happen while the bin's hit count is below
+ * 2^32.  Explicit rays (odw_trace_rays) may carry powers above 1: there the bound is
+ * (hit count of the bin) x (largest power) < 2^32, and it is the caller's to keep.          */
+#define ODW_POWER_QUANTUM_BITS 32
+#define ODW_POWER_MAX 1048576.0 /* 2^20: larger powers weigh as this                         */
 
 typedef struct odw_ctx odw_ctx;
 
@@ -399,13 +417,31 @@ int odw_trace_rays(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays,
 int odw_sync(odw_ctx* ctx);
 
 /* results --------------------------------------------------------------- */
-int odw_reset_results(odw_ctx* ctx); /* zero counters, hits, segments, histogram */
+int odw_reset_results(odw_ctx* ctx); /* zero counters, hits, segments, histogram, power plane */
 int odw_reset_hits(odw_ctx* ctx);    /* recycle the hit list only (flush)   */
 int odw_fetch_counters(odw_ctx* ctx, uint64_t* out, int32_t n);
 int odw_hit_count(odw_ctx* ctx, uint64_t* n);
 /* copies min(n_hits, capacity) rows, sorted by (ray index, bounce order)   */
 int odw_fetch_hits(odw_ctx* ctx, odw_hit* out, uint64_t capacity, uint64_t* n);
 int odw_fetch_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins);
+/* v12: the power plane of the detector.  Replaces Histogram(..., weights=hits['powers'])
+ * (histogram.py:54,78 hand **kwargs, `weights=` among them, to numpy.histogram2d) for a
+ * detector fixed before tracing.  Call after odw_set_detector.  on != 0: a plane of nx*ny
+ * uint64 sums of hit weights (ODW_POWER_QUANTUM_BITS above) is kept directly behind the
+ * count histogram, in the same block of 64-bit words (odw_device_results), zeroed by this
+ * call (every call with on != 0, also when the plane was on already; the counts stay); launches with ODW_TRACE_HISTOGRAM | ODW_TRACE_POWER_HISTOGRAM add to it: a hit that
+ * lands in bin (ix, iy) adds q(power) to plane[ix * ny + iy], a hit that goes to the overflow
+ * counter adds nothing.  on == 0 (the default): no plane; the block and everything else are
+ * what they are without this call.  The block may move when the plane is switched on: take
+ * device pointers after it.  odw_set_detector -- with any description, NULL included --
+ * switches the plane OFF again: enable it after every odw_set_detector.                     */
+int odw_enable_power_histogram(odw_ctx* ctx, int on);
+/* v12: the plane as raw quanta, out[ix * ny + iy]; replaces reading Histogram.hist of a
+ * weighted Histogram (histogram.py:54,78 with weights=).  ODW_ERR_INVALID without an enabled
+ * plane or with another bin count.  ODW_ERR_CAPACITY (message in odw_last_error) when any
+ * bin of the COUNT plane holds >= 2^32 hits: such a bin's power sum may have wrapped, and
+ * no plane is handed out.                                                                   */
+int odw_fetch_power_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins);
 /* Overlapped row fetch for continuous runs that keep every hit (the reference
  * buffers hits while the workers trace on and flushes them every few seconds,
  * results_store.py:405-457): two hit lists.  odw_swap_hit_lists puts the list
@@ -483,6 +519,13 @@ int odw_hits_range(odw_ctx* ctx, int32_t polar, const double* origin, double* ra
  * rule: bin = searchsorted(edges, v, 'right') - 1, the last edge closed      */
 int odw_hits_bin(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
                  const double* edges_b, int32_t n_b, uint64_t* counts);
+/* v12: odw_hits_bin with a second plane; replaces numpy.histogram2d(..., weights=powers) of
+ * Histogram.__init__ (histogram.py:54,78 with weights=).  Same selection, projection, edges
+ * and bin rule (the polar tables included): counts as odw_hits_bin gives them, and every
+ * binned row j also adds q(power of row j) (ODW_POWER_QUANTUM_BITS above) to
+ * power[same index].  Both planes are integer sums.                                         */
+int odw_hits_bin_power(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
+                       const double* edges_b, int32_t n_b, uint64_t* counts, uint64_t* power);
 /* mean[3] and variance[3] (about the mean) of the selected rows' points     */
 int odw_hits_moments(odw_ctx* ctx, double* mean, double* var);
 /* The screen of the plane search of `Hits.detectPlaneNormal` (jupyter_utils/hits.py:108-137: the direction along
@@ -532,6 +575,11 @@ int odw_compile_scene(odw_ctx* ctx, int32_t mode);
  * compile_seconds: of the bound kernel (0 if it came from a cache);
  * cache_hit: 0 compiled now, 1 process cache, 2 disk cache                   */
 int odw_compiled_info(odw_ctx* ctx, int32_t* bound, double* compile_seconds, int32_t* cache_hit);
+/* v12: the same question for launches with ODW_TRACE_POWER_HISTOGRAM, which run a variant of the compiled
+ * kernel of their own (compiled on the first such launch; under ODW_COMPILE_AUTO on a thread that starts
+ * with that launch, the generic kernels run meanwhile): bound = the mode if the next weighted launch runs
+ * the compiled variant, 0 if it runs a generic kernel.  Replaces nothing of the reference.             */
+int odw_compiled_power_info(odw_ctx* ctx, int32_t* bound);
 /* no device needed: writes the scene's header (NUL-terminated, truncated to
  * header_capacity) and compiles the kernel for `arch` (NULL: "gfx950");
  * code_bytes = size of the code object.  ODW_ERR_UNSUPPORTED: the scene is
@@ -650,10 +698,17 @@ int odw_archive_reset(odw_ctx* ctx);
  * so that a multi-GPU job sums everything its ranks produced with a single
  * reduce (v9; replaces the file-system merge of the reference's workers,
  * simulation_loop.py:450-507, freecad_document.py:1491-1504).  The block moves
- * when odw_set_detector asks for more bins: take the pointer after it.      */
+ * when odw_set_detector asks for more bins: take the pointer after it.
+ * v12: with an enabled power plane (odw_enable_power_histogram) the block is
+ * [counters][n_bins bins][n_bins words of the power plane] and n_words covers
+ * all three -- still one reduce; switching the plane on may move the block.  */
 int odw_device_results(odw_ctx* ctx, void** dptr, uint64_t* n_words, uint64_t* hist_offset_words);
 /* the two parts of that block by themselves                                 */
 int odw_device_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_bins);
+/* v12: the third part, the power plane (raw quanta): the device view of what
+ * odw_fetch_power_histogram copies (histogram.py:54,78 with weights=).  No
+ * plane enabled: *dptr = NULL, *n_bins = 0                                   */
+int odw_device_power_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_bins);
 int odw_device_counters(odw_ctx* ctx, void** dptr, uint64_t* n);
 int odw_stream(odw_ctx* ctx, void** hip_stream);
 
