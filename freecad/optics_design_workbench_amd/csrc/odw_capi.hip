@@ -1,9 +1,11 @@
 // odw_capi.hip -- C-ABI (include/odw_trace.h) over the gfx950 kernels.
 //
 // Host side of the native library: device context, scene/source upload into
-// the HBM layouts of odw_device.h, BVH build for big scenes, inverse-CDF
-// guide tables, launches on a private HIP stream, HIP-event timing, result
-// fetch.  No torch types anywhere: plain pointers and sizes.
+// the HBM layouts of odw_device.h, inverse-CDF guide tables, the choice of a
+// launch's kernel, launches on a private HIP stream, HIP-event timing, result
+// fetch.  A scene's host tables, boxes, grid and trees are computed without a
+// context (odw_build.h); upload_accel() here puts them on the device.  No
+// torch types anywhere: plain pointers and sizes.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -26,6 +28,7 @@
 #include "odw_kernels.hip"
 #include "odw_grid.hip"
 #include "odw_mesh.hip"
+#include "odw_build.h"
 
 using namespace odw;
 
@@ -52,15 +55,12 @@ constexpr int kSurfaceGuide = 1 << 10;  // per row of a surface sampler (tables 
 // (scripts/bench_lens_train.py, scripts/bench_crowded.py).  ODW_BVH_THRESHOLD (read when a context is created)
 // overrides it: the tests keep the grid kernel's generic variant covered with 16.
 constexpr int kBvhThreshold = 64;
-constexpr int kBvhLeaf = 8;   // largest leaf the SAH may form (measured: 8 >= 4 > 2 > 1 on meshes; round 5, mesh kernel at 1e6 facets: 8 / 6 / 4 / 3 / 2 / 1 = 7.70 / 7.73 / 7.84 / 7.95 / 8.16 / 9.04 ms -- candidates per segment 18 -> 8, node visits 11.7 -> 14.7)
-constexpr int kBvhSweepMax = 256;        // nodes with more primitives use binned SAH
 
 std::string g_error;
 
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
-  bool host = false;       // allocated with malloc (a context without a device: odw_build_check)
 };
 
 }  // namespace
@@ -70,20 +70,11 @@ struct odw_ctx {
   hipStream_t stream = nullptr;
   void* up_pin = nullptr;                  // page-locked arena small uploads are staged in (upload())
   size_t up_off = 0;
-  bool up_unstaged = false;
-  bool host_only = false;                  // no device behind this context: buffers are host memory (odw_build_check)                // an upload since the last wait was copied from the caller's memory
+  bool up_unstaged = false;                // an upload since the last wait was copied from the caller's memory
   int n_cu = 256;
   std::string err;
 
-  // host copies needed for lazy (re)builds
-  std::vector<double> h_prim_f64;
-  std::vector<int32_t> h_prim_i32;
-  std::vector<int32_t> h_cond;            // prim | opens a clause << 30 | inside << 31
-  std::vector<double> h_prim_hdr;         // 64-byte headers (boxes + the four integers), built with the BVH
-  std::vector<char> h_dead;               // primitives no ray can meet (no face, or an empty box)
-  std::vector<double> h_group_f64, h_group_gdir;
-  std::vector<int32_t> h_group_i32;
-  std::vector<uint64_t> h_seq;
+  HostScene hs;                            // host tables of the uploaded scene, needed for lazy (re)builds (odw_build.h)
   // scene-compiled flat kernel (odw_spec.hip)
   int compile_mode = 0;                    // ODW_COMPILE_*: sticky, applies to every scene uploaded later too
   bool spec_dirty = true;                  // scene / limits changed since the last binding attempt
@@ -99,7 +90,6 @@ struct odw_ctx {
   bool have_scene = false, have_source = false, have_limits = false;
   bool bvh_dirty = true;
   int flat_limit = kBvhThreshold;          // most primitives the flat kernels take (ODW_BVH_THRESHOLD at odw_create)
-  bool lean = false;                       // no grating group, no finite absorption length: LEAN kernels
 
   DevBuf prim_f64, prim_hdr, prim_i32, cond_i32, group_f64, group_i32, group_gdir, seq_mask;
   DevBuf bvh_nodes, bvh_prims, tri_nrm;
@@ -222,15 +212,6 @@ int fail(odw_ctx* ctx, int code, const std::string& msg) {
 int ensure(odw_ctx* ctx, DevBuf& b, size_t bytes) {
   if (bytes == 0) bytes = 16;
   if (b.bytes >= bytes && b.p) return ODW_OK;
-  if (ctx && ctx->host_only) {
-    // a context without a device (odw_build_check): the tables the builders "upload" live in host memory -- the same code
-    // paths, under a CPU sanitizer
-    if (b.p) free(b.p);
-    b.p = malloc(bytes);
-    b.bytes = b.p ? bytes : 0;
-    b.host = true;
-    return b.p ? ODW_OK : fail(ctx, ODW_ERR_DEVICE, "out of host memory");
-  }
   if (b.p) HIPCHK(ctx, hipFree(b.p));
   b.p = nullptr;
   b.bytes = 0;
@@ -249,7 +230,6 @@ int upload(odw_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
   int rc = ensure(ctx, b, bytes);
   if (rc) return rc;
   if (!bytes) return ODW_OK;
-  if (ctx->host_only) { std::memcpy(b.p, src, bytes); return ODW_OK; }
   if (bytes <= kUploadStaged) {
     if (!ctx->up_pin) {
       if (hipHostMalloc(&ctx->up_pin, kUploadArena, hipHostMallocDefault) != hipSuccess) { ctx->up_pin = nullptr; (void)hipGetLastError(); }
@@ -282,9 +262,7 @@ int upload_done(odw_ctx* ctx) {
 }
 
 void release(DevBuf& b) {
-  if (b.p && b.host) free(b.p);
-  else if (b.p) (void)hipFree(b.p);
-  b.host = false;
+  if (b.p) (void)hipFree(b.p);
   b.p = nullptr;
   b.bytes = 0;
 }
@@ -300,927 +278,79 @@ void batch_unselect(odw_ctx* ctx);
 // room for the post-hoc chain of a batch (odw_posthoc_batch.hip)
 int phb_reserve(odw_ctx* ctx, int S, uint64_t rays_per_scene, uint64_t slots);
 
-// ---- primitive bounding boxes in global coordinates -----------------------
-void local_bounds(int type, const double* par, double lo[3], double hi[3]) {
-  switch (type) {
-    case ODW_PRIM_BOX:
-      lo[0] = lo[1] = lo[2] = 0; hi[0] = par[0]; hi[1] = par[1]; hi[2] = par[2];
-      break;
-    case ODW_PRIM_SPHERE:
-      for (int i = 0; i < 3; ++i) { lo[i] = -par[0]; hi[i] = par[0]; }
-      break;
-    case ODW_PRIM_CYLINDER:
-      lo[0] = lo[1] = -par[0]; hi[0] = hi[1] = par[0]; lo[2] = 0; hi[2] = par[1];
-      break;
-    case ODW_PRIM_CONE: {
-      const double r = std::max(par[0], par[1]);
-      lo[0] = lo[1] = -r; hi[0] = hi[1] = r; lo[2] = 0; hi[2] = par[2];
-      break;
-    }
-    case ODW_PRIM_PARABOLOID: {
-      const double r = 2.0 * std::sqrt(std::max(par[0] * par[1], 0.0));
-      lo[0] = lo[1] = -r; hi[0] = hi[1] = r; lo[2] = 0; hi[2] = par[1];
-      break;
-    }
-    default: {
-      const double r = par[0] + par[1];
-      lo[0] = lo[1] = -r; hi[0] = hi[1] = r; lo[2] = -par[1]; hi[2] = par[1];
-    }
-  }
+// ---- the scene's structures: built on the host (odw_build.h), uploaded here -------------------
+// (read at every build: the tests that hold the two kernels, and the tree with and without cones, against each other)
+BuildOptions build_options() {
+  BuildOptions o;
+  o.mesh_kernel = !(getenv("ODW_MESH_KERNEL") && getenv("ODW_MESH_KERNEL")[0] == '0');
+  o.cones = !(getenv("ODW_MESH_CONES") && getenv("ODW_MESH_CONES")[0] == '0');
+  o.cone_stats = getenv("ODW_MESH_CONE_STATS") != nullptr;
+  return o;
 }
 
-struct Box {
-  double lo[3], hi[3];
-  void reset() { for (int i = 0; i < 3; ++i) { lo[i] = INFINITY; hi[i] = -INFINITY; } }
-  void grow(const Box& o) {
-    for (int i = 0; i < 3; ++i) { lo[i] = std::min(lo[i], o.lo[i]); hi[i] = std::max(hi[i], o.hi[i]); }
-  }
-};
-
-Box world_box(const double* pf, int type, double slack) {
-  Box b;
-  b.reset();
-  if (type == ODW_PRIM_TRIANGLE) {   // v0, e1, e2 in global coordinates
-    for (int i = 0; i < 3; ++i) {
-      const double a = pf[i], c1 = pf[i] + pf[3 + i], c2 = pf[i] + pf[6 + i];
-      const double s = slack + 1e-9 * (std::fabs(a) + std::fabs(c1) + std::fabs(c2));
-      b.lo[i] = std::min(a, std::min(c1, c2)) - s;
-      b.hi[i] = std::max(a, std::max(c1, c2)) + s;
-    }
-    return b;
-  }
-  double lo[3], hi[3];
-  local_bounds(type, pf + 12, lo, hi);
-  for (int c = 0; c < 8; ++c) {
-    const double l[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
-    // global = R^T (local - t)
-    const double d[3] = {l[0] - pf[3], l[1] - pf[7], l[2] - pf[11]};
-    const double g[3] = {pf[0] * d[0] + pf[4] * d[1] + pf[8] * d[2],
-                         pf[1] * d[0] + pf[5] * d[1] + pf[9] * d[2],
-                         pf[2] * d[0] + pf[6] * d[1] + pf[10] * d[2]};
-    for (int i = 0; i < 3; ++i) { b.lo[i] = std::min(b.lo[i], g[i]); b.hi[i] = std::max(b.hi[i], g[i]); }
-  }
-  for (int i = 0; i < 3; ++i) {
-    const double s = slack + 1e-9 * (std::fabs(b.lo[i]) + std::fabs(b.hi[i]));
-    b.lo[i] -= s;
-    b.hi[i] += s;
-  }
-  return b;
-}
-
-// BVH node, 64 bytes = one cache line: the boxes of BOTH children in float32
-// (rounded outward), so one fetch decides where to go next.  child >= 0: inner
-// node index; count > 0: leaf = `count` primitives from bvh_prims[child].
-struct BvhNode {
-  float lo0[3], hi0[3], lo1[3], hi1[3];
-  int32_t child0, child1, count0, count1;
-};
-static_assert(sizeof(BvhNode) == 64, "BvhNode must be one 64-byte line");
-
-float round_down(double v) {
-  float f = (float)v;
-  return (double)f > v ? std::nextafterf(f, -INFINITY) : f;
-}
-float round_up(double v) {
-  float f = (float)v;
-  return (double)f < v ? std::nextafterf(f, INFINITY) : f;
-}
-
-// Surface-area-heuristic build (full sweep on the three axes).  Measured on
-// hugeArray: 33 node visits and 3.0 primitive tests per segment against 57 /
-// 5.8 with median splits.
-struct BvhBuilder {
-  const std::vector<Box>& boxes;
-  std::vector<int> order;       // leaf primitive order
-  std::vector<BvhNode> nodes;
-  int max_depth = 0;
-
-  // The heuristic goes on wherever the levels that are left still hold a median-split subtree of the node's primitives
-  // down to leaves of kBvhLeaf; below that, median splits keep the tree within the traversal stack (round 5: against
-  // medians from a fixed depth on, ball lens of 1e6 facets under the mesh kernel: 12.8 -> 7.2 candidate facets per
-  // segment, 6.02 -> 5.77 ms per 1e7 rays, build 0.8 -> 1.1 s; full sweeps only up to kBvhSweepMax primitives).
-  explicit BvhBuilder(const std::vector<Box>& b) : boxes(b) {}
-  bool sah_ok(int depth, int m) const {
-    const int need = (int)std::ceil(std::log2(std::max(1.0, (double)m / kBvhLeaf)));
-    return depth + need + 2 <= ODW_BVH_STACK - 3;
-  }
-
-  static double area(const Box& b) {
-    const double ex = b.hi[0] - b.lo[0], ey = b.hi[1] - b.lo[1], ez = b.hi[2] - b.lo[2];
-    return 2.0 * (ex * ey + ey * ez + ez * ex);
-  }
-
-  struct Ref { int32_t child, count; Box box; };
-
-  // builds the subtree over ids; returns either a leaf ref or an inner node ref
-  Ref build(std::vector<int>& ids, int depth) {
-    max_depth = std::max(max_depth, depth);
-    Box bb;
-    bb.reset();
-    for (int i : ids) bb.grow(boxes[i]);
-    const int m = (int)ids.size();
-    auto make_leaf = [&]() {
-      Ref r;
-      r.child = (int32_t)order.size();
-      r.count = m;
-      r.box = bb;
-      for (int i : ids) order.push_back(i);
-      return r;
-    };
-    if (m <= 1) return make_leaf();
-    const bool sah = sah_ok(depth, m);
-    if (!sah && m <= kBvhLeaf) return make_leaf();
-    if (m > kBvhSweepMax || !sah) return build_big(ids, depth, bb);
-    // SAH sweep
-    double best_cost = INFINITY;
-    int best_axis = -1, best_split = 0;
-    std::vector<int> sorted(ids), best_sorted;
-    std::vector<double> right_area(m);
-    for (int a = 0; a < 3; ++a) {
-      std::sort(sorted.begin(), sorted.end(), [&](int x, int y) {
-        const double cx = boxes[x].lo[a] + boxes[x].hi[a], cy = boxes[y].lo[a] + boxes[y].hi[a];
-        return cx < cy || (cx == cy && x < y);
-      });
-      Box r;
-      r.reset();
-      for (int i = m - 1; i > 0; --i) { r.grow(boxes[sorted[i]]); right_area[i] = area(r); }
-      Box l;
-      l.reset();
-      for (int i = 1; i < m; ++i) {
-        l.grow(boxes[sorted[i - 1]]);
-        const double cost = area(l) * i + right_area[i] * (m - i);
-        if (cost < best_cost) { best_cost = cost; best_axis = a; best_split = i; best_sorted = sorted; }
-      }
-    }
-    // leaf if splitting does not pay (traversal step ~ 1 primitive test) and it is small
-    const double leaf_cost = area(bb) * m;
-    if (m <= kBvhLeaf && best_cost + area(bb) >= leaf_cost) return make_leaf();
-    if (best_axis < 0) return make_leaf();
-    std::vector<int> left(best_sorted.begin(), best_sorted.begin() + best_split);
-    std::vector<int> right(best_sorted.begin() + best_split, best_sorted.end());
-    return inner(left, right, depth, bb);
-  }
-
-  // big nodes (meshes): binned SAH over 32 bins of the centroid range, O(m) per
-  // node; where sah_ok() says no: median splits, which bound the remaining
-  // depth by log2(m / kBvhLeaf)
-  Ref build_big(std::vector<int>& ids, int depth, const Box& bb) {
-    const int m = (int)ids.size();
-    Box cb;
-    cb.reset();
-    for (int i : ids)
-      for (int a = 0; a < 3; ++a) {
-        const double c = boxes[i].lo[a] + boxes[i].hi[a];
-        cb.lo[a] = std::min(cb.lo[a], c);
-        cb.hi[a] = std::max(cb.hi[a], c);
-      }
-    int axis = 0;
-    for (int a = 1; a < 3; ++a) if (cb.hi[a] - cb.lo[a] > cb.hi[axis] - cb.lo[axis]) axis = a;
-    auto centroid = [&](int i, int a) { return boxes[i].lo[a] + boxes[i].hi[a]; };
-    std::vector<int> left, right;
-    bool split_done = false;
-    if (sah_ok(depth, m) && cb.hi[axis] > cb.lo[axis]) {
-      constexpr int kBins = 32;
-      double best_cost = INFINITY;
-      int best_axis = -1, best_bin = 0;
-      for (int a = 0; a < 3; ++a) {
-        const double ext = cb.hi[a] - cb.lo[a];
-        if (!(ext > 0)) continue;
-        Box bins[kBins];
-        int cnt[kBins] = {0};
-        for (auto& b : bins) b.reset();
-        for (int i : ids) {
-          const int k = std::min(kBins - 1, (int)((centroid(i, a) - cb.lo[a]) / ext * kBins));
-          bins[k].grow(boxes[i]);
-          ++cnt[k];
-        }
-        double ra[kBins];
-        int rc[kBins];
-        Box r;
-        r.reset();
-        int c = 0;
-        for (int k = kBins - 1; k > 0; --k) { r.grow(bins[k]); c += cnt[k]; ra[k] = c ? area(r) : 0.0; rc[k] = c; }
-        Box l;
-        l.reset();
-        c = 0;
-        for (int k = 1; k < kBins; ++k) {
-          l.grow(bins[k - 1]);
-          c += cnt[k - 1];
-          if (c == 0 || rc[k] == 0) continue;
-          const double cost = area(l) * c + ra[k] * rc[k];
-          if (cost < best_cost) { best_cost = cost; best_axis = a; best_bin = k; }
-        }
-      }
-      if (best_axis >= 0) {
-        const double ext = cb.hi[best_axis] - cb.lo[best_axis];
-        for (int i : ids) {
-          const int k = std::min(kBins - 1, (int)((centroid(i, best_axis) - cb.lo[best_axis]) / ext * kBins));
-          (k < best_bin ? left : right).push_back(i);
-        }
-        split_done = !left.empty() && !right.empty();
-      }
-    }
-    if (!split_done) {   // median split along the widest centroid axis
-      std::vector<int> sorted(ids);
-      std::nth_element(sorted.begin(), sorted.begin() + m / 2, sorted.end(), [&](int x, int y) {
-        const double cx = centroid(x, axis), cy = centroid(y, axis);
-        return cx < cy || (cx == cy && x < y);
-      });
-      left.assign(sorted.begin(), sorted.begin() + m / 2);
-      right.assign(sorted.begin() + m / 2, sorted.end());
-    }
-    return inner(left, right, depth, bb);
-  }
-
-  Ref inner(std::vector<int>& left, std::vector<int>& right, int depth, const Box& bb) {
-    const int id = (int)nodes.size();
-    nodes.emplace_back();
-    const Ref l = build(left, depth + 1);
-    const Ref r = build(right, depth + 1);
-    BvhNode& nd = nodes[id];
-    for (int k = 0; k < 3; ++k) {
-      nd.lo0[k] = round_down(l.box.lo[k]); nd.hi0[k] = round_up(l.box.hi[k]);
-      nd.lo1[k] = round_down(r.box.lo[k]); nd.hi1[k] = round_up(r.box.hi[k]);
-    }
-    nd.child0 = l.child; nd.count0 = l.count;
-    nd.child1 = r.child; nd.count1 = r.count;
-    Ref out;
-    out.child = id;
-    out.count = 0;
-    out.box = bb;
-    return out;
-  }
-};
-
-
-// ---- eight-wide tree of the mesh kernel (odw_mesh.hip) --------------------------------------
-// The binary tree above, collapsed: a wide node takes up to eight descendants of a binary node (the one with the
-// largest box is opened next; one whose subtree is too high for the levels that remain goes first -- that bounds
-// the depth, and with one stack entry per level the traversal stack, at kWideMaxDepth + 1).  The children's boxes
-// are stored as 8-bit offsets from the node's corner in units of a power of two per axis (rounded outward);
-// children sit in the slot whose sign pattern (x, y, z: away from / towards the corner) fits the direction from
-// the node's centre to theirs best, so that `slot XOR ray octant` orders them roughly front to back without a
-// sort.  Inner children are consecutive nodes (slot order), the facets of leaf children consecutive leaf
-// records (slot order, <= 15 per leaf).
-// Node = 32 words (128 bytes, 20 used):
-//   0..2 corner (float)            3  exponent bytes x | y << 8 | z << 16 (biased: scale = 2^(e - 127))
-//   4    first inner child         5  first leaf record
-//   6    inner slots | leaf slots << 8          7  facets per leaf slot (4 bits each)
-//   8..13 near corner offsets: x of slots 0-3, x of 4-7, y, y, z, z     14..19 far corner offsets, the same way
-//   20..23 the solid every primitive below a slot belongs to (16 bits per slot, 0xffff: several or none): a ray that
-//          has just left a convex solid drops the slots of that solid before it looks at their boxes' order
-//   24..31 per slot, the cone of the outward normals of the facets below it, where they all belong to ONE STRICTLY
-//          CONVEX solid: bytes 0..2 an axis a = round(127 u) (signed), byte 3 a threshold T + 3 <= 126 (signed); no cone:
-//          0, 0, 0, 127.  A ray that travels INSIDE that solid (it entered through one of its facets, odw_mesh.hip `inside`)
-//          can only leave through facets it meets from behind, d . n > 0; the kernel drops a slot when
-//          v_dot4(word, [round(127 d), 127]) < 0, i.e. round(127 d) . a < -127 (T + 3): then d . a < -(T + 1.5) whatever the
-//          rounding of d did (|round(127 d) - 127 d| <= 0.5 per axis, |a|_1 <= 220: 110 of the 190 to spare), and with
-//          T = ceil(|a| sin(widest angle between a and a normal + asin(cone_margin))) every facet below the slot has
-//          d . n < -cone_margin -- the whole neighbourhood of the facet the ray starts on, for one.  cone_margin
-//          (WideBvh::margin) is what keeps the rule exact: the start point lies on its facet up to the closed-edge slack, so
-//          it is above the plane of a dropped facet by less than `above`, and the plane would be met at
-//          t < above / margin <= dist_tol, where consider() rejects it anyway.
-constexpr int kWideWords = 32;
-constexpr int kWideMaxDepth = 11;
-
-struct WideBvh {
-  struct Ref { int32_t child, count; float lo[3], hi[3]; };     // count > 0: leaf of `count` primitives from order[child]
-  const std::vector<BvhNode>& bn;
-  const std::vector<int>& order;
-  const std::vector<int>& solid_of;           // solid id of every primitive
-  const float* out_normal = nullptr;          // 3 per primitive: outward unit normal of the facets of convex solids, NaN for the rest
-  double margin = 1.0;                        // >= 0.5: no cones
-  std::vector<int> span_lo, span_hi;          // per binary node: its primitives are order[span_lo .. span_hi)
-  std::vector<int> height;
-  std::vector<int> solid_below;               // per binary node: the one solid of its primitives, -1 several, -2 not asked yet
-  std::vector<uint32_t> nodes;
-  std::vector<int> leaf_prim;                 // primitive of every leaf record
-  std::vector<float> leaf_center;             // 3 per record: the centre its group is expressed around
-  int depth = 0;
-  bool ok = true;
-
-  WideBvh(const std::vector<BvhNode>& n, const std::vector<int>& o, const std::vector<int>& so)
-      : bn(n), order(o), solid_of(so), height(n.size(), -1), solid_below(n.size(), -2) {}
-
-  int ref_solid(const Ref& r) {
-    if (r.count == 0) return node_solid(r.child);
-    int s = solid_of[order[(size_t)r.child]];
-    for (int k = 1; k < r.count; ++k)
-      if (solid_of[order[(size_t)r.child + k]] != s) return -1;
-    return s;
-  }
-  int node_solid(int n) {
-    if (solid_below[n] != -2) return solid_below[n];
-    const BvhNode& nd = bn[n];
-    int s = -3;                                 // nothing seen yet
-    for (const Ref& r : {ref0(nd), ref1(nd)}) {
-      if (far_box(r.lo)) continue;
-      const int c = ref_solid(r);
-      s = s == -3 ? c : (s == c ? s : -1);
-    }
-    return solid_below[n] = s == -3 ? -1 : s;
-  }
-
-  // (leaves are written to `order` in the order the builder meets them: a subtree's primitives are one run of it)
-  void node_span(int n, int& lo, int& hi) {
-    if (span_lo.empty()) { span_lo.assign(bn.size(), -1); span_hi.assign(bn.size(), -1); }
-    if (span_lo[n] < 0) {
-      int l = INT32_MAX, h = 0;
-      const BvhNode& nd = bn[n];
-      for (const Ref& r : {ref0(nd), ref1(nd)}) {
-        if (far_box(r.lo)) continue;
-        int a, b;
-        if (r.count > 0) { a = r.child; b = r.child + r.count; } else node_span(r.child, a, b);
-        l = std::min(l, a); h = std::max(h, b);
-      }
-      span_lo[n] = l == INT32_MAX ? 0 : l; span_hi[n] = h;
-    }
-    lo = span_lo[n]; hi = span_hi[n];
-  }
-  // the cone word of a slot (see the node layout above)
-  uint32_t cone_word(const Ref& r) {
-    constexpr uint32_t none = 0x7f000000u;
-    if (!out_normal || !(margin < 0.5)) return none;
-    int lo, hi;
-    if (r.count > 0) { lo = r.child; hi = r.child + r.count; } else node_span(r.child, lo, hi);
-    double sum[3] = {0.0, 0.0, 0.0};
-    for (int k = lo; k < hi; ++k) {
-      const float* nv = out_normal + 3 * (size_t)order[(size_t)k];
-      if (!(nv[0] == nv[0])) return none;
-      for (int a = 0; a < 3; ++a) sum[a] += (double)nv[a];
-    }
-    const double len = std::sqrt(sum[0] * sum[0] + sum[1] * sum[1] + sum[2] * sum[2]);
-    if (!(len > 1e-6 * (double)(hi - lo)) || hi <= lo) return none;
-    int ax[3];
-    double al = 0.0;
-    for (int a = 0; a < 3; ++a) { ax[a] = (int)std::lround(127.0 * sum[a] / len); al += (double)ax[a] * ax[a]; }
-    al = std::sqrt(al);
-    if (!(al > 100.0)) return none;
-    double cmin = 1.0;
-    for (int k = lo; k < hi; ++k) {
-      const float* nv = out_normal + 3 * (size_t)order[(size_t)k];
-      const double nl = std::sqrt((double)nv[0] * nv[0] + (double)nv[1] * nv[1] + (double)nv[2] * nv[2]);
-      cmin = std::min(cmin, ((double)nv[0] * ax[0] + (double)nv[1] * ax[1] + (double)nv[2] * ax[2]) / (al * nl));
-    }
-    // (1e-5: the normals are float32 copies of unit vectors, the ray's direction is rounded to float32 in the kernel)
-    const double theta = std::acos(std::max(-1.0, std::min(1.0, cmin))) + std::asin(margin) + 1e-5;
-    if (!(theta < 1.5)) return none;
-    const double t = std::ceil(al * std::sin(theta));
-    if (!(t + 3.0 <= 126.0)) return none;                      // (cones that wide drop next to nothing)
-    return (uint32_t)(ax[0] & 0xff) | ((uint32_t)(ax[1] & 0xff) << 8) | ((uint32_t)(ax[2] & 0xff) << 16) | ((uint32_t)(t + 3.0) << 24);
-  }
-
-  static bool far_box(const float* lo) { return lo[0] >= 3.0e38f; }        // the child a wrapper root does not have
-  static Ref ref0(const BvhNode& nd) { Ref r{nd.child0, nd.count0, {nd.lo0[0], nd.lo0[1], nd.lo0[2]}, {nd.hi0[0], nd.hi0[1], nd.hi0[2]}}; return r; }
-  static Ref ref1(const BvhNode& nd) { Ref r{nd.child1, nd.count1, {nd.lo1[0], nd.lo1[1], nd.lo1[2]}, {nd.hi1[0], nd.hi1[1], nd.hi1[2]}}; return r; }
-
-  int node_height(int n) {
-    if (height[n] >= 0) return height[n];
-    const BvhNode& nd = bn[n];
-    int h = 0;
-    if (nd.count0 == 0 && !far_box(nd.lo0)) h = std::max(h, node_height(nd.child0));
-    if (nd.count1 == 0 && !far_box(nd.lo1)) h = std::max(h, node_height(nd.child1));
-    return height[n] = h + 1;
-  }
-  static double area(const Ref& r) {
-    const double ex = (double)r.hi[0] - r.lo[0], ey = (double)r.hi[1] - r.lo[1], ez = (double)r.hi[2] - r.lo[2];
-    return 2.0 * (ex * ey + ey * ez + ez * ex);
-  }
-
-  void build() {
-    if (bn.empty()) { ok = false; return; }
-    if (node_height(0) > 3 * (kWideMaxDepth + 1)) { ok = false; return; }
-    nodes.assign(kWideWords, 0u);
-    fill(0, 0, 0);
-  }
-
-  void fill(size_t index, int n, int d) {
-    depth = std::max(depth, d);
-    if (d > kWideMaxDepth) { ok = false; return; }
-    std::vector<Ref> cand;
-    for (const Ref& r : {ref0(bn[n]), ref1(bn[n])})
-      if (!far_box(r.lo)) cand.push_back(r);
-    const int allowed = 3 * (kWideMaxDepth - d);             // binary height a child's subtree may have
-    while (cand.size() < 8) {
-      int pick = -1;
-      int tallest = allowed;
-      for (size_t k = 0; k < cand.size(); ++k)
-        if (cand[k].count == 0 && node_height(cand[k].child) > tallest) { tallest = node_height(cand[k].child); pick = (int)k; }
-      if (pick < 0) {
-        double best = -1.0;
-        for (size_t k = 0; k < cand.size(); ++k)
-          if (cand[k].count == 0 && area(cand[k]) > best) { best = area(cand[k]); pick = (int)k; }
-      }
-      if (pick < 0) break;                                     // leaves only
-      const BvhNode& nd = bn[cand[pick].child];
-      cand[pick] = ref0(nd);
-      cand.push_back(ref1(nd));
-    }
-    // the node's box and the slots
-    float lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (const Ref& r : cand)
-      for (int a = 0; a < 3; ++a) { lo[a] = std::min(lo[a], r.lo[a]); hi[a] = std::max(hi[a], r.hi[a]); }
-    int slot_of[8], cand_in[8];
-    for (int k = 0; k < 8; ++k) { slot_of[k] = -1; cand_in[k] = -1; }
-    {
-      struct Pair { double cost; int c, s; };
-      std::vector<Pair> pairs;
-      for (size_t c = 0; c < cand.size(); ++c)
-        for (int sl = 0; sl < 8; ++sl) {
-          double cost = 0.0;
-          for (int a = 0; a < 3; ++a) {
-            const double v = 0.5 * ((double)cand[c].lo[a] + cand[c].hi[a]) - 0.5 * ((double)lo[a] + hi[a]);
-            cost += ((sl >> a) & 1) ? v : -v;
-          }
-          pairs.push_back({cost, (int)c, sl});
-        }
-      std::stable_sort(pairs.begin(), pairs.end(), [](const Pair& x, const Pair& y) { return x.cost > y.cost; });
-      for (const Pair& pr : pairs)
-        if (slot_of[pr.c] < 0 && cand_in[pr.s] < 0) { slot_of[pr.c] = pr.s; cand_in[pr.s] = pr.c; }
-    }
-    uint32_t w[kWideWords] = {0};
-    uint32_t ebyte[3];
-    double scale[3];
-    for (int a = 0; a < 3; ++a) {
-      std::memcpy(&w[a], &lo[a], 4);
-      const double ext = (double)hi[a] - (double)lo[a];
-      int e = -100;
-      if (ext > 0) {
-        int ex2;
-        std::frexp(ext / 255.0, &ex2);                        // ext / 255 = m 2^ex2, 0.5 <= m < 1: 2^ex2 >= ext / 255
-        e = ex2;
-      }
-      e = std::max(-126, std::min(127, e));
-      while (std::ldexp(255.0, e) < ext && e < 127) ++e;
-      ebyte[a] = (uint32_t)(e + 127);
-      scale[a] = std::ldexp(1.0, e);
-    }
-    w[3] = ebyte[0] | (ebyte[1] << 8) | (ebyte[2] << 16);
-    uint32_t imask = 0, lmask = 0, counts = 0;
-    const uint32_t child_base = (uint32_t)(nodes.size() / kWideWords);
-    const uint32_t leaf_base = (uint32_t)leaf_prim.size();
-    int n_inner = 0;
-    float glo[3] = {INFINITY, INFINITY, INFINITY}, ghi[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int sl = 0; sl < 8; ++sl) {
-      const int c = cand_in[sl];
-      if (c < 0) { w[24 + sl] = 0x7f000000u; continue; }
-      const Ref& r = cand[c];
-      if (r.count == 0) { imask |= 1u << sl; ++n_inner; }
-      else {
-        if (r.count > 15) { ok = false; return; }
-        lmask |= 1u << sl;
-        counts |= (uint32_t)r.count << (4 * sl);
-        for (int a = 0; a < 3; ++a) { glo[a] = std::min(glo[a], r.lo[a]); ghi[a] = std::max(ghi[a], r.hi[a]); }
-      }
-      {
-        const int so = ref_solid(r);
-        w[20 + (sl >> 1)] |= (uint32_t)((so >= 0 && so < 0xffff) ? so : 0xffff) << (16 * (sl & 1));
-        w[24 + sl] = (so >= 0 && so < 0xffff) ? cone_word(r) : 0x7f000000u;
-      }
-      for (int a = 0; a < 3; ++a) {
-        const double ql = std::floor(((double)r.lo[a] - (double)lo[a]) / scale[a]);
-        const double qh = std::ceil(((double)r.hi[a] - (double)lo[a]) / scale[a]);
-        const uint32_t bl = (uint32_t)std::max(0.0, std::min(255.0, ql)), bh = (uint32_t)std::max(0.0, std::min(255.0, qh));
-        if (qh > 255.0) { ok = false; return; }                // (cannot happen: 255 scale >= extent)
-        w[8 + 2 * a + (sl >> 2)] |= bl << (8 * (sl & 3));
-        w[14 + 2 * a + (sl >> 2)] |= bh << (8 * (sl & 3));
-      }
-    }
-    {
-      int total = 0;
-      for (int sl = 0; sl < 8; ++sl) total += (int)((counts >> (4 * sl)) & 15u);
-      if (total > 64) { ok = false; return; }                  // (the kernel's candidate mask)
-    }
-    w[4] = child_base;
-    w[5] = leaf_base;
-    w[6] = imask | (lmask << 8);
-    w[7] = counts;
-    std::memcpy(&nodes[index * kWideWords], w, sizeof w);
-    // leaf records of this node, slot order
-    const float gc[3] = {0.5f * glo[0] + 0.5f * ghi[0], 0.5f * glo[1] + 0.5f * ghi[1], 0.5f * glo[2] + 0.5f * ghi[2]};
-    for (int sl = 0; sl < 8; ++sl) {
-      const int c = cand_in[sl];
-      if (c < 0 || cand[c].count == 0) continue;
-      for (int k = 0; k < cand[c].count; ++k) {
-        leaf_prim.push_back(order[(size_t)cand[c].child + k]);
-        leaf_center.insert(leaf_center.end(), gc, gc + 3);
-      }
-    }
-    // inner children: consecutive nodes, slot order
-    nodes.resize(nodes.size() + (size_t)n_inner * kWideWords, 0u);
-    int rank = 0;
-    for (int sl = 0; sl < 8; ++sl) {
-      const int c = cand_in[sl];
-      if (c < 0 || cand[c].count != 0) continue;
-      const int child = cand[c].child;
-      fill((size_t)child_base + rank, child, d + 1);
-      if (!ok) return;
-      ++rank;
-    }
-  }
-};
-
-
-// ---- rectilinear grid for big analytic scenes (odw_grid.hip) ---------------------------------
-// Planes per axis: one in the middle of every gap between the primitives' boxes (projected on the
-// axis) -- a Draft array gets one element per cell --, then slabs wider than twice the width an
-// even division into ~cbrt(n) cells per axis would give are cut evenly.  Cell lists (CSR): every
-// primitive whose box touches the cell.  The walk is exact whatever the planes are; they only
-// decide how many cells a ray crosses and how many primitives it tests per cell.
-constexpr int kGridMaxAxis = 128;             // cells per axis (8 bits each in the walk's cell word)
-constexpr uint32_t kGridMaxCellItems = 255;   // 8-bit count in the cell word
-constexpr size_t kGridLdsBudget = 144 * 1024; // of the CU's 160 KB, one block per CU
-
-int build_grid(odw_ctx* ctx, const std::vector<Box>& boxes, const std::vector<char>& dead) {
+// The headers and flag words of ctx->hs (compute_boxes has set ODW_FLAG_ISOLATED in them) and the tables of A into
+// the context's buffers, their addresses into P.scene / P.grid.  Tables above kUploadStaged are copied in place and
+// asynchronously: upload_done() below is what lets the caller drop A (and change ctx->hs) as soon as this returns.
+int upload_accel(odw_ctx* ctx, const SceneAccel& A) {
+  const HostScene& hs = ctx->hs;
+  const bool grid = A.grid.nx > 0, tree = !A.nodes.empty(), wide = !A.leaf_recs.empty();
+  const struct { bool on; DevBuf* buf; const void* src; size_t bytes; } tables[] = {
+      {true, &ctx->prim_hdr, hs.prim_hdr.data(), hs.prim_hdr.size() * sizeof(double)},
+      {hs.n_prims > 0, &ctx->prim_i32, hs.prim_i32.data(), hs.prim_i32.size() * sizeof(int32_t)},
+      {grid, &ctx->grid_bounds, A.planes.data(), A.planes.size() * sizeof(double)},
+      {grid, &ctx->grid_cells, A.cells.data(), A.cells.size() * sizeof(uint32_t)},
+      {grid, &ctx->grid_items, A.items(), A.item_bytes()},
+      {tree, &ctx->bvh_nodes, A.nodes.data(), A.nodes.size() * sizeof(BvhNode)},
+      {tree, &ctx->bvh_prims, A.order.data(), A.order.size() * sizeof(int)},
+      {wide, &ctx->bvh_leaf, A.leaf_recs.data(), A.leaf_recs.size() * sizeof(float)},
+      {wide, &ctx->bvh_wide, A.wide_nodes.data(), A.wide_nodes.size() * sizeof(uint32_t)}};
+  int rc = ODW_OK;
+  for (const auto& t : tables)
+    if (t.on && !rc) rc = upload(ctx, *t.buf, t.src, t.bytes);
+  const int rc_done = upload_done(ctx);        // (also after a failed upload: an earlier one may still be reading A)
+  DeviceScene& S = ctx->P.scene;
   DeviceGrid& G = ctx->P.grid;
   std::memset(&G, 0, sizeof G);
-  const int n = (int)boxes.size();
-  std::vector<int> live;
-  for (int p = 0; p < n; ++p)
-    if (!dead[p]) live.push_back(p);
-  if (live.empty()) return ODW_OK;
-  Box all;
-  all.reset();
-  for (int p : live) all.grow(boxes[p]);
-  double ext[3], vol = 1.0;
-  for (int a = 0; a < 3; ++a) { ext[a] = std::max(all.hi[a] - all.lo[a], 1e-9); vol *= ext[a]; }
-  const double per_len = std::cbrt((double)live.size() / vol);     // cells per unit length for ~1 primitive per cell
-  std::vector<double> planes[3];
-  for (int a = 0; a < 3; ++a) {
-    std::vector<std::pair<double, double>> iv;
-    for (int p : live) iv.emplace_back(boxes[p].lo[a], boxes[p].hi[a]);
-    std::sort(iv.begin(), iv.end());
-    const double pad = 1e-6 * (1.0 + ext[a]);
-    std::vector<double> b{all.lo[a] - pad};
-    double cover = iv[0].second;
-    for (size_t k = 1; k < iv.size(); ++k) {
-      if (iv[k].first > cover) b.push_back(0.5 * (cover + iv[k].first));
-      cover = std::max(cover, iv[k].second);
-    }
-    b.push_back(all.hi[a] + pad);
-    const double target = 1.0 / std::max(per_len, 1e-12);          // width of a cell of the even division
-    std::vector<double> cut{b[0]};
-    for (size_t k = 1; k < b.size(); ++k) {
-      const double wdt = b[k] - b[k - 1];
-      const int parts = wdt > 2.0 * target ? (int)std::min<double>(kGridMaxAxis, std::floor(wdt / target + 0.5)) : 1;
-      for (int j = 1; j <= parts; ++j) cut.push_back(j == parts ? b[k] : b[k - 1] + wdt * j / parts);
-    }
-    if ((int)cut.size() - 1 > kGridMaxAxis) {                     // too fine: even division
-      cut.clear();
-      for (int j = 0; j <= kGridMaxAxis; ++j) cut.push_back(b.front() + (b.back() - b.front()) * j / kGridMaxAxis);
-      cut.back() = b.back();
-    }
-    planes[a] = cut;
+  S.n_nodes = 0;
+  S.bvh_leaf = nullptr;
+  S.bvh_wide = nullptr;
+  if (rc || rc_done) return rc ? rc : rc_done;
+  S.prim_hdr = (const double*)ctx->prim_hdr.p;
+  if (grid) {
+    G = A.grid;
+    G.bounds = (const double*)ctx->grid_bounds.p;
+    G.cells = (const uint32_t*)ctx->grid_cells.p;
+    G.items = ctx->grid_items.p;
   }
-  const int nx = (int)planes[0].size() - 1, ny = (int)planes[1].size() - 1, nz = (int)planes[2].size() - 1;
-  const size_t ncell = (size_t)nx * ny * nz;
-  if (ncell > (1u << 21)) return ODW_OK;
-  // cell ranges of every primitive (closed boxes: a box that ends on a plane is listed on both sides)
-  auto range = [&](int a, double lo, double hi, int& i0, int& i1) {
-    const std::vector<double>& b = planes[a];
-    const int m = (int)b.size() - 1;
-    i0 = (int)(std::upper_bound(b.begin(), b.end(), lo) - b.begin()) - 1;     // last plane <= lo
-    if (i0 > 0 && b[i0] == lo) --i0;
-    i1 = (int)(std::lower_bound(b.begin(), b.end(), hi) - b.begin()) - 1;     // slab whose upper plane >= hi
-    if (i1 + 1 < m && b[i1 + 1] == hi) ++i1;
-    i0 = std::max(0, std::min(m - 1, i0));
-    i1 = std::max(i0, std::min(m - 1, i1));
-  };
-  std::vector<uint32_t> count(ncell, 0);
-  std::vector<int> r(6 * (size_t)live.size());
-  for (size_t k = 0; k < live.size(); ++k) {
-    const Box& bx = boxes[live[k]];
-    int* q = &r[6 * k];
-    range(0, bx.lo[0], bx.hi[0], q[0], q[1]);
-    range(1, bx.lo[1], bx.hi[1], q[2], q[3]);
-    range(2, bx.lo[2], bx.hi[2], q[4], q[5]);
-    for (int z = q[4]; z <= q[5]; ++z)
-      for (int y = q[2]; y <= q[3]; ++y)
-        for (int x = q[0]; x <= q[1]; ++x) ++count[x + (size_t)nx * (y + (size_t)ny * z)];
+  if (tree) {
+    S.bvh_nodes = (const float*)ctx->bvh_nodes.p;
+    S.bvh_prims = (const int32_t*)ctx->bvh_prims.p;
+    S.n_nodes = (int)A.nodes.size();
   }
-  size_t total = 0;
-  std::vector<uint32_t> first(ncell);
-  for (size_t c = 0; c < ncell; ++c) {
-    if (count[c] > kGridMaxCellItems) return ODW_OK;              // crowded beyond the cell word: BVH kernels
-    first[c] = (uint32_t)total;
-    total += count[c];
+  if (wide) {
+    S.bvh_leaf = (const float*)ctx->bvh_leaf.p;
+    S.bvh_wide = (const uint32_t*)ctx->bvh_wide.p;
+    for (int a = 0; a < 3; ++a) { S.wide_lo[a] = A.wide_lo[a]; S.wide_hi[a] = A.wide_hi[a]; }
   }
-  if (total >= (1u << 24)) return ODW_OK;
-  std::vector<uint32_t> item_prim(std::max<size_t>(total, 1)), fill(ncell, 0);
-  for (size_t k = 0; k < live.size(); ++k) {
-    const int* q = &r[6 * k];
-    for (int z = q[4]; z <= q[5]; ++z)
-      for (int y = q[2]; y <= q[3]; ++y)
-        for (int x = q[0]; x <= q[1]; ++x) {
-          const size_t c = x + (size_t)nx * (y + (size_t)ny * z);
-          item_prim[first[c] + fill[c]++] = (uint32_t)live[k];
-        }
-  }
-  std::vector<uint32_t> cells(ncell);
-  for (size_t c = 0; c < ncell; ++c) cells[c] = first[c] | (count[c] << 24);
-  bool spheres = true;
-  for (int p : live) {
-    const int32_t* pi = &ctx->h_prim_i32[4 * (size_t)p];
-    if (pi[0] != ODW_PRIM_SPHERE || ((pi[3] >> 24) & 0xff) != 0) { spheres = false; break; }
-  }
-  std::vector<double> bounds;
-  for (int a = 0; a < 3; ++a) bounds.insert(bounds.end(), planes[a].begin(), planes[a].end());
-  int rc;
-  if ((rc = upload(ctx, ctx->grid_bounds, bounds.data(), bounds.size() * sizeof(double)))) return rc;
-  if ((rc = upload(ctx, ctx->grid_cells, cells.data(), cells.size() * sizeof(uint32_t)))) return rc;
-  size_t item_bytes;
-  std::vector<double> recs;
-  if (spheres) {
-    // 48-byte records: centre (global; prim_f64 12..15 = R, cx, cy, cz as the flat kernel reads them),
-    // radius, {primitive, group | solid << 8}, the primitive's flag word
-    recs.resize(std::max<size_t>(total, 1) * 6, 0.0);
-    for (size_t k = 0; k < total; ++k) {
-      const uint32_t p = item_prim[k];
-      const double* par = ctx->h_prim_f64.data() + 16 * (size_t)p + 12;
-      const int32_t* pi = &ctx->h_prim_i32[4 * (size_t)p];
-      double* o = &recs[6 * k];
-      o[0] = par[1]; o[1] = par[2]; o[2] = par[3]; o[3] = par[0];
-      const uint64_t bits = (uint64_t)p | ((uint64_t)(uint32_t)((pi[1] & 0xff) | ((pi[2] >> ODW_SOLID_SHIFT) << 8)) << 32);
-      std::memcpy(&o[4], &bits, sizeof bits);
-      const uint64_t flag_word = (uint64_t)(uint32_t)pi[2];          // (flags | facemask << 8 | solid << 16, for the interaction)
-      std::memcpy(&o[5], &flag_word, sizeof flag_word);
-    }
-    item_bytes = recs.size() * sizeof(double);
-    if ((rc = upload(ctx, ctx->grid_items, recs.data(), item_bytes))) return rc;
-  } else {
-    item_prim.resize((item_prim.size() + 1) & ~(size_t)1, 0u);      // whole doubles (the LDS copy moves 8 bytes at a time)
-    item_bytes = item_prim.size() * sizeof(uint32_t);
-    if ((rc = upload(ctx, ctx->grid_items, item_prim.data(), item_bytes))) return rc;
-  }
-  if ((rc = upload_done(ctx))) return rc;                           // host vectors die with this scope
-  // the kernel's LDS image (odw_grid_kernel, same arithmetic): planes | per-wave words | ray rings | cells | items
-  const size_t nbp = bounds.size();
-  const size_t word_off = 2 * nbp;
-  const size_t ring_off = (word_off + (size_t)ODW_GRID_WAVES * ODW_GRID_WAVE_WORDS + 1) / 2;
-  const size_t cell_off = 2 * (ring_off + (size_t)ODW_GRID_WAVES * ODW_GRID_RING_DOUBLES);
-  const size_t fixed = cell_off * sizeof(uint32_t);
-  const size_t staged = (((cell_off + ncell + 3) & ~(size_t)3) / 2) * sizeof(double) + item_bytes;
-  G.bounds = (const double*)ctx->grid_bounds.p;
-  G.cells = (const uint32_t*)ctx->grid_cells.p;
-  G.items = ctx->grid_items.p;
-  G.nx = nx; G.ny = ny; G.nz = nz;
-  G.n_items = (int32_t)total;
-  G.spheres = spheres ? 1 : 0;
-  G.in_lds = staged + 16 <= kGridLdsBudget ? 1 : 0;
-  G.lds_bytes = (uint32_t)((G.in_lds ? staged : fixed) + 16);
   return ODW_OK;
 }
 
-// the primitives' boxes and 64-byte headers (host only: ctx->h_prim_hdr, ctx->h_dead)
-void compute_boxes(odw_ctx* ctx, std::vector<Box>& boxes, std::vector<char>& dead) {
-  const int n = ctx->P.scene.n_prims;
-  // boxes contain every point the tolerance rules may accept
-  const double slack = 2.0 * (ctx->have_limits ? ctx->P.lim.dist_tol : 1e-2);
-  boxes.assign(n, Box());
-  std::vector<double>& flat = ctx->h_prim_hdr;
-  flat.assign((size_t)std::max(1, n) * 8, 0.0);   // 64-byte headers
-  for (int p = 0; p < n; ++p)
-    boxes[p] = world_box(ctx->h_prim_f64.data() + 16 * (size_t)p, ctx->h_prim_i32[4 * p], slack);
-  // A face that exists only inside other primitives (operands of a Common, the base of a Cut for
-  // its tool) lies in their boxes too: the box of a lens cap is the lens, not the sphere.
-  // Primitives without faces (pure operands) and faces that cannot exist get a box no ray meets.
-  std::vector<Box> full = boxes;
-  dead.assign(n, 0);
-  // A trimming list of several clauses bounds the face by the UNION over its clauses of (own box ^ that clause's
-  // must-be-inside operands): a literal of one clause alone does not bound it.  One clause: the cut as it always was.
-  for (int p = 0; p < n; ++p) {
-    const int cw = ctx->h_prim_i32[4 * p + 3], off = cw & 0xffffff, cnt = (cw >> 24) & 0xff;
-    const int end = std::min(off + cnt, (int)ctx->h_cond.size());
-    Box u;
-    u.reset();
-    int clauses = 0;
-    for (int c0 = off; c0 < end;) {
-      int c1 = c0 + 1;
-      while (c1 < end && !cond_opens(ctx->h_cond[c1])) ++c1;
-      Box b = full[p];
-      for (int c = c0; c < c1; ++c) {
-        if (ctx->h_cond[c] >= 0) continue;                     // must be OUTSIDE that one: no bound
-        const Box& o = full[cond_operand(ctx->h_cond[c])];
-        for (int a = 0; a < 3; ++a) {
-          b.lo[a] = std::max(b.lo[a], o.lo[a]);
-          b.hi[a] = std::min(b.hi[a], o.hi[a]);
-        }
-      }
-      if (clauses++ == 0) boxes[p] = b;                        // (an empty first clause stays empty unless another grows it)
-      if (b.lo[0] <= b.hi[0] && b.lo[1] <= b.hi[1] && b.lo[2] <= b.hi[2]) u.grow(b);
-      c0 = c1;
-    }
-    if (clauses > 1 && u.lo[0] <= u.hi[0]) boxes[p] = u;
-    const int facemask = (ctx->h_prim_i32[4 * p + 2] >> ODW_FACEMASK_SHIFT) & 0xff;
-    dead[p] = facemask == 0 || boxes[p].lo[0] > boxes[p].hi[0] || boxes[p].lo[1] > boxes[p].hi[1] ||
-              boxes[p].lo[2] > boxes[p].hi[2];
-    if (dead[p])
-      for (int a = 0; a < 3; ++a) boxes[p].lo[a] = boxes[p].hi[a] = 1e30;
-  }
-  // ODW_FLAG_ISOLATED (odw_device.h): solids whose box keeps clear of every other solid's
-  {
-    std::map<int, Box> solid_box;
-    for (int p = 0; p < n; ++p) {
-      ctx->h_prim_i32[4 * p + 2] &= ~ODW_FLAG_ISOLATED;
-      if (dead[p]) continue;
-      const int sid = ctx->h_prim_i32[4 * p + 2] >> ODW_SOLID_SHIFT;
-      auto it = solid_box.find(sid);
-      if (it == solid_box.end()) { solid_box[sid] = boxes[p]; continue; }
-      for (int a = 0; a < 3; ++a) {
-        it->second.lo[a] = std::min(it->second.lo[a], boxes[p].lo[a]);
-        it->second.hi[a] = std::max(it->second.hi[a], boxes[p].hi[a]);
-      }
-    }
-    const double gap = 2.0 * slack;                             // 4 distTol
-    if (solid_box.size() <= 64 && solid_box.count(0x7fff) == 0)  // (0x7fff: solid ids that did not fit the word)
-      for (int p = 0; p < n; ++p) {
-        if (dead[p]) continue;
-        const int sid = ctx->h_prim_i32[4 * p + 2] >> ODW_SOLID_SHIFT;
-        const Box& mine = solid_box[sid];
-        bool alone = true;
-        for (const auto& other : solid_box) {
-          if (other.first == sid) continue;
-          bool apart = false;
-          for (int a = 0; a < 3; ++a)
-            apart |= mine.lo[a] - other.second.hi[a] > gap || other.second.lo[a] - mine.hi[a] > gap;
-          if (!apart) { alone = false; break; }
-        }
-        if (alone) ctx->h_prim_i32[4 * p + 2] |= ODW_FLAG_ISOLATED;
-      }
-  }
-  for (int p = 0; p < n; ++p) {
-    double* h = flat.data() + 8 * (size_t)p;
-    for (int a = 0; a < 3; ++a) { h[a] = boxes[p].lo[a]; h[3 + a] = boxes[p].hi[a]; }
-    std::memcpy(h + 6, &ctx->h_prim_i32[4 * (size_t)p], 4 * sizeof(int32_t));
-  }
-  ctx->h_dead = dead;
-}
-
+// boxes, headers and structures of the uploaded scene for the limits in force (first launch, odw_compile_scene,
+// odw_upload_scene_batch)
 int build_bvh(odw_ctx* ctx) {
-  const int n = ctx->P.scene.n_prims;
-  ctx->P.scene.n_nodes = 0;
   ctx->bvh_dirty = false;
   ctx->spec_dirty = true;
   std::vector<Box> boxes;
-  std::vector<char> dead;
-  compute_boxes(ctx, boxes, dead);
-  const std::vector<double>& flat = ctx->h_prim_hdr;
-  {
-    int rc = upload(ctx, ctx->prim_hdr, flat.data(), flat.size() * sizeof(double));
-    // (compute_boxes has set ODW_FLAG_ISOLATED in the flag words)
-    if (!rc && n > 0) rc = upload(ctx, ctx->prim_i32, ctx->h_prim_i32.data(), ctx->h_prim_i32.size() * sizeof(int32_t));
-    if (rc) return rc;
-    if ((rc = upload_done(ctx))) return rc;
-    ctx->P.scene.prim_hdr = (const double*)ctx->prim_hdr.p;
-  }
-  const int bvh_threshold = ctx->flat_limit;
-  bool has_triangles = false, has_paraboloids = false;
-  for (int p = 0; p < n; ++p) {
-    has_triangles |= ctx->h_prim_i32[4 * p] == ODW_PRIM_TRIANGLE;
-    has_paraboloids |= ctx->h_prim_i32[4 * p] == ODW_PRIM_PARABOLOID;
-  }
-  std::memset(&ctx->P.grid, 0, sizeof ctx->P.grid);
-  ctx->P.scene.bvh_leaf = nullptr;
-  ctx->P.scene.bvh_wide = nullptr;
-  // (triangles are only known to the BVH kernels, paraboloids to the BVH and grid kernels)
-  if (n <= bvh_threshold && !has_triangles && !has_paraboloids) return ODW_OK;
-  if (!has_triangles) {
-    int rc = build_grid(ctx, boxes, dead);
-    if (rc) return rc;
-  }
-  // float32 traversal boxes: enlarge by what float rounding of the ray origin
-  // and of the slab arithmetic can cost (see ray_box_f32 in odw_kernels.hip)
-  for (int p = 0; p < n; ++p)
-    for (int a = 0; a < 3; ++a) {
-      const double s = 1e-4 + 4e-7 * (std::fabs(boxes[p].lo[a]) + std::fabs(boxes[p].hi[a]));
-      boxes[p].lo[a] -= s;
-      boxes[p].hi[a] += s;
-    }
-  BvhBuilder b(boxes);
-  std::vector<int> ids;
-  ids.reserve(n);
-  for (int i = 0; i < n; ++i)
-    if (!dead[i]) ids.push_back(i);
-  if (ids.empty() && n > 0) ids.push_back(0);   // (a far-away box: the tree needs one leaf)
-  b.nodes.reserve((size_t)n);
-  const BvhBuilder::Ref root = b.build(ids, 0);
-  if (root.count > 0) {   // everything in one leaf: wrap it into a root node
-    BvhNode nd;
-    for (int k = 0; k < 3; ++k) {
-      nd.lo0[k] = round_down(root.box.lo[k]); nd.hi0[k] = round_up(root.box.hi[k]);
-      // the second child does not exist.  Its box must be one no ray meets: an inverted box
-      // (lo = +inf, hi = -inf) passes the slab test for every ray (min = -inf, max = +inf on
-      // each axis) and would send the traversal back to node 0 for ever; a point far away fails
-      // it for every direction
-      nd.lo1[k] = 3.0e38f; nd.hi1[k] = 3.0e38f;
-    }
-    nd.child0 = root.child; nd.count0 = root.count;
-    nd.child1 = 0; nd.count1 = 0;
-    b.nodes.insert(b.nodes.begin(), nd);
-  }
-  if (b.max_depth + 2 > ODW_BVH_STACK) return fail(ctx, ODW_ERR_UNSUPPORTED, "BVH deeper than the LDS stack");
-  int rc;
-  if ((rc = upload(ctx, ctx->bvh_nodes, b.nodes.data(), b.nodes.size() * sizeof(BvhNode)))) return rc;
-  if ((rc = upload(ctx, ctx->bvh_prims, b.order.data(), b.order.size() * sizeof(int)))) return rc;
-  // the mesh kernel's eight-wide tree and leaf records (odw_mesh.hip: ODW_LEAF_WORDS): the facet relative to the centre
-  // of the leaf group of its node, in float32, with the bounds the conservative filter needs
-  ctx->P.scene.bvh_leaf = nullptr;
-  ctx->P.scene.bvh_wide = nullptr;
-  std::vector<float> recs;
-  // (read at every build: the test that holds the two kernels against each other)
-  const bool mesh_kernel = !(getenv("ODW_MESH_KERNEL") && getenv("ODW_MESH_KERNEL")[0] == '0');
-  std::vector<int> prim_solid((size_t)n);
-  for (int p = 0; p < n; ++p) prim_solid[p] = ctx->h_prim_i32[4 * (size_t)p + 2] >> ODW_SOLID_SHIFT;
-  WideBvh wide(b.nodes, b.order, prim_solid);
-  std::vector<float> out_normal;
-  if (has_triangles && mesh_kernel) {
-    // normal cones for rays inside STRICTLY convex tessellated solids (ODW_FLAG_STRICTLY_CONVEX; node words 24..31;
-    // ODW_MESH_CONES=0: none).  The margin: a ray that starts on a facet whose edges are all closed is out of that facet's
-    // area by 1e-9 of its edges at most; every point of a facet lies on or below the plane of every other facet up to
-    // rounding (what the flag says: 1e-13 of the mesh's size per edge, taken a hundred times wider here); the point itself
-    // is rounded (~1e-13 of the coordinates): above a dropped facet's plane by less than `above`, met at t < above / margin.
-    const bool cones_off = getenv("ODW_MESH_CONES") && getenv("ODW_MESH_CONES")[0] == '0';      // (read at every build, as ODW_MESH_KERNEL)
-    double size = 0.0, reach = 0.0;
-    out_normal.assign(3 * (size_t)n, std::numeric_limits<float>::quiet_NaN());
-    bool any = false;
-    for (int p = 0; p < n && !cones_off; ++p) {
-      const int32_t* pi = &ctx->h_prim_i32[4 * (size_t)p];
-      if (pi[0] != ODW_PRIM_TRIANGLE || !(pi[2] & ODW_FLAG_CONVEX) || !(pi[2] & ODW_FLAG_STRICTLY_CONVEX)) continue;
-      const double* pf = ctx->h_prim_f64.data() + 16 * (size_t)p;
-      const double sg = (pi[2] & ODW_FLAG_FLIP_NORMAL) ? -1.0 : 1.0;
-      for (int a = 0; a < 3; ++a) {
-        out_normal[3 * (size_t)p + a] = (float)(sg * pf[9 + a]);
-        size = std::max(size, std::fabs(pf[3 + a]) + std::fabs(pf[6 + a]));
-        reach = std::max(reach, std::max(std::fabs(boxes[p].lo[a]), std::fabs(boxes[p].hi[a])));
-      }
-      any = true;
-    }
-    if (any) {
-      // (size: the longest facet edge, and more; the mesh is at most the extent of all such facets together: reach both ways)
-      const double above = 1e-9 * size + 1e-11 * 2.0 * reach + 1e-12 * reach;
-      wide.margin = std::max(0.02, 2.0 * above / std::max(ctx->P.lim.dist_tol, 1e-300));
-      wide.out_normal = out_normal.data();
-    }
-    wide.build();
-    if (wide.ok) {
-      recs.assign(std::max<size_t>(wide.leaf_prim.size(), 1) * ODW_LEAF_WORDS, 0.0f);
-      for (size_t j = 0; j < wide.leaf_prim.size(); ++j) {
-        const int p = wide.leaf_prim[j];
-        float* r = &recs[j * ODW_LEAF_WORDS];
-        const float* c = &wide.leaf_center[3 * j];
-        const double* pf = ctx->h_prim_f64.data() + 16 * (size_t)p;
-        const int32_t* pi = &ctx->h_prim_i32[4 * (size_t)p];
-        uint32_t gs = (uint32_t)(pi[1] & 0xff) | ((uint32_t)((pi[2] >> ODW_SOLID_SHIFT) & 0x7fff) << 8);
-        float smax = 0.0f, err = 0.0f;
-        if (pi[0] == ODW_PRIM_TRIANGLE) {
-          double l1[2] = {0.0, 0.0};
-          float e1[3], e2[3];
-          for (int a = 0; a < 3; ++a) {
-            r[a] = (float)(pf[a] - (double)c[a]);
-            e1[a] = (float)pf[3 + a];
-            e2[a] = (float)pf[6 + a];
-            l1[0] += std::fabs(pf[3 + a]);
-            l1[1] += std::fabs(pf[6 + a]);
-          }
-          r[3] = e1[0]; r[4] = e1[1]; r[5] = e1[2]; r[6] = e2[0]; r[7] = e2[1]; r[8] = e2[2];
-          smax = round_up(std::max(0.0, std::max(pf[12], std::max(pf[13], pf[14]))));
-          err = round_up(4e-6 * std::max(l1[0], l1[1]));
-        } else {
-          gs |= 0x80000000u;
-        }
-        std::memcpy(&r[9], &gs, 4);
-        r[10] = smax;
-        r[11] = err;
-        std::memcpy(&r[12], &p, 4);
-        r[13] = c[0]; r[14] = c[1]; r[15] = c[2];
-      }
-      if (getenv("ODW_MESH_CONE_STATS")) {             // (diagnostics: how many slots carry a cone)
-        size_t slots = 0, cones = 0;
-        for (size_t k = 0; k + kWideWords <= wide.nodes.size(); k += kWideWords)
-          for (int sl = 0; sl < 8; ++sl)
-            if ((wide.nodes[k + 6] | (wide.nodes[k + 6] >> 8)) & (1u << sl)) { ++slots; cones += (wide.nodes[k + 24 + sl] >> 24) != 127u; }
-        fprintf(stderr, "[odw mesh cones] margin %.4g, %zu of %zu slots carry a cone\n", wide.margin, cones, slots);
-      }
-      if ((rc = upload(ctx, ctx->bvh_leaf, recs.data(), recs.size() * sizeof(float)))) return rc;
-      if ((rc = upload(ctx, ctx->bvh_wide, wide.nodes.data(), wide.nodes.size() * sizeof(uint32_t)))) return rc;
-      for (int a = 0; a < 3; ++a) {       // node 0 as the kernel decodes it: corner + 255 units of its scale
-        float corner, unit;
-        const uint32_t eb = ((wide.nodes[3] >> (8 * a)) & 0xffu) << 23;
-        std::memcpy(&corner, &wide.nodes[a], 4);
-        std::memcpy(&unit, &eb, 4);
-        ctx->P.scene.wide_lo[a] = (double)corner;
-        ctx->P.scene.wide_hi[a] = (double)corner + 255.0 * (double)unit;
-      }
-    }
-  }
-  { int rc_ = upload_done(ctx); if (rc_) return rc_; }  // host vectors die with this scope
-  ctx->P.scene.bvh_nodes = (const float*)ctx->bvh_nodes.p;
-  ctx->P.scene.bvh_prims = (const int32_t*)ctx->bvh_prims.p;
-  ctx->P.scene.bvh_leaf = recs.empty() ? nullptr : (const float*)ctx->bvh_leaf.p;
-  ctx->P.scene.bvh_wide = recs.empty() ? nullptr : (const uint32_t*)ctx->bvh_wide.p;
-  ctx->P.scene.n_nodes = (int)b.nodes.size();
-  return ODW_OK;
+  compute_boxes(ctx->hs, ctx->P.lim.dist_tol, boxes);
+  SceneAccel A;
+  std::string err;
+  // (a tree the kernels' stack cannot hold leaves A empty: the headers still go up, so that what the context holds is a
+  //  consistent scene without structures, and the launch answers with the builder's error)
+  const int rc_build = build_accel(ctx->hs, std::move(boxes), ctx->P.lim.dist_tol, ctx->flat_limit, build_options(), A, err);
+  const int rc = upload_accel(ctx, A);
+  return rc_build ? fail(ctx, rc_build, err) : rc;
 }
+
 
 // ---- device-side ordering of the hit list (odw_fetch_hits) -----------------
 __global__ void hit_keys_kernel(const odw_hit* __restrict__ hits, uint64_t n, uint64_t sentinel, uint64_t* __restrict__ keys,
@@ -1314,6 +444,23 @@ int presort_rays(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed) {
 }
 
 
+// ---- which kernel a launch takes ---------------------------------------------------------------
+// What the scene's structures alone say is accel_kind() (odw_build.h; odw_build_check answers with it), and every kind
+// has its kernel.  What a launch makes of it: a scene compiled against its structure (odw_spec.hip) takes its own kernel,
+// whatever else was built for it -- the variant this launch needs must be bound, for the scene as it is now.  Segment
+// rows are written by the flat and tree kernels only; stochastic surfaces are unknown to the grid kernel: such
+// launches fall back to the trees, which every scene with a grid has too.  (Batches hold scenes without structures:
+// compiled or flat.)
+enum class TraceKernel { flat = kAccelFlat, grid = kAccelGrid, tree = kAccelTree, mesh = kAccelWide, compiled };
+
+TraceKernel choose_kernel(const odw_ctx* ctx, uint32_t flags, bool batch) {
+  const DeviceScene& S = ctx->P.scene;
+  const bool segments = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0, stoch = ctx->n_samplers > 0;
+  const hipFunction_t fn = batch ? ctx->spec_batch_fn : (flags & ODW_TRACE_POWER_HISTOGRAM) ? ctx->spec_power_fn : ctx->spec_fn;
+  if (fn && ctx->spec_lean == ctx->hs.lean && ctx->spec_stoch == stoch && !segments) return TraceKernel::compiled;
+  return (TraceKernel)accel_kind(ctx->P.grid.nx > 0 && !stoch && !segments, S.n_nodes != 0, S.bvh_leaf != nullptr && !segments);
+}
+
 int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32_t flags,
                  const double* ray_o, const double* ray_d, const double* ray_p) {
   const bool explicit_rays = ray_o != nullptr;
@@ -1386,8 +533,6 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // per CU at 4 waves/SIMD, x2 so that a CU never waits for a block launch);
   // chunks of ODW_CHUNK rays are handed out dynamically inside the kernel
   constexpr int grid_mult = 8;
-  // big analytic scenes: grid kernel (no stochastic surfaces, no segment rows: those stay with the BVH kernels)
-  // a scene compiled against its structure (odw_spec.hip): its own kernel, whatever else was built for it
   const bool pw = (flags & ODW_TRACE_POWER_HISTOGRAM) != 0;     // the <..., POWER = true> instantiation of whichever kernel runs
   if (pw && ctx->spec_fn && !ctx->spec_power_fn && !ctx->spec_power_failed &&
       !(ctx->spec_power_wait && !ctx->spec_power_wait->load())) {
@@ -1418,16 +563,16 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       ctx->err = keep_err;
     }
   }
-  const bool use_spec = (batch ? ctx->spec_batch_fn != nullptr : pw ? ctx->spec_power_fn != nullptr : ctx->spec_fn != nullptr) && ctx->spec_lean == ctx->lean &&
-                        ctx->spec_stoch == (ctx->n_samplers > 0) && !(flags & ODW_TRACE_RECORD_SEGMENTS);
-  const bool use_grid = !use_spec && P.grid.nx > 0 && ctx->n_samplers == 0 && !(flags & ODW_TRACE_RECORD_SEGMENTS);
+  const TraceKernel kernel = choose_kernel(ctx, flags, batch);   // (after the two bindings above: they decide `compiled`)
+  const bool use_spec = kernel == TraceKernel::compiled, use_grid = kernel == TraceKernel::grid, use_mesh = kernel == TraceKernel::mesh,
+             use_tree = kernel == TraceKernel::tree;
   // Rays per hand-out unit.  A launch should hold many chunks per resident wave: with about one each -- 1e7 rays in
   // chunks of 2048 on 4096 resident waves -- the waves that get a second one set the launch's length.  Measured
   // (kernel ms at 1e7 / 1e8 rays): flat kernels 2048: 1.46 / 11.07, 1024: 1.44 / 10.93, 512: 1.39 / 10.97, 256: 1.43;
   // the ring kernels (grid, mesh: a ring fill is 64 rays whatever the chunk) 2048: 2.24 / 21.34, 512: 2.05 / 20.95,
   // 256: 1.96 / 20.86, and the mesh kernel at 1e7 rays and 6.5e4 facets 2048: 14.6, 256: 12.5, 64: 12.3.
   {
-    const bool ring = use_grid || (!use_spec && P.scene.n_nodes && P.scene.bvh_leaf && !(flags & ODW_TRACE_RECORD_SEGMENTS));
+    const bool ring = use_grid || use_mesh;
     const uint64_t waves = (uint64_t)ctx->n_cu * 16;
     const uint64_t want = ring ? std::max<uint64_t>(64, std::min<uint64_t>(256, n / (waves * 32)))
                                : std::max<uint64_t>(512, std::min<uint64_t>(1024, n / (waves * 4)));
@@ -1473,15 +618,13 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   const uint64_t cap = (uint64_t)ctx->n_cu * (batch ? batch_mult : grid_mult);
   const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n_chunks + 3) / 4, cap));
   const uint64_t grid_blocks = std::max<uint64_t>(1, std::min<uint64_t>((n_chunks + ODW_GRID_WAVES - 1) / ODW_GRID_WAVES, (uint64_t)ctx->n_cu));
-  // scenes with facets: the mesh kernel (same exclusions)
-  const bool use_mesh = !use_spec && !use_grid && P.scene.n_nodes && P.scene.bvh_leaf && !(flags & ODW_TRACE_RECORD_SEGMENTS);
   const uint64_t n_waves = use_grid ? grid_blocks * ODW_GRID_WAVES : (uint64_t)grid * 4;
-  if ((!P.scene.n_nodes || use_grid || use_spec || use_mesh) && !ctx->swapping)   // flat, grid and mesh kernels only (see record_hit)
+  if (!use_tree && !ctx->swapping)   // compiled, flat, grid and mesh kernels only (see record_hit)
     for (uint32_t b = kHitBlock; b >= 128 && b >= kHitBlock / 4 && !P.out.hit_block; b /= 2)   // (a short list: smaller blocks before none)
       if (batch ? ctx->batch_seg_slots >= ctx->batch_seg_capacity + hit_block_room(ctx->batch_seg_capacity, n_waves, b)
                 : ctx->hit_slots >= ctx->hit_capacity + hit_block_room(ctx->hit_capacity, n_waves, b)) P.out.hit_block = b;
   HIPCHK(ctx, hipMemsetAsync(ctx->chunk_counter.p, 0, sizeof(uint64_t), ctx->stream));
-  const size_t lds = P.scene.n_nodes ? (size_t)ODW_BVH_STACK * 256 * sizeof(int) : 0;
+  const size_t lds = use_tree ? (size_t)ODW_BVH_STACK * 256 * sizeof(int) : 0;
 
   std::pair<hipEvent_t, hipEvent_t> ev{nullptr, nullptr};
   if (ctx->timing) {
@@ -1509,7 +652,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     int rc = spec_launch(ctx, grid, batch ? ctx->spec_batch_fn : pw ? ctx->spec_power_fn : ctx->spec_fn);
     if (rc) return rc;
   } else if (batch) {
-    if (ctx->lean) hipLaunchKernelGGL((odw_trace_kernel<false, false, false, true, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
+    if (ctx->hs.lean) hipLaunchKernelGGL((odw_trace_kernel<false, false, false, true, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
     else hipLaunchKernelGGL((odw_trace_kernel<false, false, false, false, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
   } else if (use_grid) {
     const dim3 gb((unsigned)grid_blocks);
@@ -1544,19 +687,19 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     else { if (pw) hipLaunchKernelGGL((odw_mesh_kernel<false, true>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
            else hipLaunchKernelGGL((odw_mesh_kernel<false, false>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P); }
   } else if (flags & ODW_TRACE_RECORD_SEGMENTS) {
-    if (P.scene.n_nodes) {
+    if (use_tree) {
       if (stoch) ODW_TRACE_LAUNCH(lds, true, true, true, false);
       else ODW_TRACE_LAUNCH(lds, true, false, true, false);
     } else {
       if (stoch) ODW_TRACE_LAUNCH(0, false, true, true, false);
       else ODW_TRACE_LAUNCH(0, false, false, true, false);
     }
-  } else if (P.scene.n_nodes) {
+  } else if (use_tree) {
     if (stoch) ODW_TRACE_LAUNCH(lds, true, true, false, false);
     else ODW_TRACE_LAUNCH(lds, true, false, false, false);
   } else {
     if (stoch) ODW_TRACE_LAUNCH(0, false, true, false, false);
-    else if (ctx->lean) ODW_TRACE_LAUNCH(0, false, false, false, true);
+    else if (ctx->hs.lean) ODW_TRACE_LAUNCH(0, false, false, false, true);
     else ODW_TRACE_LAUNCH(0, false, false, false, false);
   }
 #undef ODW_TRACE_LAUNCH
@@ -1734,151 +877,22 @@ void odw_destroy(odw_ctx* ctx) {
   delete ctx;
 }
 
-// a condition as the kernels read it (odw_device.h: cond_operand, cond_opens, the sign = must be inside)
-static int32_t pack_cond(int32_t prim, int32_t inside) {
-  return (int32_t)((uint32_t)prim | ((uint32_t)(inside >> 1) & 1u) << 30 | ((uint32_t)inside & 1u) << 31);
-}
-
-// every list that opens a clause after its first word opens one with its first word too (offsets already checked)
-static bool clauses_marked(const int32_t* cond_off, int n, const std::vector<int32_t>& cond) {
-  for (int p = 0; p < n; ++p) {
-    const int off = cond_off[p], end = cond_off[p + 1];
-    if (end <= off || cond_opens(cond[off])) continue;
-    for (int c = off + 1; c < end; ++c)
-      if (cond_opens(cond[c])) return false;
-  }
-  return true;
-}
-
-// host half of odw_upload_scene: validation and the host copies of every table (no device call)
-static int scene_host_tables(odw_ctx* ctx, const odw_scene_desc* s) {
-  if (!ctx || !s) return fail(ctx, ODW_ERR_INVALID, "odw_upload_scene: null argument");
-  if (s->n_prims < 0 || s->n_groups < 0 || s->n_groups > ODW_MAX_GROUPS || s->seq_len < 0 ||
-      s->seq_len > ODW_MAX_SEQUENCE || s->n_conds < 0 || s->n_conds >= (1 << 24))
-    return fail(ctx, ODW_ERR_INVALID, "odw_upload_scene: counts out of range");
-  if ((s->n_prims > 0 && (!s->prim_type || !s->prim_group || !s->prim_flags || !s->prim_xform || !s->prim_params ||
-                          !s->prim_cond_off)) ||
-      (s->n_conds > 0 && (!s->cond_prim || !s->cond_inside)) ||
-      (s->n_groups > 0 && (!s->group_type || !s->group_ior || !s->group_refl || !s->group_abslen || !s->group_record)) ||
-      (s->seq_len > 0 && !s->seq_mask))
-    return fail(ctx, ODW_ERR_INVALID, "odw_upload_scene: null table pointer");
-  const int n = s->n_prims;
-  int max_solid = 0;
-  for (int p = 0; p < n && s->prim_solid; ++p) max_solid = std::max(max_solid, s->prim_solid[p]);
-  ctx->h_prim_f64.assign((size_t)n * 16, 0.0);
-  ctx->h_prim_i32.assign((size_t)n * 4, 0);
-  for (int p = 0; p < n; ++p) {
-    const int type = s->prim_type[p], group = s->prim_group[p];
-    if (type < ODW_PRIM_BOX || type > ODW_PRIM_PARABOLOID) return fail(ctx, ODW_ERR_UNSUPPORTED, "unknown primitive type");
-    if (group < 0 || group >= s->n_groups) return fail(ctx, ODW_ERR_INVALID, "primitive group out of range");
-    const int off = s->prim_cond_off[p], cnt = s->prim_cond_off[p + 1] - off;
-    if (off < 0 || cnt < 0 || cnt > 255 || off + cnt > s->n_conds)
-      return fail(ctx, ODW_ERR_INVALID, "bad condition offsets");
-    if (type == ODW_PRIM_TRIANGLE) {
-      if (cnt) return fail(ctx, ODW_ERR_UNSUPPORTED, "triangles cannot carry trimming conditions");
-      const double* v = s->prim_xform + 12 * (size_t)p;
-      double* d = &ctx->h_prim_f64[16 * (size_t)p];
-      double e1[3], e2[3], e3[3], nn[3];
-      for (int k = 0; k < 3; ++k) { d[k] = v[k]; e1[k] = v[3 + k] - v[k]; e2[k] = v[6 + k] - v[k]; e3[k] = e2[k] - e1[k]; }
-      nn[0] = e1[1] * e2[2] - e1[2] * e2[1];
-      nn[1] = e1[2] * e2[0] - e1[0] * e2[2];
-      nn[2] = e1[0] * e2[1] - e1[1] * e2[0];
-      const double a2 = std::sqrt(nn[0] * nn[0] + nn[1] * nn[1] + nn[2] * nn[2]);   // twice the area
-      if (!(a2 > 0) || !std::isfinite(a2)) return fail(ctx, ODW_ERR_INVALID, "degenerate triangle");
-      auto len3 = [](const double* x) { return std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]); };
-      for (int k = 0; k < 3; ++k) { d[3 + k] = e1[k]; d[6 + k] = e2[k]; d[9 + k] = nn[k] / a2; }
-      // a point at distance tol outside an edge has barycentric coordinate -tol/altitude
-      d[12] = len3(e2) / a2;   // u: distance from edge (v0, v2)
-      d[13] = len3(e1) / a2;   // v: distance from edge (v0, v1)
-      d[14] = len3(e3) / a2;   // u+v: distance from edge (v1, v2)
-      // edges shared with a neighbouring facet of the same face are not widened (sign = marker)
-      const int face_edges = s->tri_edges ? s->tri_edges[p] : 7;
-      for (int k = 0; k < 3; ++k)
-        if (!((face_edges >> k) & 1)) d[12 + k] = -d[12 + k];
-      d[15] = 0.0;
-    } else {
-      std::memcpy(&ctx->h_prim_f64[16 * (size_t)p], s->prim_xform + 12 * (size_t)p, 12 * sizeof(double));
-      std::memcpy(&ctx->h_prim_f64[16 * (size_t)p + 12], s->prim_params + 4 * (size_t)p, 4 * sizeof(double));
-      if (type == ODW_PRIM_SPHERE) {
-        // the kernel intersects spheres without their frame: centre in global coordinates = -R^T t
-        const double* m = &ctx->h_prim_f64[16 * (size_t)p];
-        for (int k = 0; k < 3; ++k)
-          ctx->h_prim_f64[16 * (size_t)p + 13 + k] = -(m[k] * m[3] + m[4 + k] * m[7] + m[8 + k] * m[11]);
-      }
-      if (type == ODW_PRIM_PARABOLOID) {
-        double* par = &ctx->h_prim_f64[16 * (size_t)p + 12];
-        if (!(par[0] > 0) || !(par[1] > 0)) return fail(ctx, ODW_ERR_INVALID, "paraboloid: focal length and height must be positive");
-        par[2] = 2.0 * std::sqrt(par[0] * par[1]);            // rim radius at z = H
-      }
-    }
-    ctx->h_prim_i32[4 * p] = type;
-    ctx->h_prim_i32[4 * p + 1] = group;
-    // flags | facemask << 8 in the low half, solid id above; scenes with more solids than fit lose the
-    // convex-solid shortcut, nothing else
-    const int solid = s->prim_solid ? s->prim_solid[p] : 0;
-    const bool fits = s->prim_solid && solid >= 0 && solid < 0x7fff && max_solid < 0x7fff;
-    ctx->h_prim_i32[4 * p + 2] = ((s->prim_flags[p] & 0xffff & ~ODW_FLAG_ISOLATED) & (fits ? ~0 : ~ODW_FLAG_CONVEX)) | ((fits ? solid : 0x7fff) << ODW_SOLID_SHIFT);
-    ctx->h_prim_i32[4 * p + 3] = off | (cnt << 24);
-  }
-  std::vector<int32_t> cond((size_t)std::max(1, s->n_conds), 0);
-  for (int c = 0; c < s->n_conds; ++c) {
-    if (s->cond_prim[c] < 0 || s->cond_prim[c] >= n || s->cond_prim[c] >= (1 << 30))
-      return fail(ctx, ODW_ERR_INVALID, "condition primitive out of range");
-    if (s->prim_type[s->cond_prim[c]] == ODW_PRIM_TRIANGLE)
-      return fail(ctx, ODW_ERR_UNSUPPORTED, "trimming against a triangle (no inside/outside of a facet)");
-    if (s->cond_inside[c] < 0 || s->cond_inside[c] > 3)
-      return fail(ctx, ODW_ERR_INVALID, "cond_inside: bit 0 inside, bit 1 opens a clause; nothing else");
-    cond[c] = pack_cond(s->cond_prim[c], s->cond_inside[c]);
-  }
-  if (!clauses_marked(s->prim_cond_off, n, cond))
-    return fail(ctx, ODW_ERR_INVALID, "a trimming list of several clauses must mark its first condition too");
-  ctx->h_cond = cond;
-  std::vector<double> gf(ODW_MAX_GROUPS * 4, 0.0), gd(ODW_MAX_GROUPS * 3, 0.0);
-  std::vector<int32_t> gi(ODW_MAX_GROUPS * 4, 0);
-  ctx->lean = true;
-  for (int g = 0; g < s->n_groups; ++g)
-    if (s->group_type[g] == ODW_OPT_GRATING || !(s->group_abslen[g] == INFINITY)) ctx->lean = false;
-  for (int g = 0; g < s->n_groups; ++g) {
-    if (s->group_type[g] < ODW_OPT_MIRROR || s->group_type[g] > ODW_OPT_VACUUM)
-      return fail(ctx, ODW_ERR_INVALID, "unknown optical type");
-    gf[4 * g] = s->group_ior[g];
-    gf[4 * g + 1] = s->group_refl[g];
-    gf[4 * g + 2] = s->group_abslen[g];
-    gf[4 * g + 3] = s->group_grating_lpm ? s->group_grating_lpm[g] : 1000.0;
-    gi[4 * g] = s->group_type[g];
-    gi[4 * g + 1] = s->group_record[g] ? 1 : 0;
-    gi[4 * g + 2] = s->group_grating_type ? s->group_grating_type[g] : 0;
-    gi[4 * g + 3] = s->group_grating_order ? s->group_grating_order[g] : 1;
-    for (int k = 0; k < 3; ++k) gd[3 * g + k] = s->group_grating_dir ? s->group_grating_dir[3 * g + k] : (k == 2);
-  }
-  std::vector<uint64_t> seq((size_t)std::max(1, s->seq_len), 0);
-  for (int i = 0; i < s->seq_len; ++i) seq[i] = s->seq_mask[i];
-  ctx->h_group_f64 = gf;
-  ctx->h_group_i32 = gi;
-  ctx->h_group_gdir = gd;
-  ctx->h_seq = seq;
-  DeviceScene& d = ctx->P.scene;
-  d.n_prims = n;
-  d.n_groups = s->n_groups;
-  d.n_nodes = 0;
-  d.seq_enabled = s->seq_enabled ? 1 : 0;
-  d.seq_len = s->seq_len;
-  d.all_mask = (s->n_groups >= 64) ? ~0ull : ((1ull << s->n_groups) - 1ull);
-  d.ignore_mask = s->ignore_mask;
-  return ODW_OK;
-}
 
 int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* s) {
-  int rc = scene_host_tables(ctx, s);
-  if (rc) return rc;
+  if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_upload_scene: null argument");
+  HostScene hs;
+  std::string err;
+  int rc = scene_host_tables(s, hs, err);
+  if (rc) return fail(ctx, rc, err);     // (a refused descriptor leaves the uploaded scene as it was)
+  ctx->hs = std::move(hs);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int n = s->n_prims;
-  const std::vector<int32_t>& cond = ctx->h_cond;
-  const std::vector<double>&gf = ctx->h_group_f64, &gd = ctx->h_group_gdir;
-  const std::vector<int32_t>& gi = ctx->h_group_i32;
-  const std::vector<uint64_t>& seq = ctx->h_seq;
-  if ((rc = upload(ctx, ctx->prim_f64, ctx->h_prim_f64.data(), ctx->h_prim_f64.size() * sizeof(double)))) return rc;
-  if ((rc = upload(ctx, ctx->prim_i32, ctx->h_prim_i32.data(), ctx->h_prim_i32.size() * sizeof(int32_t)))) return rc;
+  const std::vector<int32_t>& cond = ctx->hs.cond;
+  const std::vector<double>&gf = ctx->hs.group_f64, &gd = ctx->hs.group_gdir;
+  const std::vector<int32_t>& gi = ctx->hs.group_i32;
+  const std::vector<uint64_t>& seq = ctx->hs.seq;
+  if ((rc = upload(ctx, ctx->prim_f64, ctx->hs.prim_f64.data(), ctx->hs.prim_f64.size() * sizeof(double)))) return rc;
+  if ((rc = upload(ctx, ctx->prim_i32, ctx->hs.prim_i32.data(), ctx->hs.prim_i32.size() * sizeof(int32_t)))) return rc;
   if ((rc = upload(ctx, ctx->cond_i32, cond.data(), cond.size() * sizeof(int32_t)))) return rc;
   if ((rc = upload(ctx, ctx->group_f64, gf.data(), gf.size() * sizeof(double)))) return rc;
   if ((rc = upload(ctx, ctx->group_i32, gi.data(), gi.size() * sizeof(int32_t)))) return rc;
@@ -1889,6 +903,13 @@ int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* s) {
   }
   if ((rc = upload_done(ctx))) return rc;
   DeviceScene& d = ctx->P.scene;
+  d.n_prims = ctx->hs.n_prims;
+  d.n_groups = ctx->hs.n_groups;
+  d.n_nodes = 0;
+  d.seq_enabled = ctx->hs.seq_enabled;
+  d.seq_len = ctx->hs.seq_len;
+  d.all_mask = ctx->hs.all_mask;
+  d.ignore_mask = ctx->hs.ignore_mask;
   d.tri_nrm = (s->tri_normals && n > 0) ? (const double*)ctx->tri_nrm.p : nullptr;
   d.prim_f64 = (const double*)ctx->prim_f64.p;
   d.prim_i32 = (const int32_t*)ctx->prim_i32.p;
@@ -1938,18 +959,15 @@ int odw_compile_check(const odw_scene_desc* scene, const odw_limits* limits, int
                       char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
   if (!scene || !limits || mode != ODW_COMPILE_STRUCTURE)
     return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check: bad argument");
-  odw_ctx tmp;                     // host tables only: no device, no stream
-  std::memset(&tmp.P, 0, sizeof tmp.P);
-  int rc = scene_host_tables(&tmp, scene);
-  if (rc) return rc;
-  tmp.P.lim.dist_tol = limits->dist_tol;
-  tmp.have_limits = true;
+  HostScene tmp;
+  std::string refusal;
+  int rc = scene_host_tables(scene, tmp, refusal);
+  if (rc) return fail(nullptr, rc, refusal);
   std::vector<Box> boxes;
-  std::vector<char> dead;
-  compute_boxes(&tmp, boxes, dead);
-  const std::string why = spec_ineligible(&tmp);
+  compute_boxes(tmp, limits->dist_tol, boxes);
+  const std::string why = spec_ineligible(tmp);
   if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_compile_check: " + why);
-  const std::string text = spec_text(&tmp);
+  const std::string text = spec_text(tmp, 0);
   if (header_out && header_capacity) {
     const size_t k = std::min<size_t>(text.size(), (size_t)header_capacity - 1);
     std::memcpy(header_out, text.data(), k);
@@ -1963,50 +981,41 @@ int odw_compile_check(const odw_scene_desc* scene, const odw_limits* limits, int
   return ODW_OK;
 }
 
-// The host half of odw_upload_scene + the first launch's preparations -- validation, host tables, bounding boxes, the
-// choice among the flat loop, the rectilinear grid, the binary tree and the eight-wide tree with its leaf records, and
-// their construction -- on a context WITHOUT a device: every table the builders would upload goes to host memory instead.
-// For tests of these 1 500 lines under a CPU sanitizer (tests/test_native_sanitized.py) and for callers that want to know
-// what a scene will be traced with before a GPU is there.  structure: 0 flat loop, 1 grid, 2 binary tree, 3 eight-wide
-// tree (facets); sizes: [primitives, tree nodes, grid cells, grid items, bytes of dynamic LDS of a grid block, dead primitives].
+// What a scene will be traced with, and how large its structures are, without a device: descriptor -> HostScene
+// (validation, host tables) -> boxes -> SceneAccel, the very functions (odw_build.h) a context runs at its first launch,
+// minus the upload.  For callers that want the answer before a GPU is there; the builders themselves run under a CPU
+// sanitizer in tests/native/build_tables_main.hip, this entry with the library in tests/test_native_sanitized.py.
+// structure: 0 flat loop, 1 grid, 2 binary tree, 3 eight-wide tree (facets) -- the kernel a plain launch takes
+// (accel_kind); sizes: [primitives, tree nodes, grid cells, grid items, bytes of dynamic LDS of a grid block,
+// dead primitives].
 int odw_build_check(const odw_scene_desc* scene, const odw_limits* limits, int32_t* structure, uint64_t* sizes) {
   if (!scene || !limits) return fail(nullptr, ODW_ERR_INVALID, "odw_build_check: null argument");
   if (!(limits->dist_tol > 0) || limits->max_intersections < 0 || !(limits->max_ray_length > 0))
     return fail(nullptr, ODW_ERR_INVALID, "odw_build_check: limits out of range");
-  odw_ctx tmp;
-  std::memset(&tmp.P, 0, sizeof tmp.P);
-  tmp.host_only = true;
-  if (const char* e = getenv("ODW_BVH_THRESHOLD")) tmp.flat_limit = atoi(e);
-  int rc = scene_host_tables(&tmp, scene);
+  int flat_limit = kBvhThreshold;
+  if (const char* e = getenv("ODW_BVH_THRESHOLD")) flat_limit = atoi(e);
+  HostScene tmp;
+  SceneAccel A;
+  std::string err;
+  int rc = scene_host_tables(scene, tmp, err);
   if (!rc) {
-    tmp.P.lim.max_ray_length = limits->max_ray_length;
-    tmp.P.lim.max_intersections = limits->max_intersections;
-    tmp.P.lim.dist_tol = limits->dist_tol;
-    tmp.P.lim.power_tol = limits->power_tol;
-    tmp.have_limits = tmp.have_scene = true;
-    if (scene->tri_normals && scene->n_prims > 0)
-      rc = upload(&tmp, tmp.tri_nrm, scene->tri_normals, (size_t)scene->n_prims * 9 * sizeof(double));
-    if (!rc) rc = build_bvh(&tmp);
+    std::vector<Box> boxes;
+    compute_boxes(tmp, limits->dist_tol, boxes);
+    rc = build_accel(tmp, std::move(boxes), limits->dist_tol, flat_limit, build_options(), A, err);
   }
-  if (!rc) {
-    if (structure) *structure = tmp.P.grid.nx > 0 ? 1 : (tmp.P.scene.n_nodes ? (tmp.P.scene.bvh_leaf ? 3 : 2) : 0);
-    if (sizes) {
-      uint64_t dead = 0;
-      for (char d : tmp.h_dead) dead += d ? 1 : 0;
-      sizes[0] = (uint64_t)tmp.P.scene.n_prims;
-      sizes[1] = (uint64_t)tmp.P.scene.n_nodes;
-      sizes[2] = (uint64_t)tmp.P.grid.nx * (uint64_t)tmp.P.grid.ny * (uint64_t)tmp.P.grid.nz;
-      sizes[3] = (uint64_t)tmp.P.grid.n_items;
-      sizes[4] = (uint64_t)tmp.P.grid.lds_bytes;
-      sizes[5] = dead;
-    }
-  } else {
-    g_error = tmp.err;
+  if (rc) return fail(nullptr, rc, err);
+  if (structure) *structure = A.kind();
+  if (sizes) {
+    uint64_t dead = 0;
+    for (char d : tmp.dead) dead += d ? 1 : 0;
+    sizes[0] = (uint64_t)tmp.n_prims;
+    sizes[1] = (uint64_t)A.nodes.size();
+    sizes[2] = (uint64_t)A.grid.nx * (uint64_t)A.grid.ny * (uint64_t)A.grid.nz;
+    sizes[3] = (uint64_t)A.grid.n_items;
+    sizes[4] = (uint64_t)A.grid.lds_bytes;
+    sizes[5] = dead;
   }
-  for (DevBuf* b : {&tmp.prim_f64, &tmp.prim_hdr, &tmp.prim_i32, &tmp.cond_i32, &tmp.group_f64, &tmp.group_i32, &tmp.group_gdir, &tmp.seq_mask,
-                    &tmp.bvh_nodes, &tmp.bvh_prims, &tmp.bvh_leaf, &tmp.bvh_wide, &tmp.tri_nrm, &tmp.grid_bounds, &tmp.grid_cells, &tmp.grid_items})
-    release(*b);
-  return rc;
+  return ODW_OK;
 }
 
 int odw_upload_surface_samplers(odw_ctx* ctx, const odw_surface_sampler_desc* samplers, int32_t n) {
@@ -2441,16 +1450,15 @@ void batch_unselect(odw_ctx* ctx) {
 }
 
 // the part of a scene's host tables that is STRUCTURE (what scenes of a batch must share)
-bool same_structure(const odw_ctx& a, const odw_ctx& b, std::string& why) {
-  if (a.P.scene.n_prims != b.P.scene.n_prims || a.P.scene.n_groups != b.P.scene.n_groups) { why = "primitive or group count"; return false; }
-  for (size_t i = 0; i < a.h_prim_i32.size(); ++i) {
+bool same_structure(const HostScene& a, const HostScene& b, std::string& why) {
+  if (a.n_prims != b.n_prims || a.n_groups != b.n_groups) { why = "primitive or group count"; return false; }
+  for (size_t i = 0; i < a.prim_i32.size(); ++i) {
     const int32_t mask = (i % 4 == 2) ? ~(int32_t)ODW_FLAG_ISOLATED : ~0;       // (a matter of the boxes' values)
-    if ((a.h_prim_i32[i] & mask) != (b.h_prim_i32[i] & mask)) { why = "primitive kinds, groups, flags or trimming lists"; return false; }
+    if ((a.prim_i32[i] & mask) != (b.prim_i32[i] & mask)) { why = "primitive kinds, groups, flags or trimming lists"; return false; }
   }
-  if (a.h_cond != b.h_cond) { why = "trimming conditions"; return false; }
-  if (a.h_group_i32 != b.h_group_i32) { why = "optical types / recording switches / grating kinds"; return false; }
-  if (a.h_seq != b.h_seq || a.P.scene.seq_enabled != b.P.scene.seq_enabled || a.P.scene.seq_len != b.P.scene.seq_len ||
-      a.P.scene.ignore_mask != b.P.scene.ignore_mask) { why = "tracing sequence / ignored groups"; return false; }
+  if (a.cond != b.cond) { why = "trimming conditions"; return false; }
+  if (a.group_i32 != b.group_i32) { why = "optical types / recording switches / grating kinds"; return false; }
+  if (a.seq != b.seq || a.seq_enabled != b.seq_enabled || a.seq_len != b.seq_len || a.ignore_mask != b.ignore_mask) { why = "tracing sequence / ignored groups"; return false; }
   if (a.lean != b.lean) { why = "gratings or absorbing media in some scenes only"; return false; }
   return true;
 }
@@ -2470,30 +1478,26 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
   if ((rc = build_bvh(ctx))) return rc;
   if (ctx->P.scene.n_nodes || ctx->P.grid.nx > 0)
     return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: batches are traced by the flat kernels (analytic scenes of up to 64 primitives)");
-  const bool compiled = ctx->compile_mode != ODW_COMPILE_OFF && spec_ineligible(ctx).empty();
-  const std::string text0 = compiled ? spec_text(ctx) : std::string();
+  const bool compiled = ctx->compile_mode != ODW_COMPILE_OFF && spec_ineligible(ctx->hs).empty();
+  const std::string text0 = compiled ? spec_text(ctx->hs, ctx->n_samplers) : std::string();
   const size_t n = (size_t)ctx->P.scene.n_prims;
   // one block of doubles per scene: prim_f64 (16 n) | prim_hdr (8 n) | group_f64 (4 x 64) | group_gdir (3 x 64)
   const size_t o_hdr = 16 * n, o_gf = o_hdr + 8 * n, o_gd = o_gf + ODW_MAX_GROUPS * 4, stride = o_gd + ODW_MAX_GROUPS * 3;
   std::vector<double> blocks(stride * (size_t)n_scenes, 0.0);
   for (int k = 0; k < n_scenes; ++k) {
-    odw_ctx tmp;                     // host tables only: no device, no stream
-    std::memset(&tmp.P, 0, sizeof tmp.P);
-    if ((rc = scene_host_tables(&tmp, &scenes[k]))) { ctx->err = tmp.err; g_error = tmp.err; return rc; }
+    HostScene tmp;
     std::string why;
-    if (!same_structure(*ctx, tmp, why))
+    if ((rc = scene_host_tables(&scenes[k], tmp, why))) return fail(ctx, rc, why);
+    if (!same_structure(ctx->hs, tmp, why))
       return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: scene " + std::to_string(k) + " differs from scene 0 in structure (" + why + ")");
-    tmp.P.lim = ctx->P.lim;
-    tmp.have_limits = true;
     std::vector<Box> boxes;
-    std::vector<char> dead;
-    compute_boxes(&tmp, boxes, dead);
-    if (compiled && spec_text(&tmp) != text0)
+    compute_boxes(tmp, ctx->P.lim.dist_tol, boxes);
+    if (compiled && spec_text(tmp, ctx->n_samplers) != text0)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: scene " + std::to_string(k) + " differs from scene 0 in the structure a "
                                             "compiled kernel is built from (which frame entries are 0 / +1 / -1, shared boxes)");
     double* b = blocks.data() + stride * (size_t)k;
-    std::memcpy(b, tmp.h_prim_f64.data(), 16 * n * sizeof(double));
-    std::memcpy(b + o_hdr, tmp.h_prim_hdr.data(), 8 * n * sizeof(double));
+    std::memcpy(b, tmp.prim_f64.data(), 16 * n * sizeof(double));
+    std::memcpy(b + o_hdr, tmp.prim_hdr.data(), 8 * n * sizeof(double));
     // (the isolated-solid shortcut depends on the boxes' values; it never changes a result: left out of batches)
     for (size_t p = 0; p < n; ++p) {
       int32_t w[4];
@@ -2501,16 +1505,16 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
       w[2] &= ~ODW_FLAG_ISOLATED;
       std::memcpy(b + o_hdr + 8 * p + 6, w, sizeof w);
     }
-    std::memcpy(b + o_gf, tmp.h_group_f64.data(), ODW_MAX_GROUPS * 4 * sizeof(double));
-    std::memcpy(b + o_gd, tmp.h_group_gdir.data(), ODW_MAX_GROUPS * 3 * sizeof(double));
+    std::memcpy(b + o_gf, tmp.group_f64.data(), ODW_MAX_GROUPS * 4 * sizeof(double));
+    std::memcpy(b + o_gd, tmp.group_gdir.data(), ODW_MAX_GROUPS * 3 * sizeof(double));
   }
   if ((rc = upload(ctx, ctx->batch_values, blocks.data(), blocks.size() * sizeof(double)))) return rc;
   // the shared integer tables without the isolated-solid flag
-  std::vector<int32_t> pi = ctx->h_prim_i32;
+  std::vector<int32_t> pi = ctx->hs.prim_i32;
   for (size_t p = 0; p < n; ++p) pi[4 * p + 2] &= ~ODW_FLAG_ISOLATED;
   if (n && (rc = upload(ctx, ctx->prim_i32, pi.data(), pi.size() * sizeof(int32_t)))) return rc;
   if ((rc = upload_done(ctx))) return rc;
-  ctx->h_prim_i32 = pi;
+  ctx->hs.prim_i32 = pi;
   ctx->batch_n = n_scenes;
   ctx->batch_prims = n;
   ctx->batch_stride = stride;

@@ -106,33 +106,33 @@ std::string table(const char* type, const char* name, int n, const T* v, F fmt) 
 }
 
 // why the scene cannot be compiled, or empty
-std::string spec_ineligible(const odw_ctx* ctx) {
-  const int n = ctx->P.scene.n_prims;
+std::string spec_ineligible(const HostScene& hs) {
+  const int n = hs.n_prims;
   if (n < 1) return "no primitives";
   if (n > kSpecMaxPrims) return "more primitives (" + std::to_string(n) + ") than a compiled kernel takes (" + std::to_string(kSpecMaxPrims) + ")";
   for (int p = 0; p < n; ++p) {
-    const int t = ctx->h_prim_i32[4 * p];
+    const int t = hs.prim_i32[4 * p];
     if (t == ODW_PRIM_TRIANGLE) return "facets belong to the BVH kernels";
   }
-  if (ctx->h_prim_hdr.size() < (size_t)n * 8 || ctx->h_dead.size() < (size_t)n) return "boxes not built";
+  if (hs.prim_hdr.size() < (size_t)n * 8 || hs.dead.size() < (size_t)n) return "boxes not built";
   return "";
 }
 
 // `struct Spec` of the uploaded scene (tables of scene_host_tables / compute_boxes).  The text is the
 // cache key: equal text = equal kernel.
-std::string spec_text(const odw_ctx* ctx) {
-  const int n = ctx->P.scene.n_prims, ng = ctx->P.scene.n_groups;
+std::string spec_text(const HostScene& hs, int n_samplers) {
+  const int n = hs.n_prims, ng = hs.n_groups;
   std::vector<int> type(n), group(n), flags(n), condw(n), dead(n);
   std::vector<unsigned long long> xf(n);
   for (int p = 0; p < n; ++p) {
-    type[p] = ctx->h_prim_i32[4 * p];
-    group[p] = ctx->h_prim_i32[4 * p + 1];
-    flags[p] = ctx->h_prim_i32[4 * p + 2] & ~ODW_FLAG_ISOLATED;
-    condw[p] = ctx->h_prim_i32[4 * p + 3];
+    type[p] = hs.prim_i32[4 * p];
+    group[p] = hs.prim_i32[4 * p + 1];
+    flags[p] = hs.prim_i32[4 * p + 2] & ~ODW_FLAG_ISOLATED;
+    condw[p] = hs.prim_i32[4 * p + 3];
     const int facemask = (flags[p] >> ODW_FACEMASK_SHIFT) & 0xff;
     // (an empty box is a matter of values: such a primitive stays, its box culls it)
     dead[p] = facemask == 0;
-    const double* m = &ctx->h_prim_f64[16 * (size_t)p];
+    const double* m = &hs.prim_f64[16 * (size_t)p];
     unsigned long long w = 0;
     for (int i = 0; i < 12; ++i) {
       if (m[i] != 0.0) w |= 1ull << i;
@@ -150,11 +150,11 @@ std::string spec_text(const odw_ctx* ctx) {
     std::vector<std::vector<std::vector<int>>> inside(n);
     for (int p = 0; p < n; ++p) {
       const int off = condw[p] & 0xffffff, cnt = (condw[p] >> 24) & 0xff;
-      const int end = std::min(off + cnt, (int)ctx->h_cond.size());
+      const int end = std::min(off + cnt, (int)hs.cond.size());
       inside[p].push_back({p});
       for (int c = off; c < end; ++c) {
-        if (c != off && cond_opens(ctx->h_cond[c])) inside[p].push_back({p});
-        if (ctx->h_cond[c] < 0) inside[p].back().push_back(cond_operand(ctx->h_cond[c]));
+        if (c != off && cond_opens(hs.cond[c])) inside[p].push_back({p});
+        if (hs.cond[c] < 0) inside[p].back().push_back(cond_operand(hs.cond[c]));
       }
       for (std::vector<int>& set : inside[p]) {
         std::sort(set.begin(), set.end());
@@ -171,7 +171,7 @@ std::string spec_text(const odw_ctx* ctx) {
     }
   }
   std::vector<int> gtype(std::max(1, ng)), grec(std::max(1, ng));
-  for (int g = 0; g < ng; ++g) { gtype[g] = ctx->h_group_i32[4 * g]; grec[g] = ctx->h_group_i32[4 * g + 1]; }
+  for (int g = 0; g < ng; ++g) { gtype[g] = hs.group_i32[4 * g]; grec[g] = hs.group_i32[4 * g + 1]; }
   auto fi = [](int v) { return std::to_string(v); };
   auto fu = [](unsigned long long v) { char b[32]; snprintf(b, sizeof b, "0x%llxull", v); return std::string(b); };
   std::string s;
@@ -181,7 +181,7 @@ std::string spec_text(const odw_ctx* ctx) {
        table("int", "flags", n, flags.data(), fi) + table("int", "cond_word", n, condw.data(), fi) +
        table("bool", "dead", n, dead.data(), fi) + table("int", "box_of", n, box_of.data(), fi) +
        table("bool", "box_shared", n, box_shared.data(), fi) +
-       table("int", "cond", (int)ctx->h_cond.size(), ctx->h_cond.data(), fi) +
+       table("int", "cond", (int)hs.cond.size(), hs.cond.data(), fi) +
        table("unsigned long long", "xf", n, xf.data(), fu) + table("int", "gtype", ng, gtype.data(), fi) +
        table("bool", "record", ng, grec.data(), fi);
   // (paraboloids: the generic flat kernel leaves their code out -- it costs every scene 1 % -- and hands such
@@ -196,12 +196,12 @@ std::string spec_text(const odw_ctx* ctx) {
   s += "  static constexpr bool isolated() { return false; }\n";
   s += "  static constexpr int cond_off(int i) { return cond_word(i) & 0xffffff; }\n"
        "  static constexpr int cond_cnt(int i) { return (cond_word(i) >> 24) & 0xff; }\n";
-  s += "  static constexpr unsigned long long umask() { return " + fu(ctx->P.scene.all_mask & ~ctx->P.scene.ignore_mask) + "; }\n";
-  s += std::string("  static constexpr bool seq() { return ") + (ctx->P.scene.seq_enabled ? "true" : "false") + "; }\n";
+  s += "  static constexpr unsigned long long umask() { return " + fu(hs.all_mask & ~hs.ignore_mask) + "; }\n";
+  s += std::string("  static constexpr bool seq() { return ") + (hs.seq_enabled ? "true" : "false") + "; }\n";
   s += "};\n";
-  s += std::string("#define ODW_SPEC_LEAN ") + (ctx->lean ? "true" : "false") + "\n";
+  s += std::string("#define ODW_SPEC_LEAN ") + (hs.lean ? "true" : "false") + "\n";
   // stochastic surfaces: the kernel variant with scatter() (the sampler tables themselves are run-time data)
-  s += std::string("#define ODW_SPEC_STOCH ") + (ctx->n_samplers > 0 ? "true" : "false") + "\n";
+  s += std::string("#define ODW_SPEC_STOCH ") + (n_samplers > 0 ? "true" : "false") + "\n";
   return s;
 }
 
@@ -377,11 +377,11 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
     ctx->spec_pending = false;
   }
   if (ctx->compile_mode == ODW_COMPILE_OFF || !ctx->have_scene) return ODW_OK;
-  if (!spec_ineligible(ctx).empty()) return ODW_OK;
+  if (!spec_ineligible(ctx->hs).empty()) return ODW_OK;
   hipDeviceProp_t prop;
   HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
   const std::string arch = prop.gcnArchName;
-  const std::string text = spec_text(ctx) + (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n" : variant == kSpecPower ? "#define ODW_SPEC_POWER true\n" : "");
+  const std::string text = spec_text(ctx->hs, ctx->n_samplers) + (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n" : variant == kSpecPower ? "#define ODW_SPEC_POWER true\n" : "");
   const char* xo = getenv("ODW_SPEC_OPTS");
   const std::string jkey = arch + "|" + (xo ? xo : "") + "|" + text;
   const std::string key = std::to_string(ctx->device) + "|" + jkey;
@@ -467,7 +467,7 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
     return ODW_OK;
   }
   ctx->spec_fn = it->second.fn;
-  ctx->spec_lean = ctx->lean;
+  ctx->spec_lean = ctx->hs.lean;
   ctx->spec_stoch = ctx->n_samplers > 0;
   return ODW_OK;
 }
