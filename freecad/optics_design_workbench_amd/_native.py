@@ -43,7 +43,7 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_fetch_hits', 'odw_fetch_histogram', 'odw_segment_count', 'odw_fetch_segments', 'odw_reset_segments', 'odw_sample', 'odw_device_histogram',
            'odw_device_counters', 'odw_device_results', 'odw_stream', 'odw_timing_enable', 'odw_timing_read',
            'odw_swap_hit_lists', 'odw_fetch_swapped_hits', 'odw_release_swapped_hits', 'odw_mem_info', 'odw_host_alloc', 'odw_host_free', 'odw_load_hits', 'odw_hits_select', 'odw_hits_gather', 'odw_hits_project', 'odw_hits_range', 'odw_hits_bin', 'odw_hits_moments', 'odw_plane_screen',
-           'odw_compile_scene', 'odw_compiled_info', 'odw_compile_check', 'odw_build_check', 'odw_hits_columns',
+           'odw_compile_scene', 'odw_compiled_info', 'odw_compile_check', 'odw_compile_check_source', 'odw_compiled_source_info', 'odw_upload_source_unguided', 'odw_build_check', 'odw_table_slopes', 'odw_hits_columns',
            'odw_upload_scene_batch', 'odw_trace_batch', 'odw_batch_select', 'odw_batch_rows',
            'odw_plane_screen_batch', 'odw_archive_append', 'odw_archive_select', 'odw_archive_reset', 'odw_batch_hits_select', 'odw_batch_hits_sample', 'odw_batch_hits_project', 'odw_batch_hits_bin',
            'odw_batch_reserve', 'odw_batch_hits_begin', 'odw_batch_hits_sampled', 'odw_batch_hits_measure', 'odw_batch_hits_measured',
@@ -248,19 +248,23 @@ def scene_desc(sc):
   return d, keep
 
 
-def compile_check(scene, limits, mode='structure', arch=None):
+def compile_check(scene, limits, mode='structure', arch=None, source=None):
   """Host only (no GPU): the header of constants the library writes for `scene` and the size of the
   code object hiprtc builds from it for `arch` (default gfx950).  Raises NativeError when the scene
-  is outside the flat kernel's domain or the compilation fails."""
+  is outside the flat kernel's domain or the compilation fails.  source: a baked point source -- the kernel
+  a launch binds that generates its rays from it (ray generation compiled against the source's structure);
+  None: the source-free kernel of explicit rays and batches."""
   d, keep = scene_desc(scene)
   lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
                    float(limits.power_tol))
   buf = C.create_string_buffer(1 << 20)
   size = C.c_uint64(0)
-  f = lib().odw_compile_check
-  f.argtypes = [C.POINTER(SceneDesc), C.POINTER(LimitsDesc), C.c_int32, C.c_char_p, C.c_char_p, C.c_uint64,
-                C.POINTER(C.c_uint64)]
-  rc = f(C.byref(d), C.byref(lim), COMPILE_MODES[mode], arch.encode() if arch else None, buf, len(buf), C.byref(size))
+  f = lib().odw_compile_check_source
+  f.argtypes = [C.POINTER(SceneDesc), C.POINTER(LimitsDesc), C.c_int32, C.c_char_p, C.POINTER(SourceDesc), C.c_char_p,
+                C.c_uint64, C.POINTER(C.c_uint64)]
+  sd, keep_source = source_desc(source) if source is not None else (None, None)
+  rc = f(C.byref(d), C.byref(lim), COMPILE_MODES[mode], arch.encode() if arch else None,
+         C.byref(sd) if sd is not None else None, buf, len(buf), C.byref(size))
   check(None, rc, 'odw_compile_check')
   return buf.value.decode(), int(size.value)
 
@@ -284,6 +288,19 @@ def build_check(scene, limits, library=None):
     raise NativeError(f'odw_build_check: {ERRORS.get(rc, rc)}: {msg.decode() if msg else ""}')
   names = ('primitives', 'nodes', 'grid_cells', 'grid_items', 'grid_lds_bytes', 'dead_primitives')
   return dict(structure=STRUCTURES[int(structure.value)], **{k: int(v) for k, v in zip(names, sizes)})
+
+
+def table_slopes(cdf, edges):
+  """Host only (no GPU): the segment slopes the library stores behind the (cdf, edge) pairs of an inverse-CDF table
+  (`odw_table_slopes`): one row per row of `cdf`, the last knot of a row 0"""
+  edges = _arr(edges, np.float64)
+  cdf = _arr(cdf, np.float64).reshape(-1, len(edges))
+  out = np.empty_like(cdf)
+  f = lib().odw_table_slopes
+  f.argtypes = [_pd, _pd, C.c_int32, C.c_int32, _pd]
+  rc = f(cdf.ctypes.data_as(_pd), edges.ctypes.data_as(_pd), cdf.shape[0], cdf.shape[1], out.ctypes.data_as(_pd))
+  check(None, rc, 'odw_table_slopes')
+  return out
 
 
 def source_desc(src):

@@ -60,6 +60,30 @@ bool clauses_marked(const int32_t* cond_off, int n, const std::vector<int32_t>& 
   return true;
 }
 
+// ---- sampler tables --------------------------------------------------------------------------
+// The slope of segment j of an inverse-CDF table, (edge[j+1] - edge[j]) / (cdf[j+1] - cdf[j]): what numpy.interp
+// computes per sample and the kernels used to compute per ray.  A plain double division, correctly rounded like
+// the device's, so the bits are the same.  A repeated cdf knot divides by zero as numpy does (+-inf, 0 / 0 = nan: no
+// sample ever lands on such a segment, the search takes the last knot with cdf <= u).
+inline double table_slope(double cdf0, double edge0, double cdf1, double edge1) {
+  const double num = edge1 - edge0, den = cdf1 - cdf0;
+  if (den == 0.0) return num > 0.0 ? INFINITY : num < 0.0 ? -INFINITY : std::numeric_limits<double>::quiet_NaN();
+  return num / den;
+}
+
+// `tab` holds n_tables tables of n_knots interleaved (cdf, edge) pairs each; behind them go the slopes, one double
+// per knot in the same order (the last knot of a table has no segment: 0).  The pairs stay where they are, 16-byte
+// aligned; inv_cdf (odw_kernels.hip) reads the slope of the knot it found with one 8-byte load.
+inline void append_slopes(std::vector<double>& tab, size_t n_tables, size_t n_knots) {
+  const size_t n = n_tables * n_knots;
+  tab.resize(3 * n);
+  for (size_t t = 0; t < n_tables; ++t)
+    for (size_t j = 0; j < n_knots; ++j) {
+      const double* a = &tab[2 * (t * n_knots + j)];
+      tab[2 * n + t * n_knots + j] = j + 1 < n_knots ? table_slope(a[0], a[1], a[2], a[3]) : 0.0;
+    }
+}
+
 // host half of odw_upload_scene: validation and the host copies of every table.  hs is complete only where the
 // answer is ODW_OK
 int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) {

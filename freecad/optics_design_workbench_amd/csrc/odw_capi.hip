@@ -78,6 +78,8 @@ struct odw_ctx {
   // scene-compiled flat kernel (odw_spec.hip)
   int compile_mode = 0;                    // ODW_COMPILE_*: sticky, applies to every scene uploaded later too
   bool spec_dirty = true;                  // scene / limits changed since the last binding attempt
+  uint64_t source_key = 0;                 // structure of the table source the context holds (odw_spec.hip: spec_source_key), or 0
+  uint64_t spec_source_key = 0;            // the same of the source the bound kernel is compiled against, 0: source-free
   hipFunction_t spec_fn = nullptr;         // bound kernel (owned by the process-wide cache), or null
   bool spec_lean = false, spec_stoch = false;
   // ODW_COMPILE_AUTO: the scene's kernel is not there yet (not hot enough, or being compiled)
@@ -475,6 +477,14 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   if (ctx->bvh_dirty) {
     int rc = build_bvh(ctx);
     if (rc) return rc;
+  }
+  // a launch that generates its rays takes the kernel compiled against its source's structure; explicit rays and
+  // batches (whose rays come from buffers) run whatever is bound, and bind the source-free kernel if nothing is
+  {
+    uint64_t want = ctx->spec_source_key;
+    if (!explicit_rays && !ctx->batch_launch) want = ctx->source_key;
+    else if (ctx->spec_dirty) want = 0;
+    if (want != ctx->spec_source_key) { ctx->spec_source_key = want; ctx->spec_dirty = true; }
   }
   if (ctx->spec_dirty) {
     // a scene kernel that cannot be built (no hiprtc on this machine, a compiler error) is not a reason to
@@ -932,6 +942,7 @@ int odw_compile_scene(odw_ctx* ctx, int32_t mode) {
   ctx->compile_mode = mode;
   ctx->spec_dirty = true;
   ctx->spec_fn = nullptr;
+  ctx->spec_source_key = ctx->source_key;      // (none yet: the source-free kernel; the launch after odw_upload_source binds again)
   if (mode == ODW_COMPILE_OFF || !ctx->have_scene || !ctx->have_limits) return ODW_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->bvh_dirty) {
@@ -949,6 +960,12 @@ int odw_compiled_info(odw_ctx* ctx, int32_t* bound, double* compile_seconds, int
   return ODW_OK;
 }
 
+int odw_compiled_source_info(odw_ctx* ctx, uint64_t* structure) {
+  if (!ctx || !structure) return fail(ctx, ODW_ERR_INVALID, "odw_compiled_source_info: bad argument");
+  *structure = (ctx->spec_fn && !ctx->spec_dirty && !ctx->bvh_dirty) ? ctx->spec_source_key : 0;
+  return ODW_OK;
+}
+
 int odw_compiled_power_info(odw_ctx* ctx, int32_t* bound) {
   if (!ctx || !bound) return fail(ctx, ODW_ERR_INVALID, "odw_compiled_power_info: bad argument");
   *bound = (ctx->spec_fn && ctx->spec_power_fn && !ctx->spec_dirty && !ctx->bvh_dirty) ? ctx->compile_mode : 0;
@@ -957,6 +974,14 @@ int odw_compiled_power_info(odw_ctx* ctx, int32_t* bound) {
 
 int odw_compile_check(const odw_scene_desc* scene, const odw_limits* limits, int32_t mode, const char* arch,
                       char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
+  return odw_compile_check_source(scene, limits, mode, arch, nullptr, header_out, header_capacity, code_bytes);
+}
+
+// source: the kernel a launch that generates its rays from `source` binds (header with `struct SpecSource`, as
+// odw_upload_source keys it: guides present); NULL: the source-free kernel of explicit rays and batches
+int odw_compile_check_source(const odw_scene_desc* scene, const odw_limits* limits, int32_t mode, const char* arch,
+                             const odw_source_desc* source, char* header_out, uint64_t header_capacity,
+                             uint64_t* code_bytes) {
   if (!scene || !limits || mode != ODW_COMPILE_STRUCTURE)
     return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check: bad argument");
   HostScene tmp;
@@ -967,7 +992,8 @@ int odw_compile_check(const odw_scene_desc* scene, const odw_limits* limits, int
   compute_boxes(tmp, limits->dist_tol, boxes);
   const std::string why = spec_ineligible(tmp);
   if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_compile_check: " + why);
-  const std::string text = spec_text(tmp, 0);
+  const std::string text = spec_text(tmp, 0) +
+      (source ? spec_source_text(spec_source_key(source->xform, source->n_t_rows, true, std::isfinite(source->focal_length))) : "");
   if (header_out && header_capacity) {
     const size_t k = std::min<size_t>(text.size(), (size_t)header_capacity - 1);
     std::memcpy(header_out, text.data(), k);
@@ -1015,6 +1041,20 @@ int odw_build_check(const odw_scene_desc* scene, const odw_limits* limits, int32
     sizes[4] = (uint64_t)A.grid.lds_bytes;
     sizes[5] = dead;
   }
+  return ODW_OK;
+}
+
+// The slopes append_slopes (odw_build.h) puts behind the pairs of an uploaded table, for a caller without a device:
+// the same function on the same interleaved layout.
+int odw_table_slopes(const double* cdf, const double* edges, int32_t n_tables, int32_t n_knots, double* slopes) {
+  if (!cdf || !edges || !slopes || n_tables < 1 || n_knots < 2)
+    return fail(nullptr, ODW_ERR_INVALID, "odw_table_slopes: bad argument");
+  const size_t nt = (size_t)n_tables, nk = (size_t)n_knots;
+  std::vector<double> tab(nt * nk * 2);
+  for (size_t t = 0; t < nt; ++t)
+    for (size_t j = 0; j < nk; ++j) { tab[2 * (t * nk + j)] = cdf[t * nk + j]; tab[2 * (t * nk + j) + 1] = edges[j]; }
+  append_slopes(tab, nt, nk);
+  std::memcpy(slopes, tab.data() + 2 * nt * nk, nt * nk * sizeof(double));
   return ODW_OK;
 }
 
@@ -1079,6 +1119,8 @@ int odw_upload_surface_samplers(odw_ctx* ctx, const odw_surface_sampler_desc* sa
         }
       }
     }
+    append_slopes(ptab, nf, np);
+    append_slopes(ttab, nf * rows, nt);
     odw_ctx::SurfaceBufs& sb = ctx->surf_bufs[(size_t)i];
     int rc;
     if ((rc = upload(ctx, sb.phi_tab, ptab.data(), ptab.size() * sizeof(double)))) return rc;
@@ -1132,7 +1174,15 @@ int odw_set_surface_seed(odw_ctx* ctx, uint64_t seed) {
   return ODW_OK;
 }
 
-int odw_upload_source(odw_ctx* ctx, const odw_source_desc* s) {
+static int upload_source(odw_ctx* ctx, const odw_source_desc* s, bool guides);
+
+int odw_upload_source(odw_ctx* ctx, const odw_source_desc* s) { return upload_source(ctx, s, true); }
+
+int odw_upload_source_unguided(odw_ctx* ctx, const odw_source_desc* s) { return upload_source(ctx, s, false); }
+
+// guides = false: no azimuth guide and a theta guide of one cell, i.e. plain binary searches over the whole tables --
+// the same knots are found, the same rays come out (odw_upload_source_unguided, tests/test_gpu_spec_source.py)
+static int upload_source(odw_ctx* ctx, const odw_source_desc* s, bool guides) {
   if (!ctx || !s) return fail(ctx, ODW_ERR_INVALID, "odw_upload_source: null argument");
   if (s->n_phi_knots < 2 || s->n_t_knots < 2 || s->n_t_rows < 1 ||
       (s->n_t_rows != 1 && s->n_t_rows != s->n_phi_knots - 1))
@@ -1145,7 +1195,8 @@ int odw_upload_source(odw_ctx* ctx, const odw_source_desc* s) {
     return fail(ctx, ODW_ERR_INVALID, "phi cdf must run from 0 to 1");
   std::vector<double> ptab((size_t)np * 2), ttab((size_t)rows * nt * 2);
   for (int i = 0; i < np; ++i) { ptab[2 * i] = s->phi_cdf[i]; ptab[2 * i + 1] = s->phi_edges[i]; }
-  std::vector<int32_t> guide((size_t)rows * (kGuide + 1));
+  const int n_guide = guides ? kGuide : 1;
+  std::vector<int32_t> guide((size_t)rows * (n_guide + 1));
   for (int r = 0; r < rows; ++r) {
     const double* cdf = s->t_cdf + (size_t)r * nt;
     if (cdf[0] != 0.0 || cdf[nt - 1] != 1.0) return fail(ctx, ODW_ERR_INVALID, "theta cdf rows must run from 0 to 1");
@@ -1157,14 +1208,16 @@ int odw_upload_source(odw_ctx* ctx, const odw_source_desc* s) {
     }
     // guide[k] = last knot with cdf <= k/G: brackets the search for any u in
     // [k/G, (k+1)/G) without changing which knot is found
-    int32_t* g = guide.data() + (size_t)r * (kGuide + 1);
+    int32_t* g = guide.data() + (size_t)r * (n_guide + 1);
     int j = 0;
-    for (int k = 0; k <= kGuide; ++k) {
-      const double x = (double)k / (double)kGuide;
+    for (int k = 0; k <= n_guide; ++k) {
+      const double x = (double)k / (double)n_guide;
       while (j + 1 < nt && cdf[j + 1] <= x) ++j;
       g[k] = j;
     }
   }
+  append_slopes(ptab, 1, (size_t)np);
+  append_slopes(ttab, (size_t)rows, (size_t)nt);
   int rc;
   if ((rc = upload(ctx, ctx->phi_tab, ptab.data(), ptab.size() * sizeof(double)))) return rc;
   if ((rc = upload(ctx, ctx->t_tab, ttab.data(), ttab.size() * sizeof(double)))) return rc;
@@ -1186,18 +1239,20 @@ int odw_upload_source(odw_ctx* ctx, const odw_source_desc* s) {
   d.phi_tab = (const double*)ctx->phi_tab.p;
   d.t_tab = (const double*)ctx->t_tab.p;
   d.t_guide = (const int32_t*)ctx->t_guide.p;
-  d.phi_guide = (const int32_t*)ctx->phi_guide.p;
-  d.n_phi_guide = kPhiGuide;
+  d.phi_guide = guides ? (const int32_t*)ctx->phi_guide.p : nullptr;
+  d.n_phi_guide = guides ? kPhiGuide : 0;
   d.n_phi_knots = np;
   d.n_t_knots = nt;
   d.n_t_rows = rows;
-  d.n_guide = kGuide;
+  d.n_guide = n_guide;
   if ((rc = upload(ctx, ctx->d_source, &ctx->h_source, sizeof(DeviceSource)))) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->P.source = (const DeviceSource*)ctx->d_source.p;
   ctx->P.wavelength = s->wavelength;
   ctx->have_source = true;
   ctx->emitter_active = false;
+  ctx->source_key = spec_source_key(ctx->h_source);
+  if (ctx->spec_source_key && ctx->spec_source_key != ctx->source_key) ctx->spec_dirty = true;   // a source of another structure
   return ODW_OK;
 }
 
@@ -1262,6 +1317,7 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
     ttab[2 * i] = s->t_cdf[i];
     ttab[2 * i + 1] = s->t_edges[i];
   }
+  append_slopes(ttab, 1, (size_t)nt);
   std::vector<int32_t> guide((size_t)kGuide + 1);
   for (int k = 0, j = 0; k <= kGuide; ++k) {
     const double x = (double)k / (double)kGuide;
@@ -1296,6 +1352,7 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   ctx->P.wavelength = s->wavelength;
   ctx->have_source = true;
   ctx->emitter_active = true;
+  ctx->source_key = 0;                     // (emitted rays reach the trace kernels through buffers, like explicit ones)
   return ODW_OK;
 }
 

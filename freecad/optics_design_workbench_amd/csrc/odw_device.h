@@ -110,8 +110,8 @@ struct DeviceGrid {
 struct DeviceSource {
   double m[12];                 // local -> global
   double focal_length, wavelength, power;
-  const double* phi_tab;        // [n_phi_knots*2] (cdf, edge)
-  const double* t_tab;          // [rows*n_t_knots*2]
+  const double* phi_tab;        // [n_phi_knots*2] (cdf, edge), then [n_phi_knots] segment slopes
+  const double* t_tab;          // [rows*n_t_knots*2], then [rows*n_t_knots] segment slopes
   const int32_t* t_guide;       // [rows*(GUIDE+1)] bracket guide for the inverse CDF
   const int32_t* phi_guide;     // [n_phi_guide+1] the same for the azimuth table
   int32_t n_phi_knots, n_t_knots, n_t_rows, n_guide, n_phi_guide;
@@ -121,8 +121,8 @@ struct DeviceSource {
 // one stochastic-surface sampler (odw_surface_sampler_desc): a family of
 // source-like tables, member k = one value of the per-hit constant
 struct DeviceSurfaceSampler {
-  const double* phi_tab;        // [n_family][n_phi_knots*2]
-  const double* t_tab;          // [n_family][rows*n_t_knots*2]
+  const double* phi_tab;        // [n_family][n_phi_knots*2], then [n_family][n_phi_knots] segment slopes
+  const double* t_tab;          // [n_family][rows*n_t_knots*2], then [n_family][rows*n_t_knots] segment slopes
   const int32_t* t_guide;       // [n_family][rows*(n_guide+1)]
   int32_t n_phi_knots, n_t_knots, n_t_rows, n_guide;
   int32_t axis, n_family;
@@ -141,7 +141,7 @@ struct DeviceEmitter {
   const int32_t* cond_i32;      // prim | inside<<31
   const int32_t* face_i32;      // [n_faces*2] prim, face
   const double* face_cdf;       // [n_faces+1] cumulative untrimmed area / total
-  const double* t_tab;          // [n_t_knots*2] (cdf, edge)
+  const double* t_tab;          // [n_t_knots*2] (cdf, edge), then [n_t_knots] segment slopes
   const int32_t* t_guide;       // [n_guide+1]
   const double* tri_nrm;        // [n_prims*9] vertex normals of TRIANGLE primitives, or null
   int32_t n_faces, n_t_knots, n_guide;

@@ -110,38 +110,45 @@ __device__ __forceinline__ void ray_uniforms(uint64_t ray, uint64_t seed, double
 // table = interleaved (cdf, edge) pairs; cdf[0] = 0, cdf[n-1] = 1, u in [0,1).
 // Finds j = last knot with cdf[j] <= u inside the bracket [lo, hi] and
 // evaluates slope*(u - cdf[j]) + edge[j] WITHOUT fma contraction, i.e. the
-// exact arithmetic of numpy's arr_interp.
-__device__ __forceinline__ double inv_cdf(const double* __restrict__ tab, int lo, int hi, double u) {
+// exact arithmetic of numpy's arr_interp.  slope[j] = (edge[j+1] - edge[j]) /
+// (cdf[j+1] - cdf[j]) belongs to the knot, not to the ray: the host works it
+// out once per table (odw_build.h: append_slopes, a correctly rounded division
+// like the one this function used to do per ray) and stores it behind the pairs.
+__device__ __forceinline__ double inv_cdf(const double* __restrict__ tab, const double* __restrict__ slope, int lo, int hi,
+                                          double u) {
 #pragma clang fp contract(off)
   while (hi - lo > 1) {
     const int mid = (lo + hi) >> 1;
     if (u >= tab[2 * mid]) lo = mid; else hi = mid;
   }
   const double2 a = *reinterpret_cast<const double2*>(tab + 2 * lo);
-  const double2 b = *reinterpret_cast<const double2*>(tab + 2 * lo + 2);
+  const double sl = slope[lo];
   if (a.x == u) return a.y;
-  const double slope = (b.y - a.y) / (b.x - a.x);
-  const double prod = slope * (u - a.x);
+  const double prod = sl * (u - a.x);
   return prod + a.y;
 }
 
 struct TableView {
   const double* phi_tab; const double* t_tab; const int32_t* t_guide;
+  const double* phi_slope; const double* t_slope;  // [n_phi_knots], [rows*n_t_knots]: behind the pairs of the same buffer
   int n_phi_knots, n_t_knots, n_t_rows, n_guide;
   const int32_t* phi_guide; int n_phi_guide;      // optional (null: plain binary search)
 };
+// KNOWN: whether the azimuth guide exists and whether there is one theta table or one per phi cell are constants
+// of the caller (a source a kernel was compiled against: SpecSource), else read from the view
+template <bool KNOWN = false, bool PHI_GUIDE = false, bool SINGLE_ROW = false>
 __device__ __forceinline__ void sample_tables(const TableView& s, double u_phi, double u_t,
                                               double& t_out, double& phi_out) {
 #pragma clang fp contract(off)
   int plo = 0, phi_hi = s.n_phi_knots - 1;
-  if (s.phi_guide) {                     // bracket from the guide: two independent loads instead of a chain of ~7
+  if (KNOWN ? PHI_GUIDE : s.phi_guide != nullptr) {                     // bracket from the guide: two independent loads instead of a chain of ~7
     const int k = (int)(u_phi * (double)s.n_phi_guide);
     plo = s.phi_guide[k];
     phi_hi = min(s.phi_guide[k + 1] + 1, s.n_phi_knots - 1);
   }
-  const double phi = inv_cdf(s.phi_tab, plo, phi_hi, u_phi);
+  const double phi = inv_cdf(s.phi_tab, s.phi_slope, plo, phi_hi, u_phi);
   int row = 0;
-  if (s.n_t_rows > 1) {
+  if (KNOWN ? !SINGLE_ROW : s.n_t_rows > 1) {
     // argmin_i |mid_i - phi| (first minimum): the candidate is the cell that
     // contains phi, the exact rule is applied to it and its two neighbours
     const double e0 = s.phi_tab[1], e1 = s.phi_tab[2 * (s.n_phi_knots - 1) + 1];
@@ -155,21 +162,25 @@ __device__ __forceinline__ void sample_tables(const TableView& s, double u_phi, 
     }
   }
   const double* tab = s.t_tab + (size_t)row * (size_t)s.n_t_knots * 2;
+  const double* slope = s.t_slope + (size_t)row * (size_t)s.n_t_knots;
   const int32_t* guide = s.t_guide + (size_t)row * (size_t)(s.n_guide + 1);
   const int k = (int)(u_t * (double)s.n_guide);
   const int lo = guide[k];
   const int hi = min(guide[k + 1] + 1, s.n_t_knots - 1);
-  t_out = inv_cdf(tab, lo, hi, u_t);
+  t_out = inv_cdf(tab, slope, lo, hi, u_t);
   phi_out = phi;
 }
 
+template <bool KNOWN = false, bool PHI_GUIDE = false, bool SINGLE_ROW = false>
 __device__ __forceinline__ void sample_source(csource sp_, double u_phi, double u_t,
                                               double& t_out, double& phi_out) {
   TableView s;
   s.phi_tab = sp_->phi_tab; s.t_tab = sp_->t_tab; s.t_guide = sp_->t_guide;
   s.n_phi_knots = sp_->n_phi_knots; s.n_t_knots = sp_->n_t_knots; s.n_t_rows = sp_->n_t_rows; s.n_guide = sp_->n_guide;
   s.phi_guide = sp_->phi_guide; s.n_phi_guide = sp_->n_phi_guide;
-  sample_tables(s, u_phi, u_t, t_out, phi_out);
+  s.phi_slope = s.phi_tab + (size_t)s.n_phi_knots * 2;
+  s.t_slope = s.t_tab + (size_t)s.n_t_rows * (size_t)s.n_t_knots * 2;
+  sample_tables<KNOWN, PHI_GUIDE, SINGLE_ROW>(s, u_phi, u_t, t_out, phi_out);
 }
 
 template <class P>
@@ -200,10 +211,21 @@ __device__ __forceinline__ d3 xf_vec_t(P m, d3 v) {  // R^T v
 struct NoSpec {
   static constexpr bool enabled = false;
   static constexpr int N = 0;
+  static constexpr int NG = 0;
   static constexpr unsigned long long xf(int) { return 0xfffull; }
   static constexpr int type(int) { return 0; }
+  static constexpr int gtype(int) { return 0; }
   static constexpr int cond(int) { return 0; }
   static constexpr bool isolated() { return true; }
+};
+// The STRUCTURE of the point source a kernel is compiled against (odw_spec.h: struct SpecSource, written when the
+// launch that binds the kernel generates its rays from a table source): one theta table or one per phi cell,
+// azimuth guide or not, focal length finite or not, zero / +-1 pattern of the source's frame (the encoding of
+// Spec::xf).  Table sizes and every value stay run-time data.  NoSource = the generic generation (generate_ray).
+struct NoSource {
+  static constexpr bool enabled = false;
+  static constexpr bool single_row = false, phi_guide = false, finite_focal = false;
+  static constexpr unsigned long long xf = 0xfffull;
 };
 // Frame products of a compiled scene.  XF = the pattern of a primitive's 12 frame entries: bits 0-11
 // entry != 0, bits 12-23 entry == +1, bits 24-35 entry == -1.  A term whose coefficient is exactly zero
@@ -269,12 +291,14 @@ __device__ __forceinline__ void sincos_bounded(double x, double& s, double& c) {
 }
 
 // PointSourceProxy._makeRay (point_source.py:411-460)
+// SRC: a source whose structure is known (SpecSource): the branch folds, the frame products skip their zero terms
+template <class SRC = NoSource>
 __device__ __forceinline__ void make_ray(csource s, double t_or_r, double phi,
                                          d3& origin, d3& dir) {
   d3 ldir, lorg;
   double sp, cp;
   sincos_bounded(phi, sp, cp);
-  if (s->finite_focal) {
+  if (SRC::enabled ? SRC::finite_focal : s->finite_focal != 0) {
     double st, ct;
     sincos_bounded(t_or_r, st, ct);
     ldir = mk(st * sp, -st * cp, ct);
@@ -286,8 +310,14 @@ __device__ __forceinline__ void make_ray(csource s, double t_or_r, double phi,
   // (both vectors are unit vectors up to rounding already: the two normalisations of the reference move them
   //  by an ulp or two, frsqrt -- <= 2 ulp -- does the same without the IEEE square root and division)
   const d3 ln = ldir * frsqrt(dot(ldir, ldir));
-  const d3 p1 = xf_point(s->m, lorg);
-  const d3 p2 = xf_point(s->m, lorg + ln);
+  d3 p1, p2;
+  if constexpr (SRC::enabled) {
+    p1 = xf_point_nz<SRC::xf>(s->m, lorg);
+    p2 = xf_point_nz<SRC::xf>(s->m, lorg + ln);
+  } else {
+    p1 = xf_point(s->m, lorg);
+    p2 = xf_point(s->m, lorg + ln);
+  }
   const d3 d = p2 - p1;
   origin = p1;
   dir = d * frsqrt(dot(d, d));
@@ -793,10 +823,25 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     double bt = INFINITY;
     int bf = 0;
 #define ODW_PICK(T, F) { const bool w_ = (bool)((int)((T) > tol) & ((int)((T) < bt) | ((int)((T) == bt) & (int)((F) < bf)))); bt = w_ ? (T) : bt; bf = w_ ? (F) : bf; }
+    if constexpr (SPEC::enabled) {
+      // only the slots this primitive's type and faces can fill (the table of the trimmed branch below): an unfilled
+      // slot holds (INF, 0), which never wins, but judging it is not free -- the compiler cannot tell
+      constexpr int ty = SPEC::type(PI), fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
+      constexpr bool quadric = ty == ODW_PRIM_CYLINDER || ty == ODW_PRIM_CONE || ty == ODW_PRIM_PARABOLOID;
+      constexpr bool pair = ty == ODW_PRIM_BOX || (fm & 1) != 0;      // box: entry / exit face; else the surface's two roots
+      constexpr bool caps = ty != ODW_PRIM_BOX && ty != ODW_PRIM_SPHERE;
+      if constexpr (pair) {
+        ODW_PICK(c.t0, c.f0)
+        ODW_PICK(c.t1, c.f1)
+      }
+      if constexpr (caps && (quadric ? (fm & 2) != 0 : (fm & 1) != 0)) ODW_PICK(c.t2, c.f2)
+      if constexpr (caps && (quadric ? (fm & 4) != 0 : (fm & 1) != 0)) ODW_PICK(c.t3, c.f3)
+    } else {
     ODW_PICK(c.t0, c.f0)
     ODW_PICK(c.t1, c.f1)
     ODW_PICK(c.t2, c.f2)
     ODW_PICK(c.t3, c.f3)
+    }
 #undef ODW_PICK
     if constexpr (SPEC::enabled) consider_spec<PARAB, SPEC, PI>(sv, q, bt, bf);
     else consider<PARAB>(sv, q, bt, p, bf, group, 0, 0);
@@ -1236,6 +1281,8 @@ __device__ __forceinline__ void surface_draw(const DeviceSurfaceSampler* sp, dou
   tv.t_guide = S.t_guide + (size_t)k * (size_t)S.n_t_rows * (size_t)(S.n_guide + 1);
   tv.n_phi_knots = S.n_phi_knots; tv.n_t_knots = S.n_t_knots; tv.n_t_rows = S.n_t_rows; tv.n_guide = S.n_guide;
   tv.phi_guide = nullptr; tv.n_phi_guide = 0;
+  tv.phi_slope = S.phi_tab + ((size_t)S.n_family * 2 + (size_t)k) * (size_t)S.n_phi_knots;
+  tv.t_slope = S.t_tab + ((size_t)S.n_family * 2 + (size_t)k) * (size_t)S.n_t_rows * (size_t)S.n_t_knots;
   sample_tables(tv, u_phi, u_t, theta, phi);
 }
 
@@ -1496,11 +1543,59 @@ __device__ __noinline__ RayInit generate_ray(const DeviceSource* sp, uint64_t ra
   return r;
 }
 
+// generate_ray() for a source whose structure the kernel was compiled against: inlined into the ray loop, where the
+// source pointer is the kernel's own argument -- every field and table pointer is a scalar load, the branches on the
+// source's structure fold, nothing goes through the stack.  The same arithmetic in the same order: the same rays.
+template <class SRC>
+__device__ __forceinline__ RayInit generate_ray_spec(csource src, uint64_t ray, uint64_t seed) {
+  RayInit r;
+  double up, ut, t, phi;
+  ray_uniforms(ray, seed, up, ut);
+  sample_source<true, SRC::phi_guide, SRC::single_row>(src, up, ut, t, phi);
+  make_ray<SRC>(src, t, phi, r.point, r.dir);
+  r.power = src->power;
+  return r;
+}
+
+// The same out of line: a collimated source (focal length not finite: make_ray() places the origin too) inlined
+// into the ray loop costs the c3 structure 24 VGPR spills and 144 bytes of scratch against none and 48, so that
+// form keeps the call -- still compiled against the source, its branches folded.
+template <class SRC>
+__device__ __noinline__ RayInit generate_ray_spec_call(csource src, uint64_t ray, uint64_t seed) {
+  return generate_ray_spec<SRC>(src, ray, seed);
+}
+
+// Word K of the optical constants of the medium a ray travels in (group_f64[4 * medium + K], medium >= 0).  The
+// generic kernels gather it per lane.  A compiled scene knows which groups can be a medium at all -- lenses, and
+// transmission gratings -- and there are a handful at most: a select over them, every operand a scalar load at a
+// constant offset, no vector load to wait for.  (More than eight such groups: the gather.)
+constexpr bool can_be_medium(int gtype) {     // interact(): the groups whose branch sets `medium`
+  return gtype != ODW_OPT_MIRROR && gtype != ODW_OPT_ABSORBER && gtype != ODW_OPT_VACUUM;
+}
+template <class SPEC, int G = 0>
+constexpr int spec_media() {
+  if constexpr (G >= SPEC::NG) return 0;
+  else return (can_be_medium(SPEC::gtype(G)) ? 1 : 0) + spec_media<SPEC, G + 1>();
+}
+template <class SPEC, int K, int G = 0>
+__device__ __forceinline__ double spec_medium_word(cf64 group_f64, int medium, double v) {
+  if constexpr (G < SPEC::NG) {
+    v = spec_medium_word<SPEC, K, G + 1>(group_f64, medium, v);
+    if constexpr (can_be_medium(SPEC::gtype(G))) v = medium == G ? group_f64[4 * G + K] : v;
+  }
+  return v;
+}
+template <class SPEC, int K>
+__device__ __forceinline__ double medium_word(cf64 group_f64, int medium) {
+  if constexpr (SPEC::enabled && spec_media<SPEC>() <= 8) return spec_medium_word<SPEC, K>(group_f64, medium, 0.0);
+  else return group_f64[4 * medium + K];
+}
+
 // K3 for one hit, the part that depends on the optical group: recording, mirror / Snell / absorb /
 // vacuum / grating, medium and sequence state (ray.py:91-281).  The generic kernels pass the group's
 // words as read from the tables; a compiled scene passes constants and the branches fold.
 // n: surface normal along the travel direction; cnt: the thread's column of event counters.
-template <bool BVH, bool STOCH, bool LEAN, bool POWER = false>
+template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec>
 __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, ci32 group_i32, cf64 group_gdir, int g,
                                          int gtype, bool record, d3 n, bool entering, uint64_t ray, int nint,
                                          uint32_t* cnt, uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power,
@@ -1526,7 +1621,7 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
     power *= group_f64[4 * g + 1];
     ++seq;
   } else if (gtype == ODW_OPT_LENS) {
-    const double n1 = (medium >= 0) ? group_f64[4 * medium] : 1.0;
+    const double n1 = (medium >= 0) ? medium_word<SPEC, 0>(group_f64, medium) : 1.0;
     double n2 = 1.0;
     if (entering) { medium = g; n2 = group_f64[4 * g]; }
     bool tir;
@@ -1551,7 +1646,7 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
     const int order = group_i32[4 * g + 3];
     if (group_i32[4 * g + 2] == 0) {
       if (entering) {
-        const double nn = (medium >= 0) ? group_f64[4 * medium] : 1.0;
+        const double nn = (medium >= 0) ? medium_word<SPEC, 0>(group_f64, medium) : 1.0;
         dir = line_grating(dir, nn, nn, n, P.wavelength, order, lpm, gd, false);
         ++seq;
       }
@@ -1565,7 +1660,7 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
       medium = g;
       dir = line_grating(dir, 1.0, group_f64[4 * g], n, P.wavelength, order, lpm, gd, true);
     } else {
-      const double n1 = (medium >= 0) ? group_f64[4 * medium] : 1.0;
+      const double n1 = (medium >= 0) ? medium_word<SPEC, 0>(group_f64, medium) : 1.0;
       bool tir;
       dir = snells_law(dir, n1, 1.0, n, tir);
       if (!tir) { medium = -1; ++seq; }
@@ -1595,7 +1690,7 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
 #endif
   const bool entering = dot(dir, n) < 0;
   if (entering) n = n * -1.0;
-  interact<false, STOCH, LEAN, POWER>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
+  interact<false, STOCH, LEAN, POWER, SPEC>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
                                nint, cnt, hit_state, win, point, dir, power, medium, seq, alive);
   // n points along the incoming travel direction: out of the solid when leaving it, into it when entering
   const double out = entering ? -dot(dir, n) : dot(dir, n);
@@ -1671,7 +1766,8 @@ template <> struct HitBlockState<false> {
 // LEAN: the scene has no grating group and no finite absorption length (the host checks): their code
 // -- line_grating's chain of IEEE divisions and square roots, exp() -- is left out of the binary
 // BATCH (flat kernels): scenes of one structure side by side in one launch (DeviceBatch)
-template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false>
+template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false,
+          class SRC = NoSource>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
   static_assert(!BATCH || (!BVH && !SEG), "batch launches: flat kernels, no segment rows");
   extern __shared__ int bvh_stack[];  // ODW_BVH_STACK x 256 ints (BVH variant only)
@@ -1794,7 +1890,10 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
           else point = mk(gd[3 * gs], gd[3 * gs + 1], gd[3 * gs + 2]);
           power = as_const(P.source)->power;
         } else {
-          const RayInit r = generate_ray(P.source, P.first_ray + i, P.seed);
+          RayInit r;
+          if constexpr (SRC::enabled && SRC::finite_focal) r = generate_ray_spec<SRC>(as_const(P.source), P.first_ray + i, P.seed);
+          else if constexpr (SRC::enabled) r = generate_ray_spec_call<SRC>(as_const(P.source), P.first_ray + i, P.seed);
+          else r = generate_ray(P.source, P.first_ray + i, P.seed);
           point = r.point; dir = r.dir; power = r.power;
 #if ODW_DOUBLE == 8
           {
@@ -1847,7 +1946,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       point = point + dir * t_hit;
       // absorption along the traversed medium (ray.py:120-125, assignment)
       if (!LEAN && medium >= 0) {
-        const double L = group_f64[4 * medium + 2];
+        const double L = medium_word<SPEC, 2>(group_f64, medium);
         if (L == 0) power = 0;
         else if (L < INFINITY) power = exp(-t_hit / L);
       }
@@ -1952,8 +2051,11 @@ __global__ __launch_bounds__(256, BVH ? ODW_WAVES_PER_SIMD_BVH : ODW_WAVES_PER_S
 #ifndef ODW_SPEC_POWER
 #define ODW_SPEC_POWER false
 #endif
+#ifndef ODW_SPEC_SOURCE            // the header carries `struct SpecSource` and names it here when a source is bound
+#define ODW_SPEC_SOURCE NoSource
+#endif
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(const TraceParams P) {
-  trace_body<false, ODW_SPEC_STOCH, false, ODW_SPEC_LEAN, Spec, ODW_SPEC_BATCH, ODW_SPEC_POWER>(P);
+  trace_body<false, ODW_SPEC_STOCH, false, ODW_SPEC_LEAN, Spec, ODW_SPEC_BATCH, ODW_SPEC_POWER, ODW_SPEC_SOURCE>(P);
 }
 #endif
 
@@ -2111,7 +2213,7 @@ __global__ __launch_bounds__(256) void odw_emit_kernel(const DeviceEmitter E, ui
     double u_t, u_phi;
     philox_pair(ray, seed, 0u, 5u, u_t, u_phi);
     const int k = (int)(u_t * (double)E.n_guide);
-    const double theta = inv_cdf(E.t_tab, E.t_guide[k], min(E.t_guide[k + 1] + 1, E.n_t_knots - 1), u_t);
+    const double theta = inv_cdf(E.t_tab, E.t_tab + (size_t)E.n_t_knots * 2, E.t_guide[k], min(E.t_guide[k + 1] + 1, E.n_t_knots - 1), u_t);
     const double phi = 6.283185307179586 * u_phi;
     d3 d = rotate(gn, phi, rotate(gt, theta, gn));
     d = d * (1.0 / sqrt(dot(d, d)));

@@ -118,6 +118,43 @@ std::string spec_ineligible(const HostScene& hs) {
   return "";
 }
 
+// zero / +-1 pattern of a frame's 12 entries (odw_kernels.hip: xf_comb): bits 0-11 entry != 0, 12-23 entry == +1,
+// 24-35 entry == -1 (rotation part only)
+unsigned long long xf_pattern(const double* m) {
+  unsigned long long w = 0;
+  for (int i = 0; i < 12; ++i) {
+    if (m[i] != 0.0) w |= 1ull << i;
+    if (i % 4 != 3 && m[i] == 1.0) w |= 1ull << (12 + i);
+    if (i % 4 != 3 && m[i] == -1.0) w |= 1ull << (24 + i);
+  }
+  return w;
+}
+
+// The structure of a table source as one word: what `struct SpecSource` says (0 = no such source).  Kept by the
+// context for the source it holds (source_key) and for the kernel it has bound (spec_source_key): a launch that
+// generates its rays runs a kernel compiled against its source's structure, and a source of another structure makes
+// the next launch bind again -- the path a changed scene takes.  Sizes and values are not part of it: one kernel
+// serves a sweep over the source's parameters too.
+enum : uint64_t { kSrcEnabled = 1ull << 63, kSrcSingleRow = 1ull << 40, kSrcPhiGuide = 1ull << 41, kSrcFiniteFocal = 1ull << 42 };
+uint64_t spec_source_key(const double* frame, int n_t_rows, bool phi_guide, bool finite_focal) {
+  return kSrcEnabled | xf_pattern(frame) | (n_t_rows == 1 ? kSrcSingleRow : 0) | (phi_guide ? kSrcPhiGuide : 0) |
+         (finite_focal ? kSrcFiniteFocal : 0);
+}
+uint64_t spec_source_key(const DeviceSource& d) {
+  return spec_source_key(d.m, d.n_t_rows, d.phi_guide != nullptr, d.finite_focal != 0);
+}
+std::string spec_source_text(uint64_t key) {
+  if (!(key & kSrcEnabled)) return "";
+  auto fb = [&](uint64_t bit) { return (key & bit) ? "true" : "false"; };
+  char xf[32];
+  snprintf(xf, sizeof xf, "0x%llxull", (unsigned long long)(key & 0xfffffffffull));
+  return std::string("struct SpecSource {\n  static constexpr bool enabled = true;\n") +
+         "  static constexpr bool single_row = " + fb(kSrcSingleRow) + ";\n" +
+         "  static constexpr bool phi_guide = " + fb(kSrcPhiGuide) + ";\n" +
+         "  static constexpr bool finite_focal = " + fb(kSrcFiniteFocal) + ";\n" +
+         "  static constexpr unsigned long long xf = " + xf + ";\n};\n#define ODW_SPEC_SOURCE SpecSource\n";
+}
+
 // `struct Spec` of the uploaded scene (tables of scene_host_tables / compute_boxes).  The text is the
 // cache key: equal text = equal kernel.
 std::string spec_text(const HostScene& hs, int n_samplers) {
@@ -132,14 +169,7 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
     const int facemask = (flags[p] >> ODW_FACEMASK_SHIFT) & 0xff;
     // (an empty box is a matter of values: such a primitive stays, its box culls it)
     dead[p] = facemask == 0;
-    const double* m = &hs.prim_f64[16 * (size_t)p];
-    unsigned long long w = 0;
-    for (int i = 0; i < 12; ++i) {
-      if (m[i] != 0.0) w |= 1ull << i;
-      if (i % 4 != 3 && m[i] == 1.0) w |= 1ull << (12 + i);
-      if (i % 4 != 3 && m[i] == -1.0) w |= 1ull << (24 + i);
-    }
-    xf[p] = w;
+    xf[p] = xf_pattern(&hs.prim_f64[16 * (size_t)p]);
   }
   // primitives with the same box: equal sets {p} + {q : p must lie inside q} (compute_boxes cuts p's box by
   // the boxes of those q), one set per clause of a trimming list of several (compute_boxes: the union over the
@@ -177,6 +207,7 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
   std::string s;
   s += "struct Spec {\n  static constexpr bool enabled = true;\n";
   s += "  static constexpr int N = " + std::to_string(n) + ";\n";
+  s += "  static constexpr int NG = " + std::to_string(ng) + ";\n";
   s += table("int", "type", n, type.data(), fi) + table("int", "group", n, group.data(), fi) +
        table("int", "flags", n, flags.data(), fi) + table("int", "cond_word", n, condw.data(), fi) +
        table("bool", "dead", n, dead.data(), fi) + table("int", "box_of", n, box_of.data(), fi) +
@@ -381,7 +412,9 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   hipDeviceProp_t prop;
   HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
   const std::string arch = prop.gcnArchName;
-  const std::string text = spec_text(ctx->hs, ctx->n_samplers) + (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n" : variant == kSpecPower ? "#define ODW_SPEC_POWER true\n" : "");
+  // (the BATCH variant takes its rays from the batch's buffer, odw_batch_rays_kernel: never compiled against a source)
+  const std::string text = spec_text(ctx->hs, ctx->n_samplers) + (variant == kSpecBatch ? "" : spec_source_text(ctx->spec_source_key)) +
+                           (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n" : variant == kSpecPower ? "#define ODW_SPEC_POWER true\n" : "");
   const char* xo = getenv("ODW_SPEC_OPTS");
   const std::string jkey = arch + "|" + (xo ? xo : "") + "|" + text;
   const std::string key = std::to_string(ctx->device) + "|" + jkey;

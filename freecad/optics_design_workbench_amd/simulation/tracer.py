@@ -207,14 +207,20 @@ class Tracer:
     """dict(mode: 0 generic (in 'auto' mode: not compiled yet) / 1 structure / 2 auto -- of the kernel the next eligible launch runs,
     seconds: compile time of it (0 from a cache), cache: 0 compiled now / 1 process / 2 disk,
     power: the same as `mode` for launches that fill the power plane -- they run a variant of the compiled kernel of
-    their own, bound by the first such launch (`odw_compiled_power_info`))"""
+    their own, bound by the first such launch (`odw_compiled_power_info`),
+    source: non-zero if the bound kernel generates its rays compiled against the source's structure, 0 if it is the
+    source-free kernel (explicit rays, batches, compileScene before setSource) or none (`odw_compiled_source_info`))"""
     f = self._lib.odw_compiled_info
     f.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_int32)]
     b, sec, hit = C.c_int32(0), C.c_double(0), C.c_int32(0)
     self._chk(f(self._ctx, C.byref(b), C.byref(sec), C.byref(hit)), 'odw_compiled_info')
     pw = C.c_int32(0)
     self._chk(self._lib.odw_compiled_power_info(self._ctx, C.byref(pw)), 'odw_compiled_power_info')
-    return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value))
+    key = C.c_uint64(0)
+    f = self._lib.odw_compiled_source_info
+    f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    self._chk(f(self._ctx, C.byref(key)), 'odw_compiled_source_info')
+    return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value), source=int(key.value))
 
   def setSurfaceSeed(self, seed):
     """Philox key of the stochastic-surface draws in traceRays launches"""

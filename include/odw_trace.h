@@ -381,6 +381,10 @@ const char* odw_last_error(const odw_ctx* ctx); /* NULL ctx: global message */
 int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* scene);
 /* replaces PointSourceProxy._getVrv/_rvArgs result, point_source.py:277-386 */
 int odw_upload_source(odw_ctx* ctx, const odw_source_desc* source);
+/* the same source without the search guides odw_upload_source builds over its tables: every inversion is a
+ * plain binary search over the whole table.  The same knots are found and the same rays come out, more
+ * slowly -- for verifying the guides, not for production.  Replaces nothing of the reference.              */
+int odw_upload_source_unguided(odw_ctx* ctx, const odw_source_desc* source);
 /* replaces SurfaceSourceProxy._generateRays(mode='true'), surface_source.py:519-553;
  * the most recently uploaded source (point or surface) feeds odw_trace      */
 int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* source);
@@ -586,6 +590,15 @@ int odw_compiled_power_info(odw_ctx* ctx, int32_t* bound);
  * outside the flat kernel's domain.                                          */
 int odw_compile_check(const odw_scene_desc* scene, const odw_limits* limits, int32_t mode, const char* arch,
                       char* header_out, uint64_t header_capacity, uint64_t* code_bytes);
+/* The same for the kernel a launch binds that generates its rays from `source`: the header then carries the
+ * source's structure (one theta table or one per phi cell, the frame's zero / +-1 pattern, focal length finite
+ * or not) and ray generation is compiled against it.  source NULL: odw_compile_check.                      */
+int odw_compile_check_source(const odw_scene_desc* scene, const odw_limits* limits, int32_t mode, const char* arch,
+                             const odw_source_desc* source, char* header_out, uint64_t header_capacity,
+                             uint64_t* code_bytes);
+/* structure: non-zero if the bound compiled kernel generates rays compiled against the structure of the
+ * context's source (the word says which), 0 if it is the source-free kernel or none is bound              */
+int odw_compiled_source_info(odw_ctx* ctx, uint64_t* structure);
 /* v10: what odw_upload_scene + the first launch prepare -- validation, host
  * tables, boxes, the choice among flat loop / grid / binary tree / eight-wide
  * tree and their construction -- WITHOUT a device (the tables go to host memory).
@@ -595,6 +608,15 @@ int odw_compile_check(const odw_scene_desc* scene, const odw_limits* limits, int
  * binary tree, 3 eight-wide tree; sizes [6]: primitives, tree nodes, grid
  * cells, grid items, LDS bytes of a grid block, dead primitives.            */
 int odw_build_check(const odw_scene_desc* scene, const odw_limits* limits, int32_t* structure, uint64_t* sizes);
+/* no device needed: the segment slopes the library stores behind the (cdf, edge)
+ * pairs of every inverse-CDF table it uploads (sources, surface samplers, the
+ * surface source), slopes[t * n_knots + j] = (edges[j+1] - edges[j]) /
+ * (cdf[t][j+1] - cdf[t][j]), 0 for the last knot of a table -- numpy.interp's
+ * own slope, bit for bit; the kernels read it instead of dividing per ray.
+ * cdf [n_tables * n_knots], edges [n_knots], slopes [n_tables * n_knots].
+ * Replaces nothing of the reference (numpy computes the slope per sample).
+ * (An entry point more, no descriptor or row layout changed: still v12.)      */
+int odw_table_slopes(const double* cdf, const double* edges, int32_t n_tables, int32_t n_knots, double* slopes);
 
 /* ---- batches: many scenes of ONE structure in one launch (v9) -----------
  * Replaces the loop of a parameter sweep (examples/1-getting-started/

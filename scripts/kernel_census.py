@@ -4,8 +4,9 @@ instruction classes of profiles/r03/valu_peak.json:
 
   python scripts/kernel_census.py lensesAndMirrors [out.json]
 
-The header of the scene is written by the library (odw_compile_check), the kernel source is compiled with hipcc
-to assembly with the options odw_spec.hip hands hiprtc.  The census is STATIC (one count per instruction of the
+The header of the scene is written by the library (odw_compile_check_source: the kernel a plain launch binds, its
+ray generation compiled against the project's source; ODW_CENSUS_SOURCE=0: the source-free kernel of explicit rays
+and batches), the kernel source is compiled with hipcc to assembly with the options odw_spec.hip hands hiprtc.  The census is STATIC (one count per instruction of the
 binary, hot and cold paths alike): bench.py uses it only to split the part of SQ_INSTS_VALU the hardware counters
 do not classify (everything but f64 fma / mul / add / transcendental, int32, int64, cvt) into compares,
 v_cndmask, moves and min / max."""
@@ -102,7 +103,10 @@ def main():
   out_path = sys.argv[2] if len(sys.argv) > 2 else None
   from freecad.optics_design_workbench_amd import _native, scenes
   proj = scenes.bakeProject(os.path.join(ROOT, 'tests', 'golden', 'scenes', scene + '.FCStd'))
-  header, code_bytes = _native.compile_check(proj.scene, proj.limits, 'structure')
+  # ODW_CENSUS_SOURCE=0: the source-free kernel (explicit rays, batches); default: the kernel a plain launch binds,
+  # its ray generation compiled against the project's source
+  with_source = os.environ.get('ODW_CENSUS_SOURCE', '1') != '0'
+  header, code_bytes = _native.compile_check(proj.scene, proj.limits, 'structure', source=proj.source if with_source else None)
   d = tempfile.mkdtemp()
   try:
     open(os.path.join(d, 'odw_spec.h'), 'w').write(header)
