@@ -984,6 +984,9 @@ int ph_bin_run(odw_ctx* ctx, const std::string& who, int32_t polar, const double
   const uint64_t m = ctx->ph_n;
   const uint64_t nbins = (uint64_t)(n_a - 1) * (uint64_t)(n_b - 1);
   const uint64_t words = weighted ? 2 * nbins : nbins;            // [counts | power]
+  // (the batched chain bins from the same two buffers and uploads its edges only when they change: they are not its
+  //  edges any more -- a per-segment histogram between two groups of a sweep left the next group binned by these)
+  ctx->phb_edges_host.clear();
   if ((rc = upload(ctx, ctx->ph_edges, edges_a, (size_t)n_a * sizeof(double)))) return rc;
   if ((rc = ensure(ctx, ctx->ph_edges_b, (size_t)n_b * sizeof(double)))) return rc;
   HIPCHK(ctx, hipMemcpyAsync(ctx->ph_edges_b.p, edges_b, (size_t)n_b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));

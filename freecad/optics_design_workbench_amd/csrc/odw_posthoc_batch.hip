@@ -22,7 +22,9 @@ namespace {
 
 constexpr uint64_t kPhbRowsRoom = 4104, kPhbBinsRoom = 4096;   // sample rows / histogram bins per scene the buffers hold from the start
 constexpr uint32_t kPhbCand = 2048;        // median candidates per coordinate the pick kernel ranks; more (a cloud piled up on
-                                           // one value): that coordinate is sorted (sync entry points) / the scene reported
+                                           // one value): that coordinate is sorted (sync entry points:
+                                           // test_gpu_medians.py::test_batched_medians_step_by_step_equal_numpy) / the scene
+                                           // reported (::test_enqueued_chain_reports_the_piled_scene_and_serves_the_others)
 enum : uint32_t { PHB_SLOW_X = 1u, PHB_SLOW_Y = 2u, PHB_BAD_HIST = 4u, PHB_SAMPLE_CUT = 8u };
 
 struct PhbScene {
