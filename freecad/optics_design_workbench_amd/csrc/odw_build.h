@@ -104,7 +104,7 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
   hs.prim_i32.assign((size_t)n * 4, 0);
   for (int p = 0; p < n; ++p) {
     const int type = s->prim_type[p], group = s->prim_group[p];
-    if (type < ODW_PRIM_BOX || type > ODW_PRIM_PARABOLOID) return refuse(err, ODW_ERR_UNSUPPORTED, "unknown primitive type");
+    if (type < ODW_PRIM_BOX || type > ODW_PRIM_ELLIPSOID) return refuse(err, ODW_ERR_UNSUPPORTED, "unknown primitive type");
     if (group < 0 || group >= s->n_groups) return refuse(err, ODW_ERR_INVALID, "primitive group out of range");
     const int off = s->prim_cond_off[p], cnt = s->prim_cond_off[p + 1] - off;
     if (off < 0 || cnt < 0 || cnt > 255 || off + cnt > s->n_conds)
@@ -144,6 +144,15 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
         double* par = &hs.prim_f64[16 * (size_t)p + 12];
         if (!(par[0] > 0) || !(par[1] > 0)) return refuse(err, ODW_ERR_INVALID, "paraboloid: focal length and height must be positive");
         par[2] = 2.0 * std::sqrt(par[0] * par[1]);            // rim radius at z = H
+      }
+      if (type == ODW_PRIM_ELLIPSOID) {
+        // one face and no caps: a descriptor that asks for faces 1 or 2 (the caps of the other quadrics) describes a
+        // solid this kind is not
+        if (((s->prim_flags[p] >> ODW_FACEMASK_SHIFT) & 0xff) & ~1)
+          return refuse(err, ODW_ERR_UNSUPPORTED, "ellipsoid: one face (bit 0 of the face mask), it has no caps");
+        const double* par = &hs.prim_f64[16 * (size_t)p + 12];
+        for (int k = 0; k < 3; ++k)
+          if (!(par[k] > 0) || !std::isfinite(par[k])) return refuse(err, ODW_ERR_INVALID, "ellipsoid: the three radii must be positive");
       }
     }
     hs.prim_i32[4 * p] = type;
@@ -223,7 +232,10 @@ void local_bounds(int type, const double* par, double lo[3], double hi[3]) {
       lo[0] = lo[1] = -r; hi[0] = hi[1] = r; lo[2] = 0; hi[2] = par[1];
       break;
     }
-    default: {
+    case ODW_PRIM_ELLIPSOID:
+      for (int i = 0; i < 3; ++i) { lo[i] = -par[i]; hi[i] = par[i]; }
+      break;
+    default: {  // torus
       const double r = par[0] + par[1];
       lo[0] = lo[1] = -r; hi[0] = hi[1] = r; lo[2] = -par[1]; hi[2] = par[1];
     }
@@ -991,6 +1003,18 @@ void compute_boxes(HostScene& hs, double dist_tol, std::vector<Box>& boxes) {
   }
 }
 
+// A scene the flat loop would take but for its rare quadrics (paraboloids, ellipsoids: build_accel gives it a grid and a
+// tree, since the generic flat kernel leaves their code out): a kernel compiled against it needs neither
+bool flat_but_for_rare_quadrics(const HostScene& hs, int flat_limit) {
+  bool rare = false;
+  for (int p = 0; p < hs.n_prims; ++p) {
+    const int t = hs.prim_i32[4 * p];
+    if (t == ODW_PRIM_TRIANGLE) return false;
+    rare |= t == ODW_PRIM_PARABOLOID || t == ODW_PRIM_ELLIPSOID;
+  }
+  return rare && hs.n_prims <= flat_limit;
+}
+
 // The structures a scene is traced with: none for analytic scenes of up to flat_limit primitives (the flat kernels),
 // else the grid where the scene takes one, and the trees.  hs and boxes as compute_boxes(hs, dist_tol, boxes) left them.
 int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, int flat_limit, const BuildOptions& opt,
@@ -998,13 +1022,15 @@ int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, in
   A = SceneAccel();
   const int n = hs.n_prims;
   const std::vector<char>& dead = hs.dead;
-  bool has_triangles = false, has_paraboloids = false;
+  bool has_triangles = false, has_paraboloids = false, has_ellipsoids = false;
   for (int p = 0; p < n; ++p) {
     has_triangles |= hs.prim_i32[4 * p] == ODW_PRIM_TRIANGLE;
     has_paraboloids |= hs.prim_i32[4 * p] == ODW_PRIM_PARABOLOID;
+    has_ellipsoids |= hs.prim_i32[4 * p] == ODW_PRIM_ELLIPSOID;
   }
-  // (triangles are only known to the BVH kernels, paraboloids to the BVH and grid kernels)
-  if (n <= flat_limit && !has_triangles && !has_paraboloids) return ODW_OK;
+  // (triangles are only known to the BVH kernels, paraboloids to the BVH and grid kernels, ellipsoids to the binary
+  //  tree and the grid kernel: beside facets they take the binary tree, not the mesh kernel's eight-wide one)
+  if (n <= flat_limit && !has_triangles && !has_paraboloids && !has_ellipsoids) return ODW_OK;
   if (!has_triangles) build_grid(hs, boxes, A);
   // float32 traversal boxes: enlarge by what float rounding of the ray origin
   // and of the slab arithmetic can cost (see ray_box_f32 in odw_kernels.hip)
@@ -1048,7 +1074,7 @@ int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, in
   for (int p = 0; p < n; ++p) prim_solid[p] = hs.prim_i32[4 * (size_t)p + 2] >> ODW_SOLID_SHIFT;
   WideBvh wide(b.nodes, b.order, prim_solid);
   std::vector<float> out_normal;
-  if (has_triangles && mesh_kernel) {
+  if (has_triangles && mesh_kernel && !has_ellipsoids) {
     // normal cones for rays inside STRICTLY convex tessellated solids (ODW_FLAG_STRICTLY_CONVEX; node words 24..31;
     // ODW_MESH_CONES=0: none).  The margin: a ray that starts on a facet whose edges are all closed is out of that facet's
     // area by 1e-9 of its edges at most; every point of a facet lies on or below the plane of every other facet up to

@@ -452,7 +452,7 @@ int presort_rays(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed) {
 // whatever else was built for it -- the variant this launch needs must be bound, for the scene as it is now.  Segment
 // rows are written by the flat and tree kernels only; stochastic surfaces are unknown to the grid kernel: such
 // launches fall back to the trees, which every scene with a grid has too.  (Batches hold scenes without structures:
-// compiled or flat.)
+// compiled or flat; or scenes that have structures only because of their paraboloids or ellipsoids: compiled.)
 enum class TraceKernel { flat = kAccelFlat, grid = kAccelGrid, tree = kAccelTree, mesh = kAccelWide, compiled };
 
 TraceKernel choose_kernel(const odw_ctx* ctx, uint32_t flags, bool batch) {
@@ -507,7 +507,8 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   std::memset(&P.batch, 0, sizeof P.batch);
   if (batch) {
     // scenes of one structure side by side: flat kernels only (the scene the context holds is scene 0 of the batch)
-    if (P.scene.n_nodes || P.grid.nx > 0 || ctx->n_samplers > 0 || explicit_rays || (flags & ODW_TRACE_RECORD_SEGMENTS))
+    const bool rare = flat_but_for_rare_quadrics(ctx->hs, ctx->flat_limit);
+    if (((P.scene.n_nodes || P.grid.nx > 0) && !rare) || ctx->n_samplers > 0 || explicit_rays || (flags & ODW_TRACE_RECORD_SEGMENTS))
       return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: batches are traced by the flat kernels (analytic scenes of up to 64 "
                                             "primitives, no stochastic surfaces, no segment rows)");
     flags &= ~(uint32_t)(ODW_TRACE_HISTOGRAM | ODW_TRACE_POWER_HISTOGRAM);   // (one histogram cannot serve several scenes)
@@ -574,6 +575,9 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     }
   }
   const TraceKernel kernel = choose_kernel(ctx, flags, batch);   // (after the two bindings above: they decide `compiled`)
+  if (batch && kernel != TraceKernel::compiled && flat_but_for_rare_quadrics(ctx->hs, ctx->flat_limit))
+    return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: a batch with paraboloids or ellipsoids needs the kernel compiled against the scene, "
+                                          "which is not bound (odw_compile_scene: ODW_COMPILE_STRUCTURE)");
   const bool use_spec = kernel == TraceKernel::compiled, use_grid = kernel == TraceKernel::grid, use_mesh = kernel == TraceKernel::mesh,
              use_tree = kernel == TraceKernel::tree;
   // Rays per hand-out unit.  A launch should hold many chunks per resident wave: with about one each -- 1e7 rays in
@@ -1269,8 +1273,11 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   std::vector<double> pf((size_t)n * 16);
   std::vector<int32_t> pi((size_t)n * 4);
   for (int p = 0; p < n; ++p) {
-    if (s->prim_type[p] < ODW_PRIM_BOX || s->prim_type[p] > ODW_PRIM_PARABOLOID)
+    if (s->prim_type[p] < ODW_PRIM_BOX || s->prim_type[p] > ODW_PRIM_ELLIPSOID)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: unknown primitive kind");
+    // (the emitter kernel carries no ellipsoid code: neither an emitting face nor an operand of a trimming list)
+    if (s->prim_type[p] == ODW_PRIM_ELLIPSOID)
+      return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: ellipsoids are not built, neither as emitting faces nor as trimming operands");
     const int off = s->prim_cond_off[p], cnt = s->prim_cond_off[p + 1] - off;
     if (s->prim_type[p] == ODW_PRIM_TRIANGLE && cnt != 0)
       return fail(ctx, ODW_ERR_INVALID, "surface source: facets cannot carry trimming conditions");
@@ -1293,7 +1300,7 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   }
   if (!clauses_marked(s->prim_cond_off, n, cond))
     return fail(ctx, ODW_ERR_INVALID, "surface source: a trimming list of several clauses must mark its first condition too");
-  static const int n_faces_of[7] = {6, 1, 3, 3, 1, 1, 0};     // (paraboloid faces do not emit: rejected below)
+  static const int n_faces_of[8] = {6, 1, 3, 3, 1, 1, 0, 0};  // (paraboloid faces do not emit: rejected below; ellipsoids: above)
   std::vector<int32_t> fi((size_t)s->n_faces * 2);
   std::vector<double> fc((size_t)s->n_faces + 1, 0.0);
   double total = 0;
@@ -1533,9 +1540,14 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
   int rc = odw_upload_scene(ctx, &scenes[0]);
   if (rc) return rc;
   if ((rc = build_bvh(ctx))) return rc;
-  if (ctx->P.scene.n_nodes || ctx->P.grid.nx > 0)
-    return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: batches are traced by the flat kernels (analytic scenes of up to 64 primitives)");
   const bool compiled = ctx->compile_mode != ODW_COMPILE_OFF && spec_ineligible(ctx->hs).empty();
+  // (a scene that has structures only because of its paraboloids or ellipsoids: the generic flat kernel does not know
+  //  them, the kernel compiled against the scene does -- such a batch needs ODW_COMPILE_STRUCTURE, which binds it before
+  //  the launch)
+  const bool rare_compiled = flat_but_for_rare_quadrics(ctx->hs, ctx->flat_limit) && compiled && ctx->compile_mode == ODW_COMPILE_STRUCTURE;
+  if ((ctx->P.scene.n_nodes || ctx->P.grid.nx > 0) && !rare_compiled)
+    return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: batches are traced by the flat kernels (analytic scenes of up to 64 primitives; "
+                                          "with paraboloids or ellipsoids: by the compiled one, ODW_COMPILE_STRUCTURE)");
   const std::string text0 = compiled ? spec_text(ctx->hs, ctx->n_samplers) : std::string();
   const size_t n = (size_t)ctx->P.scene.n_prims;
   // one block of doubles per scene: prim_f64 (16 n) | prim_hdr (8 n) | group_f64 (4 x 64) | group_gdir (3 x 64)

@@ -324,10 +324,24 @@ __device__ __forceinline__ void make_ray(csource s, double t_or_r, double phi,
 }
 
 // ----------------------------------------------------------- primitives
-// PARAB: paraboloids are known to the BVH and grid kernels only (the flat kernel of the small
-// benchmark scenes is sensitive to every instruction in its loop: their branch cost it 1.1 %)
-template <bool PARAB, class PP>
+// RQ: the rare quadrics an instantiation knows (bit 0 paraboloids, bit 1 ellipsoids).  Paraboloids are known to
+// the BVH, grid and mesh kernels only (the flat kernel of the small benchmark scenes is sensitive to every
+// instruction in its loop: their branch cost it 1.1 %), ellipsoids to the BVH and grid kernels; a compiled kernel
+// knows what its scene holds (Spec::rare()).
+#define ODW_RQ_PARAB 1
+#define ODW_RQ_ELLIPSOID 2
+#define ODW_RQ_ALL 3
+template <int RQ, class PP>
 __device__ __forceinline__ double prim_sdist(int type, PP par, d3 p) {
+  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0;
+  if (ELL && type == ODW_PRIM_ELLIPSOID) {
+    // q = sum (x_i / r_i)^2 against 1 over the length of its gradient: the distance to first order, as for the
+    // paraboloid (at the centre the gradient vanishes: the floor keeps the answer "deep inside", not NaN)
+    const double sx = frcp(par[0]), sy = frcp(par[1]), sz = frcp(par[2]);
+    const double ux = p.x * sx, uy = p.y * sy, uz = p.z * sz;
+    const double gx = ux * sx, gy = uy * sy, gz = uz * sz;
+    return (ux * ux + uy * uy + uz * uz - 1.0) * 0.5 * frsqrt(fmax(gx * gx + gy * gy + gz * gz, 1e-300));
+  }
   if (PARAB && type == ODW_PRIM_PARABOLOID) {
     // x^2 + y^2 - 4 f z over the length of its gradient: the distance to first order
     const double r2 = p.x * p.x + p.y * p.y;
@@ -432,7 +446,7 @@ struct SceneView {    // constant-address-space views of the scene tables
 // would replace a running minimum -- the trim by the other operands of a
 // boolean (cond list), then bookkeeping of the two running minima (nearest of
 // all / nearest whose group is not the current medium).
-template <bool PARAB = true>
+template <int RQ = ODW_RQ_ALL>
 __device__ __forceinline__ void consider(const SceneView& sv, Query& q, double t, int p, int face,
                                          int group, int cond_off, int cond_cnt) {
   if (!(t > q.tol && t < q.tmax)) return;
@@ -457,7 +471,7 @@ __device__ __forceinline__ void consider(const SceneView& sv, Query& q, double t
       if (!held) continue;
       const int qp = cond_operand(cw);
       cf64 pf = sv.prim_f64 + (size_t)qp * 16;
-      const double sd = prim_sdist<PARAB>(sv.prim_i32[4 * qp], pf + 12, xf_point(pf, gp));
+      const double sd = prim_sdist<RQ>(sv.prim_i32[4 * qp], pf + 12, xf_point(pf, gp));
       if (cw < 0 ? sd > q.tol : sd < -q.tol) {    // must be inside / must be outside
         if (!dnf) return;
         held = false;
@@ -471,7 +485,7 @@ __device__ __forceinline__ void consider(const SceneView& sv, Query& q, double t
 
 // the same for primitive PI of a compiled scene: group and trimming list are constants, the list is
 // unrolled, every operand's frame product skips its zero terms.  trim_all: the literals C..END-1 (one clause)
-template <bool PARAB, class SPEC, int C, int END>
+template <int RQ, class SPEC, int C, int END>
 __device__ __forceinline__ bool trim_all(const SceneView& sv, const Query& q, d3 gp) {
   if constexpr (C >= END) {
     return true;
@@ -479,10 +493,10 @@ __device__ __forceinline__ bool trim_all(const SceneView& sv, const Query& q, d3
     constexpr int cw = SPEC::cond(C);
     constexpr int qp = cond_operand(cw);
     cf64 pf = sv.prim_f64 + (size_t)qp * 16;
-    const double sd = prim_sdist<PARAB>(SPEC::type(qp), pf + 12, xf_point_nz<SPEC::xf(qp)>(pf, gp));
+    const double sd = prim_sdist<RQ>(SPEC::type(qp), pf + 12, xf_point_nz<SPEC::xf(qp)>(pf, gp));
     if (cw < 0) { if (sd > q.tol) return false; }     // must be inside
     else { if (sd < -q.tol) return false; }           // must be outside
-    return trim_all<PARAB, SPEC, C + 1, END>(sv, q, gp);
+    return trim_all<RQ, SPEC, C + 1, END>(sv, q, gp);
   }
 }
 // end of the clause that begins at C: the next word that opens one, or END
@@ -494,17 +508,17 @@ __host__ __device__ constexpr int clause_end(int c, int end) {
 }
 // the list C..END-1: an OR of unrolled ANDs, resolved at compile time, left at the first clause that holds (a plain
 // conjunction is one clause: trim_all of the whole list, the code it always was)
-template <bool PARAB, class SPEC, int C, int END>
+template <int RQ, class SPEC, int C, int END>
 __device__ __forceinline__ bool trim_ok(const SceneView& sv, const Query& q, d3 gp) {
   constexpr int E = clause_end<SPEC>(C, END);
   if constexpr (E >= END) {
-    return trim_all<PARAB, SPEC, C, END>(sv, q, gp);
+    return trim_all<RQ, SPEC, C, END>(sv, q, gp);
   } else {
-    if (trim_all<PARAB, SPEC, C, E>(sv, q, gp)) return true;
-    return trim_ok<PARAB, SPEC, E, END>(sv, q, gp);
+    if (trim_all<RQ, SPEC, C, E>(sv, q, gp)) return true;
+    return trim_ok<RQ, SPEC, E, END>(sv, q, gp);
   }
 }
-template <bool PARAB, class SPEC, int PI>
+template <int RQ, class SPEC, int PI>
 __device__ __forceinline__ void consider_spec(const SceneView& sv, Query& q, double t, int face) {
   if (!(t > q.tol && t < q.tmax)) return;
   // (compiled kernels keep (primitive, face) as ONE word, primitive << 8 | face, in the `face` member: the order of the
@@ -521,9 +535,9 @@ __device__ __forceinline__ void consider_spec(const SceneView& sv, Query& q, dou
 #undef ODW_BETTER
   if (!cand_any && !cand_oth) return;
   if constexpr (SPEC::cond_cnt(PI) > 0) {
-    if (!trim_ok<PARAB, SPEC, SPEC::cond_off(PI), SPEC::cond_off(PI) + SPEC::cond_cnt(PI)>(sv, q, q.start + q.dn * t)) return;
+    if (!trim_ok<RQ, SPEC, SPEC::cond_off(PI), SPEC::cond_off(PI) + SPEC::cond_cnt(PI)>(sv, q, q.start + q.dn * t)) return;
 #if ODW_DOUBLE == 5
-    if (!trim_ok<PARAB, SPEC, SPEC::cond_off(PI), SPEC::cond_off(PI) + SPEC::cond_cnt(PI)>(sv, q, q.start + q.dn * opq(t))) return;
+    if (!trim_ok<RQ, SPEC, SPEC::cond_off(PI), SPEC::cond_off(PI) + SPEC::cond_cnt(PI)>(sv, q, q.start + q.dn * opq(t))) return;
 #endif
   }
   if (cand_any) { q.any.t = t; q.any.face = key; q.cut = fmin(q.tmax, t + 2.0 * q.tol); }
@@ -562,9 +576,10 @@ __device__ __forceinline__ void cand_min2(Cands& c, double t, int f) {
 // loop must stay inside the instruction cache).
 // SPEC / PI: primitive PI of a compiled scene -- the caller passes its constants as p, type, group,
 // flags, cond_word, so everything that depends on them folds
-template <bool PARAB = true, class SPEC = NoSpec, int PI = 0>
+template <int RQ = ODW_RQ_ALL, class SPEC = NoSpec, int PI = 0>
 __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, int p, int type, int group,
                                                int flags, int cond_word) {
+  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0;
   cf64 pf = sv.prim_f64 + (size_t)p * 16;
   const int cond_off = cond_word & 0xffffff, cond_cnt = (cond_word >> 24) & 0xff;
   const int fmask = (flags >> ODW_FACEMASK_SHIFT) & 0xff;
@@ -718,6 +733,18 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       { const bool w_ = (bool)((int)((fmask & 2) != 0) & (int)(R1 > 0) & (int)(xa * xa + ya * ya <= (R1 + tol) * (R1 + tol))); c.t2 = w_ ? ta : c.t2; c.f2 = w_ ? 1 : c.f2; }
       { const bool w_ = (bool)((int)((fmask & 4) != 0) & (int)(R2 > 0) & (int)(xb * xb + yb * yb <= (R2 + tol) * (R2 + tol))); c.t3 = w_ ? tb : c.t3; c.f3 = w_ ? 2 : c.f3; }
     }
+  } else if (ELL && type == ODW_PRIM_ELLIPSOID) {
+    // the unit sphere of the scaled frame: o' = o / r, d' = d / r component by component; t stays a length along
+    // the ray (d' is not a unit vector: the general solver).  Both roots with face 0, as for the sphere.
+    if (fmask & 1) {
+      const double sx = frcp(par[0]), sy = frcp(par[1]), sz = frcp(par[2]);
+      const d3 os = mk(o.x * sx, o.y * sy, o.z * sz), ds = mk(d.x * sx, d.y * sy, d.z * sz);
+      double t0, t1;
+      if (quad_roots(dot(ds, ds), dot(os, ds), dot(os, os) - 1.0, t0, t1) == 2) {
+        c.t0 = t0;
+        c.t1 = t1;
+      }
+    }
   } else {  // torus
     if (!(fmask & 1)) return;
     const double R1 = par[0], R2 = par[1];
@@ -829,7 +856,7 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       constexpr int ty = SPEC::type(PI), fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
       constexpr bool quadric = ty == ODW_PRIM_CYLINDER || ty == ODW_PRIM_CONE || ty == ODW_PRIM_PARABOLOID;
       constexpr bool pair = ty == ODW_PRIM_BOX || (fm & 1) != 0;      // box: entry / exit face; else the surface's two roots
-      constexpr bool caps = ty != ODW_PRIM_BOX && ty != ODW_PRIM_SPHERE;
+      constexpr bool caps = ty != ODW_PRIM_BOX && ty != ODW_PRIM_SPHERE && ty != ODW_PRIM_ELLIPSOID;
       if constexpr (pair) {
         ODW_PICK(c.t0, c.f0)
         ODW_PICK(c.t1, c.f1)
@@ -843,27 +870,27 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     ODW_PICK(c.t3, c.f3)
     }
 #undef ODW_PICK
-    if constexpr (SPEC::enabled) consider_spec<PARAB, SPEC, PI>(sv, q, bt, bf);
-    else consider<PARAB>(sv, q, bt, p, bf, group, 0, 0);
+    if constexpr (SPEC::enabled) consider_spec<RQ, SPEC, PI>(sv, q, bt, bf);
+    else consider<RQ>(sv, q, bt, p, bf, group, 0, 0);
   } else if constexpr (SPEC::enabled) {
     // (a sphere has two candidates; the trimming code exists once per candidate slot)
     // (faces that the boolean left nothing of produce no candidate: their slots are not looked at)
     constexpr int fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
     constexpr bool quadric = SPEC::type(PI) == ODW_PRIM_CYLINDER || SPEC::type(PI) == ODW_PRIM_CONE || SPEC::type(PI) == ODW_PRIM_PARABOLOID;
     if constexpr (!quadric || (fm & 1) != 0) {
-      consider_spec<PARAB, SPEC, PI>(sv, q, c.t0, c.f0);
-      consider_spec<PARAB, SPEC, PI>(sv, q, c.t1, c.f1);
+      consider_spec<RQ, SPEC, PI>(sv, q, c.t0, c.f0);
+      consider_spec<RQ, SPEC, PI>(sv, q, c.t1, c.f1);
     }
-    if constexpr (SPEC::type(PI) != ODW_PRIM_SPHERE) {
-      if constexpr (!quadric || (fm & 2) != 0) consider_spec<PARAB, SPEC, PI>(sv, q, c.t2, c.f2);
-      if constexpr (!quadric || (fm & 4) != 0) consider_spec<PARAB, SPEC, PI>(sv, q, c.t3, c.f3);
+    if constexpr (SPEC::type(PI) != ODW_PRIM_SPHERE && SPEC::type(PI) != ODW_PRIM_ELLIPSOID) {
+      if constexpr (!quadric || (fm & 2) != 0) consider_spec<RQ, SPEC, PI>(sv, q, c.t2, c.f2);
+      if constexpr (!quadric || (fm & 4) != 0) consider_spec<RQ, SPEC, PI>(sv, q, c.t3, c.f3);
     }
   } else {
 #pragma unroll 1
     for (int k = 0; k < 4; ++k) {
       const double t = k == 0 ? c.t0 : (k == 1 ? c.t1 : (k == 2 ? c.t2 : c.t3));
       const int f = k == 0 ? c.f0 : (k == 1 ? c.f1 : (k == 2 ? c.f2 : c.f3));
-      consider<PARAB>(sv, q, t, p, f, group, cond_off, cond_cnt);
+      consider<RQ>(sv, q, t, p, f, group, cond_off, cond_cnt);
     }
   }
 }
@@ -926,8 +953,9 @@ __device__ __forceinline__ d3 tri_normal(cf64 pf, const double* __restrict__ vn,
 }
 
 // outward normal of face `face` of primitive p at local point lp
-template <bool PARAB = true>
+template <int RQ = ODW_RQ_ALL>
 __device__ __forceinline__ d3 face_normal(int type, cf64 par, int face, d3 lp) {
+  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0;
   if (type == ODW_PRIM_BOX) {
     const double s = (face & 1) ? 1.0 : -1.0;
     const int a = face >> 1;
@@ -941,6 +969,12 @@ __device__ __forceinline__ d3 face_normal(int type, cf64 par, int face, d3 lp) {
     if (type == ODW_PRIM_CONE) k = (par[1] - par[0]) / par[2];
     // gradient of x^2 + y^2 - (R1 + k z)^2, or of x^2 + y^2 - 4 f z
     const d3 g = mk(lp.x, lp.y, (PARAB && type == ODW_PRIM_PARABOLOID) ? -2.0 * par[0] : -k * (par[0] + k * lp.z));
+    return g * frsqrt(dot(g, g));
+  }
+  if (ELL && type == ODW_PRIM_ELLIPSOID) {
+    // gradient of sum (x_i / r_i)^2
+    const double sx = frcp(par[0]), sy = frcp(par[1]), sz = frcp(par[2]);
+    const d3 g = mk(lp.x * sx * sx, lp.y * sy * sy, lp.z * sz * sz);
     return g * frsqrt(dot(g, g));
   }
   const double f = 1.0 - par[0] * frsqrt(lp.x * lp.x + lp.y * lp.y);
@@ -999,13 +1033,13 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
       }
       boxhit[PI] = in_box;
       if (in_box)
-        intersect_prim<SPEC::parab(), SPEC, PI>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
+        intersect_prim<SPEC::rare(), SPEC, PI>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
 #if ODW_DOUBLE == 3 || ODW_DOUBLE == 4 || ODW_DOUBLE == 12
       // (the second pass finds the candidates already known: consider_spec leaves early, before the trimming tests)
       if (in_box && SPEC::type(PI) == (ODW_DOUBLE == 3 ? ODW_PRIM_CYLINDER : (ODW_DOUBLE == 4 ? ODW_PRIM_BOX : ODW_PRIM_SPHERE))) {
         Query q2 = q;
         q2.start.x = opq(q.start.x);
-        intersect_prim<SPEC::parab(), SPEC, PI>(sv, q2, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
+        intersect_prim<SPEC::rare(), SPEC, PI>(sv, q2, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
         q.any = q2.any; q.oth = q2.oth;
       }
 #endif
@@ -1074,7 +1108,7 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
       // selected (ray.py:432,440): shrink the search like the reference does
       const double cut = fmin(q.tmax, q.any.t + 2.0 * q.tol);
       if (!ray_box(hdr, oi, inv, cut)) continue;
-      intersect_prim<false>(sv, q, p, type, g, flags, cond_word);
+      intersect_prim<0>(sv, q, p, type, g, flags, cond_word);
     }
   } else {
     // BVH traversal in float32 (culling only: leaves are intersected in
@@ -1163,7 +1197,7 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
         const int g = pi[1];
         if (((mask >> g) & 1) && (pi[2] >> ODW_SOLID_SHIFT) != skip_solid) {
           if (pi[0] == ODW_PRIM_TRIANGLE) intersect_tri(sv, q, p, g);
-          else intersect_prim<true>(sv, q, p, pi[0], g, pi[2], pi[3]);
+          else intersect_prim<ODW_RQ_ALL>(sv, q, p, pi[0], g, pi[2], pi[3]);
         }
       }
     }
@@ -1677,12 +1711,12 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
                                          int& skip, int& only, bool& alive) {
   constexpr int flags = SPEC::flags(PI), g = SPEC::group(PI);
   cf64 pf = sv.prim_f64 + (size_t)PI * 16;
-  d3 n = face_normal<SPEC::parab()>(SPEC::type(PI), pf + 12, face, xf_point_nz<SPEC::xf(PI)>(pf, point));
+  d3 n = face_normal<SPEC::rare()>(SPEC::type(PI), pf + 12, face, xf_point_nz<SPEC::xf(PI)>(pf, point));
   if constexpr ((flags & ODW_FLAG_FLIP_NORMAL) != 0) n = n * -1.0;
   n = xf_vec_t_nz<SPEC::xf(PI)>(pf, n);
 #if ODW_DOUBLE == 6
   {
-    d3 n2 = face_normal<SPEC::parab()>(SPEC::type(PI), pf + 12, face, xf_point_nz<SPEC::xf(PI)>(pf, mk(opq(point.x), point.y, point.z)));
+    d3 n2 = face_normal<SPEC::rare()>(SPEC::type(PI), pf + 12, face, xf_point_nz<SPEC::xf(PI)>(pf, mk(opq(point.x), point.y, point.z)));
     if constexpr ((flags & ODW_FLAG_FLIP_NORMAL) != 0) n2 = n2 * -1.0;
     n2 = xf_vec_t_nz<SPEC::xf(PI)>(pf, n2);
     n = n2.x == n.x ? n : n2;
@@ -1964,7 +1998,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         n = tri_normal(pf, sc.tri_nrm ? sc.tri_nrm + (size_t)prim * 9 : nullptr, point);
         if (pi[2] & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;
       } else {
-        n = face_normal<BVH>(pi[0], pf + 12, face, xf_point(pf, point));
+        n = face_normal<BVH ? ODW_RQ_ALL : 0>(pi[0], pf + 12, face, xf_point(pf, point));
         if (pi[2] & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;
         n = xf_vec_t(pf, n);
       }
@@ -2202,7 +2236,8 @@ __global__ __launch_bounds__(256) void odw_emit_kernel(const DeviceEmitter E, ui
         if (!ok) continue;
         const int qp = cond_operand(cw);
         const double* of = E.prim_f64 + (size_t)qp * 16;
-        const double sd = prim_sdist<true>(E.prim_i32[4 * qp], of + 12, xf_point(of, gp));
+        // (the emitter's tables hold no ellipsoid: odw_upload_surface_source refuses them)
+        const double sd = prim_sdist<ODW_RQ_PARAB>(E.prim_i32[4 * qp], of + 12, xf_point(of, gp));
         if (cw < 0 ? sd > E.dist_tol : sd < -E.dist_tol) ok = false;
       }
       if (!ok) continue;

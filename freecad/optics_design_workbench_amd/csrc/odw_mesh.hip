@@ -115,7 +115,7 @@ MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, 
           n = tri_normal(pf, sc.tri_nrm ? sc.tri_nrm + (size_t)prim * 9 : nullptr, point);
           if (pi[2] & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;
         } else {
-          n = face_normal<true>(pi[0], pf + 12, face, xf_point(pf, point));
+          n = face_normal<ODW_RQ_PARAB>(pi[0], pf + 12, face, xf_point(pf, point));
           if (pi[2] & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;
           n = xf_vec_t(pf, n);
         }
@@ -197,7 +197,8 @@ MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, 
 }
 
 // an analytic primitive listed in a leaf (a screen behind the mesh), a function of its own for the same reason:
-// intersect_prim<> holds every kind of primitive, the quartic of the torus included
+// intersect_prim<> holds every kind of primitive this kernel knows (build_accel hands scenes with an ellipsoid to the
+// binary tree), the quartic of the torus included
 struct MeshBest { Best any, oth; };
 __device__ __forceinline__
 MeshBest mesh_intersect_prim(ckargs kargs, d3 start, d3 dn, double tol, double tmax, int medium, Best any, Best oth, int p) {
@@ -213,7 +214,7 @@ MeshBest mesh_intersect_prim(ckargs kargs, d3 start, d3 dn, double tol, double t
   Query q;
   q.start = start; q.dn = dn; q.tol = tol; q.tmax = tmax; q.medium = medium; q.any = any; q.oth = oth;
   ci32 pi = sv.prim_i32 + 4 * p;
-  intersect_prim<true>(sv, q, p, pi[0], pi[1], pi[2], pi[3]);
+  intersect_prim<ODW_RQ_PARAB>(sv, q, p, pi[0], pi[1], pi[2], pi[3]);
   MeshBest r;
   r.any = q.any; r.oth = q.oth;
   return r;

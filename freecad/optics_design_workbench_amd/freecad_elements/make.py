@@ -66,6 +66,13 @@ def makeTorus(doc, name='Torus', radius1=10.0, radius2=2.0, **pl):
                        Angle1=-180.0, Angle2=180.0, Angle3=360.0, Placement=_placement(**pl))
 
 
+def makeEllipsoid(doc, name='Ellipsoid', radius1=2.0, radius2=4.0, radius3=0.0, angle1=-90.0, angle2=90.0, angle3=360.0, **pl):
+  """FreeCAD's Part::Ellipsoid with its own property names and defaults: semi-axes Radius2 along x, Radius3 (0: as
+  Radius2) along y, Radius1 along z (scene.geometry._primitive_of)"""
+  return doc.addObject('Part::Ellipsoid', name, Radius1=float(radius1), Radius2=float(radius2), Radius3=float(radius3),
+                       Angle1=float(angle1), Angle2=float(angle2), Angle3=float(angle3), Placement=_placement(**pl))
+
+
 def makeParaboloid(doc, name='Paraboloid', focalLength=10.0, height=5.0, **pl):
   """solid paraboloid of revolution x^2 + y^2 <= 4 f z, z <= height in its own frame (vertex at the
   origin, axis +z): the blank of a parabolic mirror.  FreeCAD has no such primitive (there it is the
@@ -162,7 +169,7 @@ def makeMesh(doc, vertices, triangles, vertexNormals=None, name='Mesh', **pl):
 
 
 def makeTessellated(doc, solid, segments=48, smooth=True, name=None):
-  """mesh of a primitive solid object (Part::Sphere / Cylinder / Cone / Torus / Box) at the same placement"""
+  """mesh of a primitive solid object (Part::Sphere / Ellipsoid / Cylinder / Cone / Torus / Box) at the same placement"""
   from ..scene import geometry
   node = geometry._primitive_of(solid)
   if node is None:

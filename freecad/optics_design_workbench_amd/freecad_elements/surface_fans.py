@@ -104,6 +104,8 @@ def _primitive_face_table(kind, params, to_world, dist_tol):
     faces[2] = FaceView((-rr, rr, -rr, rr), np.pi * rr * rr, lambda u, v: world([u, v, h]),
                         lambda u, v, x: np.hypot(u, v) <= rr + dist_tol, lambda u, v: wdir([0.0, 0.0, 1.0]),
                         lambda u, v: (wdir([1.0, 0.0, 0.0]), wdir([0.0, 1.0, 0.0])))
+  elif kind == geometry.ELLIPSOID:
+    raise geometry.UnsupportedGeometry('faces of an ellipsoid as fan grids are not built')
   else:
     raise geometry.UnsupportedGeometry(f'no fan grid for primitive kind {kind}')
   return faces
@@ -130,6 +132,14 @@ def _primitive_faces(kind, params, to_world, names, dist_tol):
 
 
 # ------------------------------------------------------------------ faces of boolean results
+def _ellipsoid_distance(q, p):
+  """first-order distance of the local point q from the ellipsoid of semi-axes p[:3] (negative inside): the rule of
+  the kernels' trimming tests"""
+  r = np.asarray(p[:3], float)
+  g = np.linalg.norm(q / (r * r))
+  return 0.5 * (np.sum((q / r)**2) - 1.0) / max(g, 1e-150)
+
+
 def _inside_primitive(fp, x, tol):
   """is the point inside the (closed) primitive, or within tol of its boundary"""
   m = fp.to_world.m
@@ -139,6 +149,8 @@ def _inside_primitive(fp, x, tol):
     return bool(np.all(q >= -tol) and np.all(q <= np.array(p[:3]) + tol))
   if k == geometry.SPHERE:
     return bool(np.linalg.norm(q) <= p[0] + tol)
+  if k == geometry.ELLIPSOID:
+    return bool(_ellipsoid_distance(q, p) <= tol)
   rho = np.hypot(q[0], q[1])
   if k == geometry.CYLINDER:
     return bool(rho <= p[0] + tol and -tol <= q[2] <= p[1] + tol)
@@ -160,6 +172,8 @@ def _strictly_inside_primitive(fp, x, tol):
     return bool(np.all(q > tol) and np.all(q < np.array(p[:3]) - tol))
   if k == geometry.SPHERE:
     return bool(np.linalg.norm(q) < p[0] - tol)
+  if k == geometry.ELLIPSOID:
+    return bool(_ellipsoid_distance(q, p) < -tol)
   rho = np.hypot(q[0], q[1])
   if k == geometry.CYLINDER:
     return bool(rho < p[0] - tol and tol < q[2] < p[1] - tol)

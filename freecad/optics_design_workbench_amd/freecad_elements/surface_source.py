@@ -59,6 +59,8 @@ def faceArea(kind, params, face):
   p = params
   if kind == geometry.PARABOLOID:
     raise geometry.UnsupportedGeometry('faces of a paraboloid as a surface source are not built')
+  if kind == geometry.ELLIPSOID:
+    raise geometry.UnsupportedGeometry('faces of an ellipsoid as a surface source are not built')
   if kind == geometry.BOX:
     a = face >> 1
     return p[(a + 1) % 3] * p[(a + 2) % 3]
@@ -131,6 +133,9 @@ def bakeSurfaceSource(doc, obj):
           facets.append(_meshFacets(obj, part, tree, container, subs))
           continue
         flat = geometry.flatten(tree, container)
+        if any(fp.kind == geometry.ELLIPSOID for fp in flat):
+          raise geometry.UnsupportedGeometry(f'{obj.Name}: faces of an ellipsoid as a surface source are not built ({part.Name}), '
+                                             f'nor faces trimmed by an ellipsoid')
         base = len(prims)
         for k, fp in enumerate(flat):
           fp.index = base + k

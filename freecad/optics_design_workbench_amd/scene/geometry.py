@@ -16,11 +16,11 @@ import numpy as np
 
 from .placement import Placement
 
-BOX, SPHERE, CYLINDER, CONE, TORUS, TRIANGLE, PARABOLOID = range(7)
-KIND_NAMES = ['box', 'sphere', 'cylinder', 'cone', 'torus', 'triangle', 'paraboloid']
+BOX, SPHERE, CYLINDER, CONE, TORUS, TRIANGLE, PARABOLOID, ELLIPSOID = range(8)
+KIND_NAMES = ['box', 'sphere', 'cylinder', 'cone', 'torus', 'triangle', 'paraboloid', 'ellipsoid']
 # (paraboloid: face 0 = the surface of revolution, face 2 = the cap at z = H as on cylinders and
 #  cones; there is no face 1)
-N_FACES = {BOX: 6, SPHERE: 1, CYLINDER: 3, CONE: 3, TORUS: 1, TRIANGLE: 1, PARABOLOID: 3}
+N_FACES = {BOX: 6, SPHERE: 1, CYLINDER: 3, CONE: 3, TORUS: 1, TRIANGLE: 1, PARABOLOID: 3, ELLIPSOID: 1}
 PARABOLOID_FACES = 0b101
 
 
@@ -105,6 +105,34 @@ def _primitive_of(obj):
       raise UnsupportedGeometry(f'{obj.Name}: tori with an open tube section need FreeCAD')
     prim = Node('prim', kind=TORUS, params=(obj.Radius1, obj.Radius2, 0.0, 0.0), source=obj.Name)
     return _swept(prim, obj.Angle3, float(obj.Radius1) + float(obj.Radius2), obj.Name)
+  if t == 'Part::Ellipsoid':
+    # FreeCAD's own construction (Part::Ellipsoid::execute, Mod/Part/App/PrimitiveFeature.cpp): a sphere of radius
+    # Radius2 with Angle1/2/3, scaled by (1, Radius3 / Radius2, Radius1 / Radius2); a Radius3 of 0 counts as Radius2.
+    # Hence the semi-axes rx = Radius2, ry = Radius3 or Radius2, rz = Radius1.
+    rx, rz = float(obj.Radius2), float(obj.Radius1)
+    ry = float(obj.Radius3) or rx
+    if not (rx > 0 and ry > 0 and rz > 0):
+      raise UnsupportedGeometry(f'{obj.Name}: ellipsoid needs positive radii')
+    prim = Node('prim', kind=ELLIPSOID, params=(rx, ry, rz, 0.0), source=obj.Name)
+    size = max(rx, ry, rz)
+    a1, a2 = float(obj.Angle1), float(obj.Angle2)
+    if not (_close(a1, -90) and _close(a2, 90)):
+      # the angles act before the scaling: the sphere's parallels at the latitudes Angle1/2 become the planes
+      # z = rz sin(Angle) (the spherical segment above with R -> rz)
+      if not -90 - 1e-9 <= a1 < a2 <= 90 + 1e-9:
+        raise UnsupportedGeometry(f'{obj.Name}: ellipsoid latitudes {a1}, {a2}')
+      z1, z2 = rz * np.sin(np.radians(max(a1, -90.0))), rz * np.sin(np.radians(min(a2, 90.0)))
+      slab = Node('prim', placement=Placement(base=(-2 * size, -2 * size, z1)), kind=BOX, params=(4 * size, 4 * size, z2 - z1, 0.0), source=obj.Name)
+      prim = Node('common', children=[prim, slab], source=obj.Name)
+    # a linear map keeps half-planes through the z axis half-planes through the z axis: the one at azimuth 0 stays,
+    # the one at Angle3 goes to atan2(ry sin a, rx cos a)
+    a3 = float(obj.Angle3)
+    if not _close(a3, 360) and 0 < a3 <= 180 + 1e-9 and not _close(a3, 180):
+      a3 = float(np.degrees(np.arctan2(ry * np.sin(np.radians(a3)), rx * np.cos(np.radians(a3)))))
+    swept = _swept(prim, a3, size, obj.Name)
+    if swept is not prim and prim.op == 'common':        # (one conjunction, not a nest of them)
+      swept = Node('common', children=prim.children + swept.children[1:], source=obj.Name)
+    return swept
   if t == 'Part::FeaturePython' and obj.ProxyClass == 'Paraboloid':
     # solid paraboloid of revolution x^2 + y^2 <= 4 f z, z <= Height (freecad_elements.make.makeParaboloid;
     # FreeCAD has no such primitive: there it is the revolution of a parabola about its axis)
@@ -416,7 +444,7 @@ def is_convex(node):
   """True for solids a straight line meets in one interval: box, sphere,
   cylinder, cone and intersections (Common) of such"""
   if node.op == 'prim':
-    return node.kind in (BOX, SPHERE, CYLINDER, CONE, PARABOLOID)
+    return node.kind in (BOX, SPHERE, CYLINDER, CONE, PARABOLOID, ELLIPSOID)
   if node.op == 'common':
     return all(is_convex(c) for c in node.children)
   return False
@@ -543,6 +571,8 @@ def local_bounds(kind, params):
   if kind == PARABOLOID:
     r = 2.0 * np.sqrt(p[0] * p[1])
     return np.array([-r, -r, 0.0]), np.array([r, r, p[1]])
+  if kind == ELLIPSOID:
+    return np.array([-p[0], -p[1], -p[2]]), np.array([p[0], p[1], p[2]])
   raise ValueError(kind)
 
 
@@ -648,6 +678,15 @@ def tessellate(kind, params, segments=48):
     pt = lambda U, V: st(R * np.sin(np.pi * V) * np.cos(two_pi * U), R * np.sin(np.pi * V) * np.sin(two_pi * U),
                          -R * np.cos(np.pi * V))
     parts.append(_grid(n, m, pt, lambda U, V: pt(U, V) / R))
+  elif kind == ELLIPSOID:
+    # the sphere's (u, v) grid scaled per axis; normals from the gradient (x / rx^2, y / ry^2, z / rz^2)
+    r = np.array(params[:3], dtype=np.float64)
+    m = max(2, n // 2)
+    unit = lambda U, V: st(np.sin(np.pi * V) * np.cos(two_pi * U), np.sin(np.pi * V) * np.sin(two_pi * U), -np.cos(np.pi * V))
+    def nr(U, V):
+      g = unit(U, V) / r
+      return g / np.linalg.norm(g, axis=-1, keepdims=True)
+    parts.append(_grid(n, m, lambda U, V: unit(U, V) * r, nr))
   elif kind == TORUS:
     R1, R2 = params[0], params[1]
     nr = lambda U, V: st(np.cos(two_pi * V) * np.cos(two_pi * U), np.cos(two_pi * V) * np.sin(two_pi * U),

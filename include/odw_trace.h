@@ -50,6 +50,13 @@ enum {
 /*           "slotted parabolic mirrors"; FreeCAD builds it as the revolution */
 /*           of a parabola)        params = f (focal length), H, 2 sqrt(f H)  */
 /*           (= the rim radius, filled in by the library), -                 */
+/*  ELLIPSOID centre 0, axes along x, y, z: the solid                        */
+/*           (x/rx)^2 + (y/ry)^2 + (z/rz)^2 <= 1 (FreeCAD's Part::Ellipsoid: */
+/*           the conic reflector, the aberration-free immersion lens)        */
+/*                                 params = rx, ry, rz (all > 0, anything    */
+/*           else is ODW_ERR_INVALID), -.  One face, no caps (face mask bits */
+/*           above bit 0 are ODW_ERR_UNSUPPORTED).  Known to the             */
+/*           scene-compiled, grid and binary-tree kernels.                   */
 /*  TRIANGLE one facet of a tessellated face (shapes whose surfaces are not */
 /*           quadrics: STEP imports, B-splines -- what FreeCAD's            */
 /*           `Shape.tessellate(tol)` returns).  No local frame: prim_xform  */
@@ -65,12 +72,13 @@ enum {
   ODW_PRIM_CONE = 3,
   ODW_PRIM_TORUS = 4,
   ODW_PRIM_TRIANGLE = 5,
-  ODW_PRIM_PARABOLOID = 6
+  ODW_PRIM_PARABOLOID = 6,
+  ODW_PRIM_ELLIPSOID = 7
 };
 
 /* face bit positions inside prim_flags >> ODW_FACEMASK_SHIFT               */
 /*  BOX: 0:-x 1:+x 2:-y 3:+y 4:-z 5:+z ; CYL/CONE: 0:lateral 1:z=0 2:z=H    */
-/*  SPHERE/TORUS/TRIANGLE: 0 ; PARABOLOID: 0:lateral 2:z=H (bit 1 unused)    */
+/*  SPHERE/TORUS/TRIANGLE/ELLIPSOID: 0 ; PARABOLOID: 0:lateral 2:z=H (bit 1 unused)    */
 #define ODW_FLAG_FLIP_NORMAL 0x1 /* face normals point INTO the primitive   */
                                  /* (tool of a Part::Cut)                   */
 #define ODW_FLAG_CONVEX 0x2      /* the primitive's solid (prim_solid) is convex:*/
