@@ -44,7 +44,7 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_fetch_hits', 'odw_fetch_histogram', 'odw_segment_count', 'odw_fetch_segments', 'odw_reset_segments', 'odw_sample', 'odw_device_histogram',
            'odw_device_counters', 'odw_device_results', 'odw_stream', 'odw_timing_enable', 'odw_timing_read',
            'odw_swap_hit_lists', 'odw_fetch_swapped_hits', 'odw_release_swapped_hits', 'odw_mem_info', 'odw_host_alloc', 'odw_host_free', 'odw_load_hits', 'odw_hits_select', 'odw_hits_gather', 'odw_hits_project', 'odw_hits_range', 'odw_hits_bin', 'odw_hits_moments', 'odw_plane_screen',
-           'odw_compile_scene', 'odw_compiled_info', 'odw_compile_check', 'odw_compile_check_source', 'odw_compiled_source_info', 'odw_upload_source_unguided', 'odw_build_check', 'odw_table_slopes', 'odw_hits_columns',
+           'odw_compile_scene', 'odw_compiled_info', 'odw_compile_check', 'odw_compile_check_source', 'odw_compiled_source_info', 'odw_upload_source_unguided', 'odw_build_check', 'odw_table_slopes', 'odw_spec_image', 'odw_hits_columns',
            'odw_upload_scene_batch', 'odw_trace_batch', 'odw_batch_select', 'odw_batch_rows',
            'odw_plane_screen_batch', 'odw_archive_append', 'odw_archive_select', 'odw_archive_reset', 'odw_batch_hits_select', 'odw_batch_hits_sample', 'odw_batch_hits_project', 'odw_batch_hits_bin',
            'odw_batch_reserve', 'odw_batch_hits_begin', 'odw_batch_hits_sampled', 'odw_batch_hits_measure', 'odw_batch_hits_measured',
@@ -289,6 +289,30 @@ def build_check(scene, limits, library=None):
     raise NativeError(f'odw_build_check: {ERRORS.get(rc, rc)}: {msg.decode() if msg else ""}')
   names = ('primitives', 'nodes', 'grid_cells', 'grid_items', 'grid_lds_bytes', 'dead_primitives')
   return dict(structure=STRUCTURES[int(structure.value)], **{k: int(v) for k, v in zip(names, sizes)})
+
+
+def spec_image(scene, limits):
+  """Host only (no GPU): the value image of the kernel compiled against `scene` (`odw_spec_image`: the block of doubles its
+  unrolled loop reads) for `limits`, and its layout -> dict(image, boxes, gf, gd, gi, frame, par, box, der, box_of, in_arguments);
+  frame ... box_of: one entry per primitive, offsets into image (-1: none)"""
+  d, keep = scene_desc(scene)
+  lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
+                   float(limits.power_tol))
+  f = lib().odw_spec_image
+  f.argtypes = [C.POINTER(SceneDesc), C.POINTER(LimitsDesc), _pd, C.c_uint64, C.POINTER(C.c_uint64), _pi, C.c_uint64,
+                _pd, C.POINTER(C.c_int32)]
+  size, inside = C.c_uint64(0), C.c_int32(0)
+  check(None, f(C.byref(d), C.byref(lim), None, 0, C.byref(size), None, 0, None, C.byref(inside)), 'odw_spec_image')
+  image = np.zeros(int(size.value), np.float64)
+  n = int(d.n_prims)
+  offsets = np.zeros(3 + 5 * n, np.int32)
+  boxes = np.zeros((n, 6), np.float64)
+  check(None, f(C.byref(d), C.byref(lim), image.ctypes.data_as(_pd), image.size, C.byref(size), offsets.ctypes.data_as(_pi),
+                offsets.size, boxes.ctypes.data_as(_pd), C.byref(inside)), 'odw_spec_image')
+  per = offsets[3:].reshape(n, 5)
+  return dict(image=image, boxes=boxes, gf=int(offsets[0]), gd=int(offsets[1]), gi=int(offsets[2]), frame=per[:, 0].copy(),
+              par=per[:, 1].copy(), box=per[:, 2].copy(), der=per[:, 3].copy(), box_of=per[:, 4].copy(),
+              in_arguments=bool(inside.value))
 
 
 def table_slopes(cdf, edges):

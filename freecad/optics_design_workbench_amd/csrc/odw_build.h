@@ -1003,6 +1003,174 @@ void compute_boxes(HostScene& hs, double dist_tol, std::vector<Box>& boxes) {
   }
 }
 
+// ---- the value image of a scene-compiled kernel ------------------------------------------------
+// A compiled kernel (odw_spec.hip) knows its scene's structure; every float64 VALUE its unrolled loop reads comes from
+// one dense block of doubles, laid out for exactly that structure and read at compile-time offsets:
+//   [0..3]   limits: distTol, maxRayLength + distTol, 2 distTol, 0
+//   groups:  group_f64 (4 per group) | group_gdir (3 per group) | grating type and order (the group_i32 row: 2 doubles)
+//   per primitive: the frame entries that are neither 0 nor +-1 (xf_pattern), in index order | its 4 parameters |
+//                  with a box of its own (box_of[p] == p, some face): centre xyz, half extent xyz |
+//                  with a face: the constants intersect_prim derives from parameters and tolerance (spec_image_build)
+// The layout depends on the structure only, the values on the scene's numbers and the limits.
+
+// zero / +-1 pattern of a frame's 12 entries (odw_kernels.hip: xf_comb): bits 0-11 entry != 0, 12-23 entry == +1,
+// 24-35 entry == -1 (rotation part only)
+inline unsigned long long xf_pattern(const double* m) {
+  unsigned long long w = 0;
+  for (int i = 0; i < 12; ++i) {
+    if (m[i] != 0.0) w |= 1ull << i;
+    if (i % 4 != 3 && m[i] == 1.0) w |= 1ull << (12 + i);
+    if (i % 4 != 3 && m[i] == -1.0) w |= 1ull << (24 + i);
+  }
+  return w;
+}
+// the entries of a frame the image stores
+inline unsigned xf_stored(unsigned long long xf) { return (unsigned)(xf & ~(xf >> 12) & ~(xf >> 24) & 0xfffull); }
+
+// primitives with the same box: equal sets {p} + {q : p must lie inside q} (compute_boxes cuts p's box by
+// the boxes of those q), one set per clause of a trimming list of several (compute_boxes: the union over the
+// clauses of such cuts -- equal sets of sets, equal boxes).  box_of = the first such primitive, box_shared =
+// another one refers to it.  (dead here: no face -- an empty box is a matter of values)
+inline void spec_box_sharing(const HostScene& hs, std::vector<int>& box_of, std::vector<int>& box_shared) {
+  const int n = hs.n_prims;
+  box_of.assign(n, 0);
+  box_shared.assign(n, 0);
+  std::vector<std::vector<std::vector<int>>> inside(n);
+  std::vector<char> dead(n);
+  for (int p = 0; p < n; ++p) {
+    const int cw = hs.prim_i32[4 * p + 3], off = cw & 0xffffff, cnt = (cw >> 24) & 0xff;
+    const int end = std::min(off + cnt, (int)hs.cond.size());
+    dead[p] = (((hs.prim_i32[4 * p + 2] & ~ODW_FLAG_ISOLATED) >> ODW_FACEMASK_SHIFT) & 0xff) == 0;
+    inside[p].push_back({p});
+    for (int c = off; c < end; ++c) {
+      if (c != off && cond_opens(hs.cond[c])) inside[p].push_back({p});
+      if (hs.cond[c] < 0) inside[p].back().push_back(cond_operand(hs.cond[c]));
+    }
+    for (std::vector<int>& set : inside[p]) {
+      std::sort(set.begin(), set.end());
+      set.erase(std::unique(set.begin(), set.end()), set.end());
+    }
+    std::sort(inside[p].begin(), inside[p].end());
+  }
+  for (int p = 0; p < n; ++p) {
+    box_of[p] = p;
+    // (the sets are equal, but compute_boxes cuts with the operands' FULL boxes only: p's box is
+    //  box(p) ^ box(q1) ^ ..., the same expression for both when the sets agree)
+    for (int q = 0; q < p; ++q)
+      if (!dead[q] && !dead[p] && hs.prim_i32[4 * q + 1] == hs.prim_i32[4 * p + 1] && inside[q] == inside[p]) {
+        box_of[p] = q;
+        box_shared[q] = 1;
+        break;
+      }
+  }
+}
+
+constexpr int kSpecImageLimits = 4;       // doubles of the limits section (it travels in the kernel arguments always)
+// A launch's kernel arguments hold 4 KB: TraceParams, the image's pointer, the image, and the arguments the compiler
+// adds (256 bytes; twice that is left).  A larger image stays in device memory.
+constexpr size_t kSpecArgBytes = 4096 - 512;
+
+struct SpecLayout {
+  int n = 0, ng = 0, size = 0;
+  int gf = 0, gd = 0, gi = 0;                       // group_f64, group_gdir, group_i32 rows
+  std::vector<int> frame, par, box, der;            // per primitive (box, der: -1 = none)
+  std::vector<int> box_of, box_shared;
+  bool fits(size_t params_bytes) const { return ((params_bytes + 7) & ~(size_t)7) + 8 + (size_t)size * 8 <= kSpecArgBytes; }
+};
+
+inline int spec_derived_count(int type) {
+  switch (type) {
+    case ODW_PRIM_BOX: return 3;
+    case ODW_PRIM_CYLINDER: case ODW_PRIM_CONE: case ODW_PRIM_PARABOLOID: case ODW_PRIM_TORUS: return 4;
+    default: return 0;
+  }
+}
+
+inline SpecLayout spec_image_layout(const HostScene& hs) {
+  SpecLayout L;
+  const int n = L.n = hs.n_prims, ng = L.ng = hs.n_groups;
+  spec_box_sharing(hs, L.box_of, L.box_shared);
+  int at = kSpecImageLimits;
+  L.gf = at; at += 4 * ng;
+  L.gd = at; at += 3 * ng;
+  L.gi = at; at += 2 * ng;
+  L.frame.assign(n, 0); L.par.assign(n, 0); L.box.assign(n, -1); L.der.assign(n, -1);
+  for (int p = 0; p < n; ++p) {
+    const bool faces = (((hs.prim_i32[4 * p + 2]) >> ODW_FACEMASK_SHIFT) & 0xff) != 0;
+    L.frame[p] = at; at += __builtin_popcount(xf_stored(xf_pattern(&hs.prim_f64[16 * (size_t)p])));
+    L.par[p] = at; at += 4;
+    if (faces && L.box_of[p] == p) { L.box[p] = at; at += 6; }
+    const int nd = faces ? spec_derived_count(hs.prim_i32[4 * p]) : 0;
+    if (nd) { L.der[p] = at; at += nd; }
+  }
+  L.size = at;
+  return L;
+}
+
+// Centre and half extent of the interval [lo, hi] (lo <= hi, finite) as the compiled kernels' box screen reads them:
+// c near the middle (its rounding does not matter), h >= 0 rounded outward until c - h <= lo and c + h >= hi hold in
+// float64 -- the screened interval contains the box, slack included.
+inline void box_centre_half(double lo, double hi, double& c, double& h) {
+#pragma clang fp contract(off)
+  c = 0.5 * lo + 0.5 * hi;
+  h = std::max(hi - c, c - lo);
+  if (!(h >= 0.0)) h = 0.0;
+  while (c - h > lo || c + h < hi) h = std::nextafter(h, INFINITY);
+}
+
+// The image of hs (boxes built: compute_boxes) for the limits lim, img[0 .. L.size).  Every derived constant is the
+// sequence of IEEE operations intersect_prim performs on the device for it (odw_kernels.hip, compiled with
+// -ffp-contract=on): std::fma where a product and a sum of ONE expression fuse there, plain operations elsewhere --
+// and nothing else fuses here.
+inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const SpecLayout& L, double* img) {
+#pragma clang fp contract(off)
+  const double tol = lim.dist_tol;
+  std::fill(img, img + L.size, 0.0);
+  img[0] = tol;
+  img[1] = lim.max_ray_length + tol;
+  img[2] = 2.0 * tol;
+  for (int g = 0; g < L.ng; ++g) {
+    for (int k = 0; k < 4; ++k) img[L.gf + 4 * g + k] = hs.group_f64[4 * (size_t)g + k];
+    for (int k = 0; k < 3; ++k) img[L.gd + 3 * g + k] = hs.group_gdir[3 * (size_t)g + k];
+    std::memcpy(&img[L.gi + 2 * g], &hs.group_i32[4 * (size_t)g], 4 * sizeof(int32_t));
+  }
+  for (int p = 0; p < L.n; ++p) {
+    const double* pf = &hs.prim_f64[16 * (size_t)p];
+    const double* par = pf + 12;
+    const unsigned stored = xf_stored(xf_pattern(pf));
+    int at = L.frame[p];
+    for (int i = 0; i < 12; ++i)
+      if ((stored >> i) & 1u) img[at++] = pf[i];
+    for (int k = 0; k < 4; ++k) img[L.par[p] + k] = par[k];
+    if (L.box[p] >= 0) {
+      // centre and half extent of the box, the half extent rounded outward: [c - h, c + h] holds [lo, hi] in float64
+      const double* b = &hs.prim_hdr[8 * (size_t)p];
+      for (int a = 0; a < 3; ++a) box_centre_half(b[a], b[3 + a], img[L.box[p] + a], img[L.box[p] + 3 + a]);
+    }
+    if (L.der[p] < 0) continue;
+    double* d = img + L.der[p];
+    const int type = hs.prim_i32[4 * p];
+    if (type == ODW_PRIM_BOX) {
+      for (int a = 0; a < 3; ++a) d[a] = par[a] + tol;                    // the face rectangles' far edges
+    } else if (type == ODW_PRIM_TORUS) {
+      const double R1 = par[0], R2 = par[1];
+      d[0] = std::fma(R1 + R2, 1.0000001, 1e-9);                          // bound
+      d[1] = std::fma(R2, 1.0000001, 1e-9);                               // zs
+      d[2] = std::fma(R1 - R2, 0.9999999, -1e-9);                         // rin
+      d[3] = d[2] * d[2];
+    } else {
+      const bool parab = type == ODW_PRIM_PARABOLOID;
+      const double R1 = parab ? 0.0 : par[0];
+      const double R2 = (type == ODW_PRIM_CYLINDER) ? par[0] : (parab ? par[2] : par[1]);
+      const double H = (type == ODW_PRIM_CONE) ? par[2] : par[1];
+      d[0] = H + tol;
+      d[1] = R1 * R1 * (1.0 - 1e-9);                                      // the cylinder's side test
+      d[2] = (R1 + tol) * (R1 + tol);
+      d[3] = (R2 + tol) * (R2 + tol);
+    }
+  }
+}
+
 // A scene the flat loop would take but for its rare quadrics (paraboloids, ellipsoids: build_accel gives it a grid and a
 // tree, since the generic flat kernel leaves their code out): a kernel compiled against it needs neither
 bool flat_but_for_rare_quadrics(const HostScene& hs, int flat_limit) {

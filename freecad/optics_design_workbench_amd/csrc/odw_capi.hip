@@ -82,6 +82,12 @@ struct odw_ctx {
   uint64_t spec_source_key = 0;            // the same of the source the bound kernel is compiled against, 0: source-free
   hipFunction_t spec_fn = nullptr;         // bound kernel (owned by the process-wide cache), or null
   bool spec_lean = false, spec_stoch = false;
+  // the bound kernel's value image (odw_build.h: SpecLayout; odw_spec.hip: spec_launch builds it at every launch)
+  SpecLayout spec_layout;
+  std::vector<double> spec_image_now, spec_image_host;   // this launch's image; the one in spec_image (images beyond the arguments)
+  std::vector<char> spec_args;
+  DevBuf spec_image;
+  size_t batch_img_off = 0;                // doubles from a batch block's start to its image (0: the batch has none)
   // ODW_COMPILE_AUTO: the scene's kernel is not there yet (not hot enough, or being compiled)
   bool spec_pending = false;
   std::string spec_key;
@@ -562,7 +568,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       ctx->err = keep_err;
     }
   }
-  if (batch && ctx->spec_fn && !ctx->spec_batch_fn && !ctx->spec_batch_failed) {
+  if (batch && ctx->spec_fn && !ctx->spec_batch_fn && !ctx->spec_batch_failed && ctx->batch_img_off) {
     // the compiled kernel's BATCH variant: bound on the first batch launch of the structure (a compilation of its own,
     // cached like the other; odw_compile_scene's mode decides, as for single launches).  A variant that cannot be built
     // is not tried again for this binding, and its failure does not become the error of a launch that succeeds on the
@@ -663,7 +669,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     if (rc) return rc;
   }
   if (use_spec) {
-    int rc = spec_launch(ctx, grid, batch ? ctx->spec_batch_fn : pw ? ctx->spec_power_fn : ctx->spec_fn);
+    int rc = spec_launch(ctx, grid, batch ? ctx->spec_batch_fn : pw ? ctx->spec_power_fn : ctx->spec_fn, batch);
     if (rc) return rc;
   } else if (batch) {
     if (ctx->hs.lean) hipLaunchKernelGGL((odw_trace_kernel<false, false, false, true, true>), dim3(grid), dim3(256), 0, ctx->stream, P);
@@ -852,7 +858,7 @@ void odw_destroy(odw_ctx* ctx) {
   }
   for (auto& ev : ctx->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
   for (auto& ev : ctx->free_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
-  DevBuf* all[] = {&ctx->prim_f64, &ctx->prim_hdr, &ctx->prim_i32, &ctx->cond_i32, &ctx->group_f64, &ctx->group_i32,
+  DevBuf* all[] = {&ctx->spec_image, &ctx->prim_f64, &ctx->prim_hdr, &ctx->prim_i32, &ctx->cond_i32, &ctx->group_f64, &ctx->group_i32,
                    &ctx->group_gdir, &ctx->seq_mask, &ctx->bvh_nodes, &ctx->bvh_prims, &ctx->bvh_leaf, &ctx->bvh_wide,
                    &ctx->phi_tab, &ctx->t_tab, &ctx->t_guide, &ctx->d_source, &ctx->d_det, &ctx->hits, &ctx->hit_count, &ctx->chunk_counter, &ctx->results,
                    &ctx->ray_o, &ctx->ray_d, &ctx->ray_p, &ctx->ray_aos, &ctx->samp_t, &ctx->samp_phi,
@@ -1008,6 +1014,46 @@ int odw_compile_check_source(const odw_scene_desc* scene, const odw_limits* limi
   if (!spec_compile(text, arch && *arch ? arch : "gfx950", code, err))
     return fail(nullptr, ODW_ERR_DEVICE, err);
   if (code_bytes) *code_bytes = code.size();
+  return ODW_OK;
+}
+
+// The value image of a compiled kernel and its layout, without a device: the functions (odw_build.h) a launch of the
+// compiled kernel runs, for callers that hold them against the operations written out (tests/test_spec_image.py).
+int odw_spec_image(const odw_scene_desc* scene, const odw_limits* limits, double* image, uint64_t image_capacity,
+                   uint64_t* image_size, int32_t* offsets, uint64_t offsets_capacity, double* boxes,
+                   int32_t* in_arguments) {
+  if (!scene || !limits) return fail(nullptr, ODW_ERR_INVALID, "odw_spec_image: null argument");
+  if (!(limits->dist_tol > 0) || !(limits->max_ray_length > 0)) return fail(nullptr, ODW_ERR_INVALID, "odw_spec_image: limits out of range");
+  HostScene tmp;
+  std::string refusal;
+  int rc = scene_host_tables(scene, tmp, refusal);
+  if (rc) return fail(nullptr, rc, refusal);
+  std::vector<Box> built;
+  compute_boxes(tmp, limits->dist_tol, built);
+  const std::string why = spec_ineligible(tmp);
+  if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_spec_image: " + why);
+  const SpecLayout L = spec_image_layout(tmp);
+  if (image_size) *image_size = (uint64_t)L.size;
+  if (in_arguments) *in_arguments = L.fits(sizeof(TraceParams)) ? 1 : 0;
+  if (image) {
+    if (image_capacity < (uint64_t)L.size) return fail(nullptr, ODW_ERR_CAPACITY, "odw_spec_image: image_capacity too small");
+    DeviceLimits lim;
+    lim.max_ray_length = limits->max_ray_length;
+    lim.dist_tol = limits->dist_tol;
+    lim.power_tol = limits->power_tol;
+    lim.max_intersections = limits->max_intersections;
+    spec_image_build(tmp, lim, L, image);
+  }
+  if (boxes)
+    for (int p = 0; p < L.n; ++p) std::memcpy(boxes + 6 * (size_t)p, &tmp.prim_hdr[8 * (size_t)p], 6 * sizeof(double));
+  if (offsets) {
+    if (offsets_capacity < 3 + 5 * (uint64_t)L.n) return fail(nullptr, ODW_ERR_CAPACITY, "odw_spec_image: offsets_capacity too small");
+    offsets[0] = L.gf; offsets[1] = L.gd; offsets[2] = L.gi;
+    for (int p = 0; p < L.n; ++p) {
+      int32_t* o = offsets + 3 + 5 * p;
+      o[0] = L.frame[p]; o[1] = L.par[p]; o[2] = L.box[p]; o[3] = L.der[p]; o[4] = L.box_of[p];
+    }
+  }
   return ODW_OK;
 }
 
@@ -1548,10 +1594,17 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
   if ((ctx->P.scene.n_nodes || ctx->P.grid.nx > 0) && !rare_compiled)
     return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: batches are traced by the flat kernels (analytic scenes of up to 64 primitives; "
                                           "with paraboloids or ellipsoids: by the compiled one, ODW_COMPILE_STRUCTURE)");
-  const std::string text0 = compiled ? spec_text(ctx->hs, ctx->n_samplers) : std::string();
+  // (the header text of a scene a compiled kernel could take, whatever the mode is now: it also says whether the
+  //  scenes share the layout of the value image)
+  const bool eligible = spec_ineligible(ctx->hs).empty();
+  const std::string text0 = eligible ? spec_text(ctx->hs, ctx->n_samplers) : std::string();
+  const SpecLayout L0 = eligible ? spec_image_layout(ctx->hs) : SpecLayout();
+  bool images = eligible;
   const size_t n = (size_t)ctx->P.scene.n_prims;
-  // one block of doubles per scene: prim_f64 (16 n) | prim_hdr (8 n) | group_f64 (4 x 64) | group_gdir (3 x 64)
-  const size_t o_hdr = 16 * n, o_gf = o_hdr + 8 * n, o_gd = o_gf + ODW_MAX_GROUPS * 4, stride = o_gd + ODW_MAX_GROUPS * 3;
+  // one block of doubles per scene: prim_f64 (16 n) | prim_hdr (8 n) | group_f64 (4 x 64) | group_gdir (3 x 64) |
+  // the value image of the compiled kernel's BATCH variant (odw_build.h: spec_image_build)
+  const size_t o_hdr = 16 * n, o_gf = o_hdr + 8 * n, o_gd = o_gf + ODW_MAX_GROUPS * 4, o_img = o_gd + ODW_MAX_GROUPS * 3,
+               stride = o_img + (size_t)L0.size;
   std::vector<double> blocks(stride * (size_t)n_scenes, 0.0);
   for (int k = 0; k < n_scenes; ++k) {
     HostScene tmp;
@@ -1561,10 +1614,14 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
       return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: scene " + std::to_string(k) + " differs from scene 0 in structure (" + why + ")");
     std::vector<Box> boxes;
     compute_boxes(tmp, ctx->P.lim.dist_tol, boxes);
-    if (compiled && spec_text(tmp, ctx->n_samplers) != text0)
-      return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: scene " + std::to_string(k) + " differs from scene 0 in the structure a "
-                                            "compiled kernel is built from (which frame entries are 0 / +1 / -1, shared boxes)");
+    if (eligible && spec_text(tmp, ctx->n_samplers) != text0) {
+      if (compiled)
+        return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: scene " + std::to_string(k) + " differs from scene 0 in the structure a "
+                                              "compiled kernel is built from (which frame entries are 0 / +1 / -1, shared boxes)");
+      images = false;                                  // (generic kernels only for this batch)
+    }
     double* b = blocks.data() + stride * (size_t)k;
+    if (images) spec_image_build(tmp, ctx->P.lim, L0, b + o_img);
     std::memcpy(b, tmp.prim_f64.data(), 16 * n * sizeof(double));
     std::memcpy(b + o_hdr, tmp.prim_hdr.data(), 8 * n * sizeof(double));
     // (the isolated-solid shortcut depends on the boxes' values; it never changes a result: left out of batches)
@@ -1587,7 +1644,8 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
   ctx->batch_n = n_scenes;
   ctx->batch_prims = n;
   ctx->batch_stride = stride;
-  ctx->batch_spec_text = text0;
+  ctx->batch_img_off = images ? o_img : 0;
+  ctx->batch_spec_text = compiled ? text0 : std::string();
   return ODW_OK;
 }
 

@@ -12,6 +12,7 @@
 //   group_f64: 64 x 4 f64         ior, reflectivity, absorption length, grating lpm
 //   group_i32: 64 x 4 i32         optical type, record, grating type, grating order
 //   cdf tables: interleaved (cdf, edge) f64 pairs per knot, one 16-B load each
+// (A kernel compiled against a scene reads its float64 values from the scene's value image instead: odw_build.h.)
 // Everything a wave needs per primitive is addressed with wave-uniform
 // indices, so hipcc emits scalar (s_load) loads: the scene costs SGPRs, not
 // VGPRs, and no LDS staging is needed for the small benchmark scenes.

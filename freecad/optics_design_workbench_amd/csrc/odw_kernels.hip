@@ -206,8 +206,9 @@ __device__ __forceinline__ d3 xf_vec_t(P m, d3 v) {  // R^T v
 // primitive loop of the flat kernel is then unrolled over it: type dispatch, face masks and condition
 // lists fold away, frame products skip their zero terms, and every table read has a constant offset
 // (no dependent scalar loads, no scalar branches).  All float64 VALUES (frames, parameters, boxes,
-// optical constants) are still read from the tables, so one compiled kernel serves every scene of the
-// same structure (a radius sweep compiles once).  NoSpec = the generic kernels.
+// optical constants) are run-time data still, read from the scene's value image (odw_build.h; SceneView::img:
+// one block of doubles behind TraceParams in the kernel arguments, or behind one pointer), so one compiled
+// kernel serves every scene of the same structure (a radius sweep compiles once).  NoSpec = the generic kernels.
 struct NoSpec {
   static constexpr bool enabled = false;
   static constexpr int N = 0;
@@ -253,6 +254,14 @@ __device__ __forceinline__ double xf_comb(P m, double a, double b, double c) {
   }
   return acc;
 }
+// A frame of the value image (odw_build.h): only the entries xf_comb reads -- those that are neither 0 nor +-1 -- in
+// index order.  Entry i sits behind the stored entries below it: a constant once the index is one.
+template <unsigned long long XF>
+struct PackedFrame {
+  cf64 p;
+  static constexpr unsigned stored = (unsigned)(XF & ~(XF >> 12) & ~(XF >> 24) & 0xfffull);
+  __device__ __forceinline__ double operator[](int i) const { return p[__builtin_popcount(stored & ((1u << i) - 1u))]; }
+};
 template <unsigned long long XF, class P>
 __device__ __forceinline__ d3 xf_point_nz(P m, d3 p) {
   return mk(xf_comb<XF, 0, 1, 2, 3>(m, p.x, p.y, p.z), xf_comb<XF, 4, 5, 6, 7>(m, p.x, p.y, p.z),
@@ -440,6 +449,7 @@ struct Query {
 struct SceneView {    // constant-address-space views of the scene tables
   cf64 prim_f64, prim_hdr;
   ci32 prim_i32, cond_i32;
+  cf64 img, lim;      // (compiled kernels, which read nothing of the above) the value image and its limits section
 };
 
 // One candidate intersection of primitive p: range test, then -- only if it
@@ -492,8 +502,8 @@ __device__ __forceinline__ bool trim_all(const SceneView& sv, const Query& q, d3
   } else {
     constexpr int cw = SPEC::cond(C);
     constexpr int qp = cond_operand(cw);
-    cf64 pf = sv.prim_f64 + (size_t)qp * 16;
-    const double sd = prim_sdist<RQ>(SPEC::type(qp), pf + 12, xf_point_nz<SPEC::xf(qp)>(pf, gp));
+    const PackedFrame<SPEC::xf(qp)> pf{sv.img + SPEC::frame(qp)};
+    const double sd = prim_sdist<RQ>(SPEC::type(qp), sv.img + SPEC::par(qp), xf_point_nz<SPEC::xf(qp)>(pf, gp));
     if (cw < 0) { if (sd > q.tol) return false; }     // must be inside
     else { if (sd < -q.tol) return false; }           // must be outside
     return trim_all<RQ, SPEC, C + 1, END>(sv, q, gp);
@@ -540,7 +550,7 @@ __device__ __forceinline__ void consider_spec(const SceneView& sv, Query& q, dou
     if (!trim_ok<RQ, SPEC, SPEC::cond_off(PI), SPEC::cond_off(PI) + SPEC::cond_cnt(PI)>(sv, q, q.start + q.dn * opq(t))) return;
 #endif
   }
-  if (cand_any) { q.any.t = t; q.any.face = key; q.cut = fmin(q.tmax, t + 2.0 * q.tol); }
+  if (cand_any) { q.any.t = t; q.any.face = key; q.cut = fmin(q.tmax, t + sv.lim[2]); }
   if (cand_oth) { q.oth.t = t; q.oth.face = key; }
 }
 
@@ -584,6 +594,14 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
   const int cond_off = cond_word & 0xffffff, cond_cnt = (cond_word >> 24) & 0xff;
   const int fmask = (flags >> ODW_FACEMASK_SHIFT) & 0xff;
   cf64 par = pf + 12;
+  // (a compiled scene: parameters, frame and the constants derived from parameters and tolerance come from the value
+  //  image -- ODW_DER(I, E): the image's word I for this primitive, the expression E it was built from otherwise)
+  cf64 der = nullptr;
+  if constexpr (SPEC::enabled) {
+    par = sv.img + SPEC::par(PI);
+    der = sv.img + SPEC::der(PI);
+  }
+#define ODW_DER(I, E) (SPEC::enabled ? der[I] : (E))
   const double tol = q.tol;
   Cands c;
   c.t0 = c.t1 = c.t2 = c.t3 = INFINITY;
@@ -608,8 +626,9 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
   } else {
   d3 o, d;
   if constexpr (SPEC::enabled) {
-    o = xf_point_nz<SPEC::xf(PI)>(pf, q.start);
-    d = xf_vec_nz<SPEC::xf(PI)>(pf, q.dn);
+    const PackedFrame<SPEC::xf(PI)> fr{sv.img + SPEC::frame(PI)};
+    o = xf_point_nz<SPEC::xf(PI)>(fr, q.start);
+    d = xf_vec_nz<SPEC::xf(PI)>(fr, q.dn);
   } else {
     o = xf_point(pf, q.start);
     d = xf_vec(pf, q.dn);
@@ -632,6 +651,10 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     // the two distances -- one v_min / v_max each instead of a select (two v_cndmask behind the compare) each
     const double nx_ = fmin(ax, bx), ny_ = fmin(ay, by), nz_ = fmin(az, bz);
     const double fx_ = fmax(ax, bx), fy_ = fmax(ay, by), fz_ = fmax(az, bz);
+    // (the far edges of the face rectangles, written where they are used: the generic kernels evaluate them there)
+#define ODW_SXT ODW_DER(0, par[0] + tol)
+#define ODW_SYT ODW_DER(1, par[1] + tol)
+#define ODW_SZT ODW_DER(2, par[2] + tol)
     if (cond_cnt) {
       // Trimmed box (operand of a boolean): any face can be rejected by its trim, so every valid
       // face has to reach consider() -- within the tolerance of an edge the ray meets the widened
@@ -641,8 +664,8 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       {                                                                                         \
         const double t_ = (T);                                                                  \
         const double u_ = fma(t_, D1, P1), v_ = fma(t_, D2, P2);                                \
-        const bool ok_ = ((fmask >> (FACE)) & 1) && t_ > tol && u_ >= -tol && u_ <= (S1) + tol && \
-                         v_ >= -tol && v_ <= (S2) + tol;                                        \
+        const bool ok_ = ((fmask >> (FACE)) & 1) && t_ > tol && u_ >= -tol && u_ <= (S1) &&     \
+                         v_ >= -tol && v_ <= (S2);                                              \
         const bool a_ = ok_ && t_ < TA;                                                         \
         const bool b_ = ok_ && !a_ && t_ < TB;                                                  \
         TB = a_ ? TA : (b_ ? t_ : TB);                                                          \
@@ -650,12 +673,12 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
         TA = a_ ? t_ : TA;                                                                      \
         FA = a_ ? (FACE) : FA;                                                                  \
       }
-      ODW_BOX_FACE2(nx_, px ? 0 : 1, o.y, d.y, par[1], o.z, d.z, par[2], c.t0, c.f0, c.t2, c.f2);
-      ODW_BOX_FACE2(ny_, py ? 2 : 3, o.z, d.z, par[2], o.x, d.x, par[0], c.t0, c.f0, c.t2, c.f2);
-      ODW_BOX_FACE2(nz_, pz ? 4 : 5, o.x, d.x, par[0], o.y, d.y, par[1], c.t0, c.f0, c.t2, c.f2);
-      ODW_BOX_FACE2(fx_, px ? 1 : 0, o.y, d.y, par[1], o.z, d.z, par[2], c.t1, c.f1, c.t3, c.f3);
-      ODW_BOX_FACE2(fy_, py ? 3 : 2, o.z, d.z, par[2], o.x, d.x, par[0], c.t1, c.f1, c.t3, c.f3);
-      ODW_BOX_FACE2(fz_, pz ? 5 : 4, o.x, d.x, par[0], o.y, d.y, par[1], c.t1, c.f1, c.t3, c.f3);
+      ODW_BOX_FACE2(nx_, px ? 0 : 1, o.y, d.y, ODW_SYT, o.z, d.z, ODW_SZT, c.t0, c.f0, c.t2, c.f2);
+      ODW_BOX_FACE2(ny_, py ? 2 : 3, o.z, d.z, ODW_SZT, o.x, d.x, ODW_SXT, c.t0, c.f0, c.t2, c.f2);
+      ODW_BOX_FACE2(nz_, pz ? 4 : 5, o.x, d.x, ODW_SXT, o.y, d.y, ODW_SYT, c.t0, c.f0, c.t2, c.f2);
+      ODW_BOX_FACE2(fx_, px ? 1 : 0, o.y, d.y, ODW_SYT, o.z, d.z, ODW_SZT, c.t1, c.f1, c.t3, c.f3);
+      ODW_BOX_FACE2(fy_, py ? 3 : 2, o.z, d.z, ODW_SZT, o.x, d.x, ODW_SXT, c.t1, c.f1, c.t3, c.f3);
+      ODW_BOX_FACE2(fz_, pz ? 5 : 4, o.x, d.x, ODW_SXT, o.y, d.y, ODW_SYT, c.t1, c.f1, c.t3, c.f3);
 #undef ODW_BOX_FACE2
     } else {
     double bt = INFINITY;
@@ -667,14 +690,14 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     {                                                                                         \
       const double t_ = (T);                                                                  \
       const double u_ = fma(t_, D1, P1), v_ = fma(t_, D2, P2);                                \
-      const bool ok_ = ODW_BOX_OK(((fmask >> (FACE)) & 1) != 0, t_ > tol, u_ >= -tol, u_ <= (S1) + tol, \
-                                  v_ >= -tol, v_ <= (S2) + tol);                              \
+      const bool ok_ = ODW_BOX_OK(((fmask >> (FACE)) & 1) != 0, t_ > tol, u_ >= -tol, u_ <= (S1), \
+                                  v_ >= -tol, v_ <= (S2));                                    \
       if (ok_ && (t_ < bt || (t_ == bt && (FACE) < bf))) { bt = t_; bf = (FACE); }            \
     }
     // entry faces: low face when moving in +axis direction
-    ODW_BOX_FACE(nx_, px ? 0 : 1, o.y, d.y, par[1], o.z, d.z, par[2]);
-    ODW_BOX_FACE(ny_, py ? 2 : 3, o.z, d.z, par[2], o.x, d.x, par[0]);
-    ODW_BOX_FACE(nz_, pz ? 4 : 5, o.x, d.x, par[0], o.y, d.y, par[1]);
+    ODW_BOX_FACE(nx_, px ? 0 : 1, o.y, d.y, ODW_SYT, o.z, d.z, ODW_SZT);
+    ODW_BOX_FACE(ny_, py ? 2 : 3, o.z, d.z, ODW_SZT, o.x, d.x, ODW_SXT);
+    ODW_BOX_FACE(nz_, pz ? 4 : 5, o.x, d.x, ODW_SXT, o.y, d.y, ODW_SYT);
     c.t0 = bt;
     c.f0 = bf;
     const double t_in = fmax(fmax(nx_, ny_), nz_);
@@ -682,15 +705,18 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     if (!(bt < INFINITY) || !(t_in < t_out)) {
       bt = INFINITY;
       bf = 0;
-      ODW_BOX_FACE(fx_, px ? 1 : 0, o.y, d.y, par[1], o.z, d.z, par[2]);
-      ODW_BOX_FACE(fy_, py ? 3 : 2, o.z, d.z, par[2], o.x, d.x, par[0]);
-      ODW_BOX_FACE(fz_, pz ? 5 : 4, o.x, d.x, par[0], o.y, d.y, par[1]);
+      ODW_BOX_FACE(fx_, px ? 1 : 0, o.y, d.y, ODW_SYT, o.z, d.z, ODW_SZT);
+      ODW_BOX_FACE(fy_, py ? 3 : 2, o.z, d.z, ODW_SZT, o.x, d.x, ODW_SXT);
+      ODW_BOX_FACE(fz_, pz ? 5 : 4, o.x, d.x, ODW_SXT, o.y, d.y, ODW_SYT);
       c.t1 = bt;
       c.f1 = bf;
     }
 #undef ODW_BOX_FACE
 #undef ODW_BOX_OK
     }
+#undef ODW_SXT
+#undef ODW_SYT
+#undef ODW_SZT
   } else if (type == ODW_PRIM_CYLINDER || type == ODW_PRIM_CONE || (PARAB && type == ODW_PRIM_PARABOLOID)) {
     // one quadric template: cylinder / cone x^2 + y^2 = (R1 + k z)^2, paraboloid x^2 + y^2 = 4 f z
     // (R1 = k = 0 and a term linear in z; its only cap is the one at z = H, face 2)
@@ -700,6 +726,7 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     const double H = (type == ODW_PRIM_CONE) ? par[2] : par[1];
     const double k = (type == ODW_PRIM_CONE) ? (R2 - R1) / H : 0.0;
     const double f2 = parab ? 2.0 * par[0] : 0.0;
+#define ODW_HT ODW_DER(0, H + tol)
     // A cylinder's side without its quadratic (flat kernels): the squared distance from the axis is convex along the
     // ray, so a ray that is inside the radius where it crosses the planes z = -tol and z = H + tol is inside in between
     // -- no root of the side can pass the z test below.  A beam through the inside of a lens is that case for every
@@ -711,9 +738,9 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     double invz = 0.0;
     if ((fmask & 6) || (side_skip && type == ODW_PRIM_CYLINDER && side)) invz = frcp(d.z);
     if (side_skip && type == ODW_PRIM_CYLINDER && side) {
-      const double tl = (-tol - o.z) * invz, th = (H + tol - o.z) * invz;
+      const double tl = (-tol - o.z) * invz, th = (ODW_HT - o.z) * invz;
       const double xl = fma(tl, d.x, o.x), yl = fma(tl, d.y, o.y), xh = fma(th, d.x, o.x), yh = fma(th, d.y, o.y);
-      const double lim = R1 * R1 * (1.0 - 1e-9);
+      const double lim = ODW_DER(1, R1 * R1 * (1.0 - 1e-9));
       side = !(fma(xl, xl, yl * yl) < lim && fma(xh, xh, yh * yh) < lim);
     }
     if (side) {
@@ -723,16 +750,17 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
                                 o.x * d.x + o.y * d.y - k * rz * d.z - f2 * d.z,
                                 o.x * o.x + o.y * o.y - rz * rz - 2.0 * f2 * o.z, t0, t1);
       const double z0 = o.z + t0 * d.z, z1 = o.z + t1 * d.z;
-      c.t0 = (bool)((int)(nr >= 1) & (int)(z0 >= -tol) & (int)(z0 <= H + tol) & (int)((R1 + k * z0) >= -tol)) ? t0 : c.t0;
-      c.t1 = (bool)((int)(nr == 2) & (int)(z1 >= -tol) & (int)(z1 <= H + tol) & (int)((R1 + k * z1) >= -tol)) ? t1 : c.t1;
+      c.t0 = (bool)((int)(nr >= 1) & (int)(z0 >= -tol) & (int)(z0 <= ODW_HT) & (int)((R1 + k * z0) >= -tol)) ? t0 : c.t0;
+      c.t1 = (bool)((int)(nr == 2) & (int)(z1 >= -tol) & (int)(z1 <= ODW_HT) & (int)((R1 + k * z1) >= -tol)) ? t1 : c.t1;
     }
     if (fmask & 6) {
       const double ta = (0.0 - o.z) * invz, tb = (H - o.z) * invz;
       const double xa = o.x + ta * d.x, ya = o.y + ta * d.y;
       const double xb = o.x + tb * d.x, yb = o.y + tb * d.y;
-      { const bool w_ = (bool)((int)((fmask & 2) != 0) & (int)(R1 > 0) & (int)(xa * xa + ya * ya <= (R1 + tol) * (R1 + tol))); c.t2 = w_ ? ta : c.t2; c.f2 = w_ ? 1 : c.f2; }
-      { const bool w_ = (bool)((int)((fmask & 4) != 0) & (int)(R2 > 0) & (int)(xb * xb + yb * yb <= (R2 + tol) * (R2 + tol))); c.t3 = w_ ? tb : c.t3; c.f3 = w_ ? 2 : c.f3; }
+      { const bool w_ = (bool)((int)((fmask & 2) != 0) & (int)(R1 > 0) & (int)(xa * xa + ya * ya <= ODW_DER(2, (R1 + tol) * (R1 + tol)))); c.t2 = w_ ? ta : c.t2; c.f2 = w_ ? 1 : c.f2; }
+      { const bool w_ = (bool)((int)((fmask & 4) != 0) & (int)(R2 > 0) & (int)(xb * xb + yb * yb <= ODW_DER(3, (R2 + tol) * (R2 + tol)))); c.t3 = w_ ? tb : c.t3; c.f3 = w_ ? 2 : c.f3; }
     }
+#undef ODW_HT
   } else if (ELL && type == ODW_PRIM_ELLIPSOID) {
     // the unit sphere of the scaled frame: o' = o / r, d' = d / r component by component; t stays a length along
     // the ray (d' is not a unit vector: the general solver).  Both roots with face 0, as for the sphere.
@@ -750,12 +778,12 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     const double R1 = par[0], R2 = par[1];
     const double t0 = -dot(o, d);          // |d| = 1
     const d3 cc = o + d * t0;              // closest approach to the centre
-    const double bound = (R1 + R2) * 1.0000001 + 1e-9;
+    const double bound = ODW_DER(0, (R1 + R2) * 1.0000001 + 1e-9);
     const double h2 = bound * bound - dot(cc, cc);
     if (!(h2 > 0)) return;                 // misses the bounding sphere
     double s_lo = -fsqrt(h2), s_hi = -s_lo;
     // slab |z| <= R2 (+slack): the torus lies inside it
-    const double zs = R2 * 1.0000001 + 1e-9;
+    const double zs = ODW_DER(1, R2 * 1.0000001 + 1e-9);
     if (d.z != 0) {
       const double iz = frcp(d.z);
       double a = (-zs - cc.z) * iz, b = (zs - cc.z) * iz;
@@ -771,8 +799,8 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     {
       const double xa = cc.x + s_lo * d.x, ya = cc.y + s_lo * d.y;
       const double xb = cc.x + s_hi * d.x, yb = cc.y + s_hi * d.y;
-      const double rin = (R1 - R2) * 0.9999999 - 1e-9;
-      if (rin > 0 && xa * xa + ya * ya < rin * rin && xb * xb + yb * yb < rin * rin) return;
+      const double rin = ODW_DER(2, (R1 - R2) * 0.9999999 - 1e-9);
+      if (rin > 0 && xa * xa + ya * ya < ODW_DER(3, rin * rin) && xb * xb + yb * yb < ODW_DER(3, rin * rin)) return;
     }
     // Crossings of the tube surface by marching the exact distance function
     // f(s) = |(rho - R1, z)| - R2 (|df/ds| <= 1, so a step of |f| cannot
@@ -893,6 +921,7 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       consider<RQ>(sv, q, t, p, f, group, cond_off, cond_cnt);
     }
   }
+#undef ODW_DER
 }
 
 // squared distance of the point w from the segment 0 -> e
@@ -999,6 +1028,22 @@ __device__ __forceinline__ bool ray_box(P bx, d3 oi, d3 inv, double tmax) {
   return hi >= fmax(lo, 0.0) && lo < tmax;
 }
 
+// The same screen on a box of the value image (compiled kernels): bx = centre xyz, half extent xyz, the half extent
+// rounded outward by the host (odw_build.h: spec_image_build).  With a = c inv - o inv the planes of an axis lie at
+// a -+ h |inv|, nearer first whatever the sign of inv: three fma per axis, no min / max to order the pair (the
+// absolute value and the negation are source modifiers).  A zero direction component: inv is NaN, so is every
+// distance of that axis, and it drops out of fmin / fmax as above.
+template <class P>
+__device__ __forceinline__ bool ray_box_centred(P bx, d3 oi, d3 inv, double tmax) {
+  double a = fma(bx[0], inv.x, -oi.x), w = fabs(inv.x);
+  double lo = fma(-bx[3], w, a), hi = fma(bx[3], w, a);
+  a = fma(bx[1], inv.y, -oi.y); w = fabs(inv.y);
+  lo = fmax(lo, fma(-bx[4], w, a)); hi = fmin(hi, fma(bx[4], w, a));
+  a = fma(bx[2], inv.z, -oi.z); w = fabs(inv.z);
+  lo = fmax(lo, fma(-bx[5], w, a)); hi = fmin(hi, fma(bx[5], w, a));
+  return hi >= fmax(lo, 0.0) && lo < tmax;
+}
+
 // findNearestIntersection (ray.py:290-452).  Returns prim (<0: none).
 // BVH=false: flat loop, wave-uniform primitive index (scalar loads), each
 //            primitive culled by its bounding box first -- the analogue of the
@@ -1026,9 +1071,9 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
         in_box = boxhit[SPEC::box_of(PI)];
       } else {
         const double cut = q.cut;
-        in_box = ray_box(sv.prim_hdr + 8 * PI, oi, inv, cut);
+        in_box = ray_box_centred(sv.img + SPEC::box(PI), oi, inv, cut);
 #if ODW_DOUBLE == 1
-        in_box = in_box & ray_box(sv.prim_hdr + 8 * PI, mk(opq(oi.x), oi.y, oi.z), inv, cut);
+        in_box = in_box & ray_box_centred(sv.img + SPEC::box(PI), mk(opq(oi.x), oi.y, oi.z), inv, cut);
 #endif
       }
       boxhit[PI] = in_box;
@@ -1046,7 +1091,7 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
     } else if constexpr (SPEC::box_of(PI) == PI) {
       // (skipped for this lane -- not relevant, or the convex solid just left --, but a later primitive may
       //  ask for this box: its own test then)
-      boxhit[PI] = SPEC::box_shared(PI) ? ray_box(sv.prim_hdr + 8 * PI, oi, inv, q.cut) : false;
+      boxhit[PI] = SPEC::box_shared(PI) ? ray_box_centred(sv.img + SPEC::box(PI), oi, inv, q.cut) : false;
     }
   }
 }
@@ -1064,7 +1109,9 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
                                        uint64_t mask, double& t_hit, int& face,
                                        int* __restrict__ stack, int skip_solid, int only_solid = -1) {
   Query q;
-  q.start = start; q.dn = dn; q.tol = lim.dist_tol; q.tmax = lim.max_ray_length + lim.dist_tol;
+  q.start = start; q.dn = dn;
+  if constexpr (SPEC::enabled) { q.tol = sv.lim[0]; q.tmax = sv.lim[1]; }
+  else { q.tol = lim.dist_tol; q.tmax = lim.max_ray_length + lim.dist_tol; }
   q.medium = medium;
   q.in_medium = __ballot(medium >= 0) != 0ull;
   q.cut = q.tmax;
@@ -1205,7 +1252,7 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
   if constexpr (SPEC::enabled) {
     // (consider_spec keeps primitive << 8 | face in the `face` member)
     if (q.any.face == 0x7fffffff) return -1;
-    const bool use_oth_ = q.oth.face != 0x7fffffff && q.oth.t < q.any.t + 2.0 * q.tol;
+    const bool use_oth_ = q.oth.face != 0x7fffffff && q.oth.t < q.any.t + sv.lim[2];
     t_hit = use_oth_ ? q.oth.t : q.any.t;
     const int key = use_oth_ ? q.oth.face : q.any.face;
     face = key & 0xff;
@@ -1710,13 +1757,14 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
                                          uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
                                          int& skip, int& only, bool& alive) {
   constexpr int flags = SPEC::flags(PI), g = SPEC::group(PI);
-  cf64 pf = sv.prim_f64 + (size_t)PI * 16;
-  d3 n = face_normal<SPEC::rare()>(SPEC::type(PI), pf + 12, face, xf_point_nz<SPEC::xf(PI)>(pf, point));
+  const PackedFrame<SPEC::xf(PI)> pf{sv.img + SPEC::frame(PI)};
+  cf64 par = sv.img + SPEC::par(PI);
+  d3 n = face_normal<SPEC::rare()>(SPEC::type(PI), par, face, xf_point_nz<SPEC::xf(PI)>(pf, point));
   if constexpr ((flags & ODW_FLAG_FLIP_NORMAL) != 0) n = n * -1.0;
   n = xf_vec_t_nz<SPEC::xf(PI)>(pf, n);
 #if ODW_DOUBLE == 6
   {
-    d3 n2 = face_normal<SPEC::rare()>(SPEC::type(PI), pf + 12, face, xf_point_nz<SPEC::xf(PI)>(pf, mk(opq(point.x), point.y, point.z)));
+    d3 n2 = face_normal<SPEC::rare()>(SPEC::type(PI), par, face, xf_point_nz<SPEC::xf(PI)>(pf, mk(opq(point.x), point.y, point.z)));
     if constexpr ((flags & ODW_FLAG_FLIP_NORMAL) != 0) n2 = n2 * -1.0;
     n2 = xf_vec_t_nz<SPEC::xf(PI)>(pf, n2);
     n = n2.x == n.x ? n : n2;
@@ -1822,6 +1870,19 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   ci32 group_i32 = as_const(sc.group_i32);
   cf64 group_gdir = as_const(sc.group_gdir);
   cu64 seq_mask = as_const(sc.seq_mask);
+  if constexpr (SPEC::enabled) {
+    // a compiled kernel reads every value from its scene's image (odw_build.h), found behind TraceParams in the kernel
+    // arguments (SpecTail): the image itself where it fits them, else its limits section and its device address.
+    // One base, constant offsets.
+    cf64 tail = (cf64)((const char ODW_CONST*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(TraceParams) + 7) & ~(size_t)7));
+    sv.lim = tail + 1;
+    if constexpr (SPEC::img_fits && !BATCH) sv.img = tail + 1;
+    else sv.img = as_const(*(const double* const ODW_CONST*)tail);
+    sv.prim_f64 = sv.prim_hdr = nullptr;
+    group_f64 = sv.img + SPEC::gf;
+    group_gdir = sv.img + SPEC::gd;
+    group_i32 = (ci32)(sv.img + SPEC::gi);
+  }
   // BATCH: the scene the wave's rays belong to, and the scene of the hand-out unit it holds (wave-uniform)
   uint32_t scene = 0, unit_scene = 0;
   // Persistent waves with ray regeneration.  Rays are handed out in chunks of
@@ -1898,10 +1959,18 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
           close_hit_block(P, hit_lds + (threadIdx.x >> 6) * 4, unit_scene);    // (closes the old scene's block, notes the new scene)
           scene = unit_scene;
           const size_t off = (size_t)scene * (size_t)P.batch.stride;
+          if constexpr (SPEC::enabled) {
+            cf64 tail = (cf64)((const char ODW_CONST*)__builtin_amdgcn_kernarg_segment_ptr() + ((sizeof(TraceParams) + 7) & ~(size_t)7));
+            sv.img = as_const(*(const double* const ODW_CONST*)tail + off);
+            group_f64 = sv.img + SPEC::gf;
+            group_gdir = sv.img + SPEC::gd;
+            group_i32 = (ci32)(sv.img + SPEC::gi);
+          } else {
           sv.prim_f64 = as_const(sc.prim_f64 + off);
           sv.prim_hdr = as_const(sc.prim_hdr + off);
           group_f64 = as_const(sc.group_f64 + off);
           group_gdir = as_const(sc.group_gdir + off);
+          }
         }
       }
       const uint32_t rank = __popcll(idle & ((1ull << lane) - 1ull));
@@ -2088,7 +2157,17 @@ __global__ __launch_bounds__(256, BVH ? ODW_WAVES_PER_SIMD_BVH : ODW_WAVES_PER_S
 #ifndef ODW_SPEC_SOURCE            // the header carries `struct SpecSource` and names it here when a source is bound
 #define ODW_SPEC_SOURCE NoSource
 #endif
-extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(const TraceParams P) {
+// What follows TraceParams in the arguments (odw_spec.hip: spec_launch): the device address of the value image (batches,
+// images beyond the arguments; else null) and the image -- all of it, or its limits section alone.  Read through the
+// argument segment's address (trace_body), never through this parameter: it only makes the room.
+template <int N>
+struct SpecTail {
+  const double* image;
+  double v[N];
+};
+extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(
+    const TraceParams P, const SpecTail<(Spec::img_fits && !ODW_SPEC_BATCH) ? Spec::IMG : 4> T) {
+  (void)T;
   trace_body<false, ODW_SPEC_STOCH, false, ODW_SPEC_LEAN, Spec, ODW_SPEC_BATCH, ODW_SPEC_POWER, ODW_SPEC_SOURCE>(P);
 }
 #endif

@@ -9,7 +9,9 @@
 // against it with hiprtc (0.5 - 2 s), and launches that kernel instead of the generic one: the
 // primitive loop is unrolled, type dispatch and face masks fold away, frame products skip their zero
 // terms, table reads have constant offsets (odw_kernels.hip: SPEC).  All float64 VALUES (frames,
-// parameters, boxes, optical constants) are still read from the uploaded tables, so one kernel serves
+// parameters, boxes, optical constants, and what intersect_prim derives from parameters and tolerance) are
+// run-time data still -- one dense block of doubles per scene, the value image (odw_build.h: spec_image_build),
+// laid out for the structure and handed over with the kernel arguments (spec_launch) --, so one kernel serves
 // every scene of the same structure: a parameter sweep compiles once.  (Values as literals of the
 // kernel were tried as a second level: 13.1 against 12.2 ms per 1e8 C3 rays -- the constants crowd the
 // scalar registers, 56 spilled -- and rounding no longer matched the generic kernel; not kept.)
@@ -118,17 +120,7 @@ std::string spec_ineligible(const HostScene& hs) {
   return "";
 }
 
-// zero / +-1 pattern of a frame's 12 entries (odw_kernels.hip: xf_comb): bits 0-11 entry != 0, 12-23 entry == +1,
-// 24-35 entry == -1 (rotation part only)
-unsigned long long xf_pattern(const double* m) {
-  unsigned long long w = 0;
-  for (int i = 0; i < 12; ++i) {
-    if (m[i] != 0.0) w |= 1ull << i;
-    if (i % 4 != 3 && m[i] == 1.0) w |= 1ull << (12 + i);
-    if (i % 4 != 3 && m[i] == -1.0) w |= 1ull << (24 + i);
-  }
-  return w;
-}
+// (xf_pattern, the zero / +-1 pattern of a frame: odw_build.h)
 
 // The structure of a table source as one word: what `struct SpecSource` says (0 = no such source).  Kept by the
 // context for the source it holds (source_key) and for the kernel it has bound (spec_source_key): a launch that
@@ -171,35 +163,9 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
     dead[p] = facemask == 0;
     xf[p] = xf_pattern(&hs.prim_f64[16 * (size_t)p]);
   }
-  // primitives with the same box: equal sets {p} + {q : p must lie inside q} (compute_boxes cuts p's box by
-  // the boxes of those q), one set per clause of a trimming list of several (compute_boxes: the union over the
-  // clauses of such cuts -- equal sets of sets, equal boxes).  box_of = the first such primitive, box_shared =
-  // another one refers to it.
-  std::vector<int> box_of(n), box_shared(n, 0);
-  {
-    std::vector<std::vector<std::vector<int>>> inside(n);
-    for (int p = 0; p < n; ++p) {
-      const int off = condw[p] & 0xffffff, cnt = (condw[p] >> 24) & 0xff;
-      const int end = std::min(off + cnt, (int)hs.cond.size());
-      inside[p].push_back({p});
-      for (int c = off; c < end; ++c) {
-        if (c != off && cond_opens(hs.cond[c])) inside[p].push_back({p});
-        if (hs.cond[c] < 0) inside[p].back().push_back(cond_operand(hs.cond[c]));
-      }
-      for (std::vector<int>& set : inside[p]) {
-        std::sort(set.begin(), set.end());
-        set.erase(std::unique(set.begin(), set.end()), set.end());
-      }
-      std::sort(inside[p].begin(), inside[p].end());
-    }
-    for (int p = 0; p < n; ++p) {
-      box_of[p] = p;
-      // (the sets are equal, but compute_boxes cuts with the operands' FULL boxes only: p's box is
-      //  box(p) ^ box(q1) ^ ..., the same expression for both when the sets agree)
-      for (int q = 0; q < p; ++q)
-        if (!dead[q] && !dead[p] && group[q] == group[p] && inside[q] == inside[p]) { box_of[p] = q; box_shared[q] = 1; break; }
-    }
-  }
+  // primitives with the same box, and where the kernel finds every value it reads (odw_build.h: the value image)
+  const SpecLayout L = spec_image_layout(hs);
+  const std::vector<int>&box_of = L.box_of, &box_shared = L.box_shared;
   std::vector<int> gtype(std::max(1, ng)), grec(std::max(1, ng));
   for (int g = 0; g < ng; ++g) { gtype[g] = hs.group_i32[4 * g]; grec[g] = hs.group_i32[4 * g + 1]; }
   auto fi = [](int v) { return std::to_string(v); };
@@ -226,6 +192,12 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
   // than the extra predicate on every primitive costs (11.85 against 11.30 ms, 8 spilled SGPRs).  The rule
   // never changes a result, so the two kernels still produce the same rows.
   s += "  static constexpr bool isolated() { return false; }\n";
+  // the value image: its size, whether it travels in the kernel arguments, and the offset of every piece
+  s += "  static constexpr int IMG = " + std::to_string(L.size) + ";\n";
+  s += std::string("  static constexpr bool img_fits = ") + (L.fits(sizeof(TraceParams)) ? "true" : "false") + ";\n";
+  s += "  static constexpr int gf = " + std::to_string(L.gf) + ", gd = " + std::to_string(L.gd) + ", gi = " + std::to_string(L.gi) + ";\n";
+  s += table("int", "frame", n, L.frame.data(), fi) + table("int", "par", n, L.par.data(), fi) +
+       table("int", "box", n, L.box.data(), fi) + table("int", "der", n, L.der.data(), fi);
   s += "  static constexpr int cond_off(int i) { return cond_word(i) & 0xffffff; }\n"
        "  static constexpr int cond_cnt(int i) { return (cond_word(i) >> 24) & 0xff; }\n";
   s += "  static constexpr unsigned long long umask() { return " + fu(hs.all_mask & ~hs.ignore_mask) + "; }\n";
@@ -410,6 +382,10 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   }
   if (ctx->compile_mode == ODW_COMPILE_OFF || !ctx->have_scene) return ODW_OK;
   if (!spec_ineligible(ctx->hs).empty()) return ODW_OK;
+  if (!batch) {                                   // (the variants share the single-scene kernel's layout)
+    ctx->spec_layout = spec_image_layout(ctx->hs);
+    ctx->spec_image_host.clear();
+  }
   hipDeviceProp_t prop;
   HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
   const std::string arch = prop.gcnArchName;
@@ -520,10 +496,41 @@ void spec_note_launch(odw_ctx* ctx, uint64_t n_rays) {
   if (jt == G.jobs.end() || jt->second->done.load()) ctx->spec_dirty = true;
 }
 
-int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn) {
-  TraceParams P = ctx->P;
-  size_t size = sizeof P;
-  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &P, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+// Launch of a compiled kernel.  Its arguments: TraceParams | the image's device address | the image itself where it
+// fits (single-scene launches), else its limits section alone (odw_kernels.hip: SpecTail).  The image is built here, from
+// the host tables and limits in force at this very launch: whatever changed values under the bound structure --
+// another scene of a sweep, other limits -- is in it.  An image too large for the arguments goes to device memory when
+// it differs from the one there; a batch's images lie in its blocks (odw_upload_scene_batch), one per scene.
+int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch) {
+  const SpecLayout& L = ctx->spec_layout;
+  if (L.n != ctx->hs.n_prims || L.size < kSpecImageLimits) return fail(ctx, ODW_ERR_DEVICE, "compiled kernel without its value image");
+  constexpr size_t tail = (sizeof(TraceParams) + 7) & ~(size_t)7;
+  const bool resident = !batch && L.fits(sizeof(TraceParams));
+  std::vector<double>& img = ctx->spec_image_now;
+  img.resize((size_t)L.size);
+  spec_image_build(ctx->hs, ctx->P.lim, L, img.data());
+  const double* dev = nullptr;
+  if (batch) {
+    if (!ctx->batch_img_off) return fail(ctx, ODW_ERR_DEVICE, "batch without value images");
+    dev = (const double*)ctx->batch_values.p + ctx->batch_img_off;
+  } else if (!resident) {
+    std::vector<double>& there = ctx->spec_image_host;
+    if (there.size() != img.size() || std::memcmp(there.data(), img.data(), img.size() * sizeof(double)) != 0) {
+      there.clear();
+      int rc = upload(ctx, ctx->spec_image, img.data(), img.size() * sizeof(double));
+      if (rc) return rc;
+      there = img;
+    }
+    dev = (const double*)ctx->spec_image.p;
+  }
+  const size_t nv = resident ? (size_t)L.size : (size_t)kSpecImageLimits;
+  std::vector<char>& args = ctx->spec_args;
+  args.assign(tail + sizeof(double*) + nv * sizeof(double), 0);
+  std::memcpy(args.data(), &ctx->P, sizeof(TraceParams));
+  std::memcpy(args.data() + tail, &dev, sizeof dev);
+  std::memcpy(args.data() + tail + sizeof dev, img.data(), nv * sizeof(double));
+  size_t size = args.size();
+  void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   HIPCHK(ctx, hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, ctx->stream, nullptr, config));
   return ODW_OK;
 }

@@ -625,6 +625,26 @@ int odw_build_check(const odw_scene_desc* scene, const odw_limits* limits, int32
  * Replaces nothing of the reference (numpy computes the slope per sample).
  * (An entry point more, no descriptor or row layout changed: still v12.)      */
 int odw_table_slopes(const double* cdf, const double* edges, int32_t n_tables, int32_t n_knots, double* slopes);
+/* no device needed: the value image of the kernel compiled against `scene` -- the one block of doubles its
+ * unrolled loop reads at compile-time offsets -- for `limits`, and where its pieces lie.
+ * image [image_capacity] (may be NULL), *image_size = its doubles: [0] distTol, [1] maxRayLength + distTol,
+ * [2] 2 distTol, [3] 0; per group the optical constants (4), the grating direction (3) and its four
+ * integers (optical type, record, grating type, grating order: two doubles' room); per primitive the frame
+ * entries that are neither 0 nor +-1 in index order, its 4 parameters, centre xyz and half extent xyz of its
+ * box (the half extent rounded outward: [c - h, c + h] holds the box the generic kernels screen with), and the
+ * constants its intersection derives from parameters and tolerance: box S_i + tol (3); cylinder, cone,
+ * paraboloid H + tol, R1 R1 (1 - 1e-9), (R1 + tol)^2, (R2 + tol)^2; torus bound, slab half height, inner
+ * radius, its square.
+ * offsets [offsets_capacity >= 3 + 5 n_prims] (may be NULL): group_f64, group_gdir, group_i32 sections, then
+ * per primitive: frame, parameters, box (-1: it shares another's or has no face), derived (-1: none), the
+ * primitive whose box it is screened with.
+ * boxes [6 n_prims] (may be NULL): lo xyz, hi xyz of every primitive's box as the generic kernels screen with it.
+ * in_arguments: 1 if a single-scene launch carries the image in its kernel arguments, 0 if it reads it from
+ * device memory.  ODW_ERR_UNSUPPORTED: the scene is outside the compiled kernels' domain.
+ * Replaces nothing of the reference.  (An entry point more, no descriptor or row layout changed: still v12.) */
+int odw_spec_image(const odw_scene_desc* scene, const odw_limits* limits, double* image, uint64_t image_capacity,
+                   uint64_t* image_size, int32_t* offsets, uint64_t offsets_capacity, double* boxes,
+                   int32_t* in_arguments);
 
 /* ---- batches: many scenes of ONE structure in one launch (v9) -----------
  * Replaces the loop of a parameter sweep (examples/1-getting-started/

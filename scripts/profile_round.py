@@ -55,7 +55,9 @@ if args.script:
 def run(cmd, log):
   print('+', ' '.join(cmd), flush=True)
   with open(os.path.join(out, log), 'w') as f:
-    subprocess.run(cmd, cwd=ROOT, env=env, stdout=f, stderr=subprocess.STDOUT, check=True)
+    # (a time limit per pass; a pass that fails or runs into it ends the whole collection: nothing more is started on
+    #  a GPU that may have faulted)
+    subprocess.run(cmd, cwd=ROOT, env=env, stdout=f, stderr=subprocess.STDOUT, check=True, timeout=600)
 
 
 def db_of(folder):
@@ -72,7 +74,7 @@ def tables(con):
 # 1. the bench line
 if not args.no_bench:
   res = subprocess.run(['python3', os.path.join(ROOT, 'bench.py'), '--config', args.config, '--no-extra', '--full'], cwd=ROOT, env=env,
-                       capture_output=True, text=True, check=True)
+                       capture_output=True, text=True, check=True, timeout=900)
   line = [l for l in res.stdout.splitlines() if l.startswith('{')][-1]
   open(os.path.join(out, f'{tag}_bench.json'), 'w').write(line + '\n')
   print(line[:200], flush=True)
@@ -129,9 +131,8 @@ for k, cs in enumerate(sets):
   d = os.path.join(out, f'{tag}_pmc{k}')
   try:
     run(['rocprofv3', '--pmc'] + cs + ['--kernel-trace', '-d', d, '--'] + BENCH, f'{tag}_pmc{k}.log')
-  except subprocess.CalledProcessError as e:
-    print('counter set failed:', cs, e, flush=True)
-    continue
+  except (subprocess.CalledProcessError, subprocess.TimeoutExpired) as e:
+    raise SystemExit(f'counter set failed: {cs}: {e}')
   con = db_of(d)
   view = [t for t in tables(con) if t.startswith('counters_collection')]
   cols = [c[1] for c in con.execute(f'pragma table_info({view[0]})')]
