@@ -28,7 +28,7 @@ CNT_NAMES = ['traced_rays', 'recorded_hits', 'segments', 'escaped', 'died', 'cap
 TRACE_RECORD_HITS, TRACE_HISTOGRAM, TRACE_RECORD_SEGMENTS, TRACE_POWER_HISTOGRAM = 1, 2, 4, 8
 POWER_QUANTUM_BITS = 32                   # ODW_POWER_QUANTUM_BITS: a hit's weight is rint(clamp(power, 0, 2^20) * 2^32)
 FLAG_FLIP_NORMAL, FLAG_CONVEX = 1, 2      # ODW_FLAG_* of prim_flags (include/odw_trace.h)
-PRIM_PARABOLOID, PRIM_ELLIPSOID = 6, 7    # ODW_PRIM_*: the rare quadrics (scene.geometry holds the whole list of kinds)
+PRIM_PARABOLOID, PRIM_ELLIPSOID, PRIM_CONICOID = 6, 7, 8    # ODW_PRIM_*: the rare quadrics (scene.geometry holds the whole list of kinds)
 COMPILE_OFF, COMPILE_STRUCTURE, COMPILE_AUTO = 0, 1, 2
 COMPILE_MODES = {None: 0, False: 0, 'off': 0, 0: 0, 'structure': 1, 1: 1, True: 1, 'auto': 2, 2: 2}
 ERRORS = {1: 'invalid argument', 2: 'device error', 3: 'no scene', 4: 'capacity', 5: 'unsupported'}

@@ -104,7 +104,7 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
   hs.prim_i32.assign((size_t)n * 4, 0);
   for (int p = 0; p < n; ++p) {
     const int type = s->prim_type[p], group = s->prim_group[p];
-    if (type < ODW_PRIM_BOX || type > ODW_PRIM_ELLIPSOID) return refuse(err, ODW_ERR_UNSUPPORTED, "unknown primitive type");
+    if (type < ODW_PRIM_BOX || type > ODW_PRIM_CONICOID) return refuse(err, ODW_ERR_UNSUPPORTED, "unknown primitive type");
     if (group < 0 || group >= s->n_groups) return refuse(err, ODW_ERR_INVALID, "primitive group out of range");
     const int off = s->prim_cond_off[p], cnt = s->prim_cond_off[p + 1] - off;
     if (off < 0 || cnt < 0 || cnt > 255 || off + cnt > s->n_conds)
@@ -153,6 +153,21 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
         const double* par = &hs.prim_f64[16 * (size_t)p + 12];
         for (int k = 0; k < 3; ++k)
           if (!(par[k] > 0) || !std::isfinite(par[k])) return refuse(err, ODW_ERR_INVALID, "ellipsoid: the three radii must be positive");
+      }
+      if (type == ODW_PRIM_CONICOID) {
+        // faces 0 (the conic surface) and 2 (the cap z = H); there is no face 1, the vertex is a point
+        if (((s->prim_flags[p] >> ODW_FACEMASK_SHIFT) & 0xff) & ~5)
+          return refuse(err, ODW_ERR_UNSUPPORTED, "conicoid: faces 0 (surface) and 2 (cap at z = H) only");
+        double* par = &hs.prim_f64[16 * (size_t)p + 12];
+        const double R = par[0], K = par[1], H = par[2];
+        if (!(R > 0) || !std::isfinite(R) || !std::isfinite(K) || !(H > 0) || !std::isfinite(H))
+          return refuse(err, ODW_ERR_INVALID, "conicoid: vertex radius and height must be positive and finite, the conic constant finite");
+        // (K > -1: the solid ends at or before the equator z = R / (1 + K), where the surface stops being a graph over rho)
+        if (K > -1.0 && !(H <= R / (1.0 + K)))
+          return refuse(err, ODW_ERR_INVALID, "conicoid: for K > -1 the height must not exceed R / (1 + K)");
+        const double rim2 = 2.0 * R * H - (1.0 + K) * H * H;
+        if (!(rim2 > 0) || !std::isfinite(rim2)) return refuse(err, ODW_ERR_INVALID, "conicoid: no rim at this height");
+        par[3] = std::sqrt(rim2);                              // rim radius at z = H
       }
     }
     hs.prim_i32[4 * p] = type;
@@ -234,6 +249,9 @@ void local_bounds(int type, const double* par, double lo[3], double hi[3]) {
     }
     case ODW_PRIM_ELLIPSOID:
       for (int i = 0; i < 3; ++i) { lo[i] = -par[i]; hi[i] = par[i]; }
+      break;
+    case ODW_PRIM_CONICOID:   // (0 <= z <= H lies at or before the equator: the rim is the widest parallel)
+      lo[0] = lo[1] = -par[3]; hi[0] = hi[1] = par[3]; lo[2] = 0; hi[2] = par[2];
       break;
     default: {  // torus
       const double r = par[0] + par[1];
@@ -1082,6 +1100,7 @@ inline int spec_derived_count(int type) {
   switch (type) {
     case ODW_PRIM_BOX: return 3;
     case ODW_PRIM_CYLINDER: case ODW_PRIM_CONE: case ODW_PRIM_PARABOLOID: case ODW_PRIM_TORUS: return 4;
+    case ODW_PRIM_CONICOID: return 3;
     default: return 0;
   }
 }
@@ -1158,6 +1177,10 @@ inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const
       d[1] = std::fma(R2, 1.0000001, 1e-9);                               // zs
       d[2] = std::fma(R1 - R2, 0.9999999, -1e-9);                         // rin
       d[3] = d[2] * d[2];
+    } else if (type == ODW_PRIM_CONICOID) {
+      d[0] = par[2] + tol;                                                // the z window's upper end
+      d[1] = (par[3] + tol) * (par[3] + tol);                             // the cap's disc
+      d[2] = 1.0 + par[1];                                                // the z^2 coefficient
     } else {
       const bool parab = type == ODW_PRIM_PARABOLOID;
       const double R1 = parab ? 0.0 : par[0];
@@ -1171,14 +1194,14 @@ inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const
   }
 }
 
-// A scene the flat loop would take but for its rare quadrics (paraboloids, ellipsoids: build_accel gives it a grid and a
+// A scene the flat loop would take but for its rare quadrics (paraboloids, ellipsoids, conicoids: build_accel gives it a grid and a
 // tree, since the generic flat kernel leaves their code out): a kernel compiled against it needs neither
 bool flat_but_for_rare_quadrics(const HostScene& hs, int flat_limit) {
   bool rare = false;
   for (int p = 0; p < hs.n_prims; ++p) {
     const int t = hs.prim_i32[4 * p];
     if (t == ODW_PRIM_TRIANGLE) return false;
-    rare |= t == ODW_PRIM_PARABOLOID || t == ODW_PRIM_ELLIPSOID;
+    rare |= t == ODW_PRIM_PARABOLOID || t == ODW_PRIM_ELLIPSOID || t == ODW_PRIM_CONICOID;
   }
   return rare && hs.n_prims <= flat_limit;
 }
@@ -1194,7 +1217,8 @@ int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, in
   for (int p = 0; p < n; ++p) {
     has_triangles |= hs.prim_i32[4 * p] == ODW_PRIM_TRIANGLE;
     has_paraboloids |= hs.prim_i32[4 * p] == ODW_PRIM_PARABOLOID;
-    has_ellipsoids |= hs.prim_i32[4 * p] == ODW_PRIM_ELLIPSOID;
+    // (conicoids go where ellipsoids go: known to the binary tree and the grid kernel's item branch)
+    has_ellipsoids |= hs.prim_i32[4 * p] == ODW_PRIM_ELLIPSOID || hs.prim_i32[4 * p] == ODW_PRIM_CONICOID;
   }
   // (triangles are only known to the BVH kernels, paraboloids to the BVH and grid kernels, ellipsoids to the binary
   //  tree and the grid kernel: beside facets they take the binary tree, not the mesh kernel's eight-wide one)

@@ -1319,8 +1319,11 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   std::vector<double> pf((size_t)n * 16);
   std::vector<int32_t> pi((size_t)n * 4);
   for (int p = 0; p < n; ++p) {
-    if (s->prim_type[p] < ODW_PRIM_BOX || s->prim_type[p] > ODW_PRIM_ELLIPSOID)
+    if (s->prim_type[p] < ODW_PRIM_BOX || s->prim_type[p] > ODW_PRIM_CONICOID)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: unknown primitive kind");
+    // (nor conicoid code: the emitter rides along in every compiled code object and stays what it is)
+    if (s->prim_type[p] == ODW_PRIM_CONICOID)
+      return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: a conicoid is not built, neither as emitting faces nor as a trimming operand");
     // (the emitter kernel carries no ellipsoid code: neither an emitting face nor an operand of a trimming list)
     if (s->prim_type[p] == ODW_PRIM_ELLIPSOID)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: ellipsoids are not built, neither as emitting faces nor as trimming operands");
@@ -1346,7 +1349,7 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   }
   if (!clauses_marked(s->prim_cond_off, n, cond))
     return fail(ctx, ODW_ERR_INVALID, "surface source: a trimming list of several clauses must mark its first condition too");
-  static const int n_faces_of[8] = {6, 1, 3, 3, 1, 1, 0, 0};  // (paraboloid faces do not emit: rejected below; ellipsoids: above)
+  static const int n_faces_of[9] = {6, 1, 3, 3, 1, 1, 0, 0, 0};  // (paraboloid faces do not emit: rejected below; ellipsoids, conicoids: above)
   std::vector<int32_t> fi((size_t)s->n_faces * 2);
   std::vector<double> fc((size_t)s->n_faces + 1, 0.0);
   double total = 0;

@@ -333,16 +333,26 @@ __device__ __forceinline__ void make_ray(csource s, double t_or_r, double phi,
 }
 
 // ----------------------------------------------------------- primitives
-// RQ: the rare quadrics an instantiation knows (bit 0 paraboloids, bit 1 ellipsoids).  Paraboloids are known to
-// the BVH, grid and mesh kernels only (the flat kernel of the small benchmark scenes is sensitive to every
-// instruction in its loop: their branch cost it 1.1 %), ellipsoids to the BVH and grid kernels; a compiled kernel
-// knows what its scene holds (Spec::rare()).
+// RQ: the rare quadrics an instantiation knows (bit 0 paraboloids, bit 1 ellipsoids, bit 2 conicoids).  Paraboloids
+// are known to the BVH, grid and mesh kernels only (the flat kernel of the small benchmark scenes is sensitive to every
+// instruction in its loop: their branch cost it 1.1 %), ellipsoids and conicoids to the BVH and grid kernels; a
+// compiled kernel knows what its scene holds (Spec::rare()).
 #define ODW_RQ_PARAB 1
 #define ODW_RQ_ELLIPSOID 2
-#define ODW_RQ_ALL 3
+#define ODW_RQ_CONICOID 4
+#define ODW_RQ_ALL 7
 template <int RQ, class PP>
 __device__ __forceinline__ double prim_sdist(int type, PP par, d3 p) {
-  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0;
+  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
+  if (CON && type == ODW_PRIM_CONICOID) {
+    // q = x^2 + y^2 + (1 + K) z^2 - 2 R z over the length of its gradient g = (x, y, (1 + K) z - R): half of it is the
+    // distance to first order, as for the paraboloid and the ellipsoid (the floor: the gradient vanishes at the
+    // centre of an ellipsoidal cap's full solid).  -z keeps the other sheet of a hyperboloid (K < -1) outside.
+    const double kk = 1.0 + par[1];
+    const double r2 = p.x * p.x + p.y * p.y, gz = kk * p.z - par[0];
+    const double lat = (r2 + (kk * p.z - 2.0 * par[0]) * p.z) * 0.5 * frsqrt(fmax(r2 + gz * gz, 1e-300));
+    return fmax(lat, fmax(p.z - par[2], -p.z));
+  }
   if (ELL && type == ODW_PRIM_ELLIPSOID) {
     // q = sum (x_i / r_i)^2 against 1 over the length of its gradient: the distance to first order, as for the
     // paraboloid (at the centre the gradient vanishes: the floor keeps the answer "deep inside", not NaN)
@@ -589,7 +599,7 @@ __device__ __forceinline__ void cand_min2(Cands& c, double t, int f) {
 template <int RQ = ODW_RQ_ALL, class SPEC = NoSpec, int PI = 0>
 __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, int p, int type, int group,
                                                int flags, int cond_word) {
-  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0;
+  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
   cf64 pf = sv.prim_f64 + (size_t)p * 16;
   const int cond_off = cond_word & 0xffffff, cond_cnt = (cond_word >> 24) & 0xff;
   const int fmask = (flags >> ODW_FACEMASK_SHIFT) & 0xff;
@@ -773,6 +783,30 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
         c.t1 = t1;
       }
     }
+  } else if (CON && type == ODW_PRIM_CONICOID) {
+    // the conic of revolution x^2 + y^2 + (1 + K) z^2 = 2 R z, 0 <= z <= H (params R, K, H, rim): both roots with
+    // face 0 inside the z window -- for K < -1 the leading coefficient can vanish or turn negative (a ray along or
+    // steeper than an asymptote: quad_roots copes, as for the cone) and z >= -tol drops the roots on the other sheet --
+    // and the cap z = H, face 2, in slot 3 as on the paraboloid.  Conditions without short-circuit evaluation.
+    const double R = par[0], H = par[2];
+    const double kk = ODW_DER(2, 1.0 + par[1]);
+    if (fmask & 1) {
+      const double ht = ODW_DER(0, H + tol);
+      double t0 = INFINITY, t1 = INFINITY;
+      const int nr = quad_roots(d.x * d.x + d.y * d.y + kk * d.z * d.z,
+                                o.x * d.x + o.y * d.y + (kk * o.z - R) * d.z,
+                                o.x * o.x + o.y * o.y + (kk * o.z - 2.0 * R) * o.z, t0, t1);
+      const double z0 = o.z + t0 * d.z, z1 = o.z + t1 * d.z;
+      c.t0 = (bool)((int)(nr >= 1) & (int)(z0 >= -tol) & (int)(z0 <= ht)) ? t0 : c.t0;
+      c.t1 = (bool)((int)(nr == 2) & (int)(z1 >= -tol) & (int)(z1 <= ht)) ? t1 : c.t1;
+    }
+    if (fmask & 4) {
+      const double tb = (H - o.z) * frcp(d.z);
+      const double xb = o.x + tb * d.x, yb = o.y + tb * d.y;
+      const bool w_ = xb * xb + yb * yb <= ODW_DER(1, (par[3] + tol) * (par[3] + tol));
+      c.t3 = w_ ? tb : c.t3;
+      c.f3 = w_ ? 2 : c.f3;
+    }
   } else {  // torus
     if (!(fmask & 1)) return;
     const double R1 = par[0], R2 = par[1];
@@ -882,7 +916,7 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       // only the slots this primitive's type and faces can fill (the table of the trimmed branch below): an unfilled
       // slot holds (INF, 0), which never wins, but judging it is not free -- the compiler cannot tell
       constexpr int ty = SPEC::type(PI), fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
-      constexpr bool quadric = ty == ODW_PRIM_CYLINDER || ty == ODW_PRIM_CONE || ty == ODW_PRIM_PARABOLOID;
+      constexpr bool quadric = ty == ODW_PRIM_CYLINDER || ty == ODW_PRIM_CONE || ty == ODW_PRIM_PARABOLOID || ty == ODW_PRIM_CONICOID;
       constexpr bool pair = ty == ODW_PRIM_BOX || (fm & 1) != 0;      // box: entry / exit face; else the surface's two roots
       constexpr bool caps = ty != ODW_PRIM_BOX && ty != ODW_PRIM_SPHERE && ty != ODW_PRIM_ELLIPSOID;
       if constexpr (pair) {
@@ -904,7 +938,8 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     // (a sphere has two candidates; the trimming code exists once per candidate slot)
     // (faces that the boolean left nothing of produce no candidate: their slots are not looked at)
     constexpr int fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
-    constexpr bool quadric = SPEC::type(PI) == ODW_PRIM_CYLINDER || SPEC::type(PI) == ODW_PRIM_CONE || SPEC::type(PI) == ODW_PRIM_PARABOLOID;
+    constexpr bool quadric = SPEC::type(PI) == ODW_PRIM_CYLINDER || SPEC::type(PI) == ODW_PRIM_CONE || SPEC::type(PI) == ODW_PRIM_PARABOLOID ||
+                             SPEC::type(PI) == ODW_PRIM_CONICOID;
     if constexpr (!quadric || (fm & 1) != 0) {
       consider_spec<RQ, SPEC, PI>(sv, q, c.t0, c.f0);
       consider_spec<RQ, SPEC, PI>(sv, q, c.t1, c.f1);
@@ -984,7 +1019,7 @@ __device__ __forceinline__ d3 tri_normal(cf64 pf, const double* __restrict__ vn,
 // outward normal of face `face` of primitive p at local point lp
 template <int RQ = ODW_RQ_ALL>
 __device__ __forceinline__ d3 face_normal(int type, cf64 par, int face, d3 lp) {
-  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0;
+  constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
   if (type == ODW_PRIM_BOX) {
     const double s = (face & 1) ? 1.0 : -1.0;
     const int a = face >> 1;
@@ -1004,6 +1039,12 @@ __device__ __forceinline__ d3 face_normal(int type, cf64 par, int face, d3 lp) {
     // gradient of sum (x_i / r_i)^2
     const double sx = frcp(par[0]), sy = frcp(par[1]), sz = frcp(par[2]);
     const d3 g = mk(lp.x * sx * sx, lp.y * sy * sy, lp.z * sz * sz);
+    return g * frsqrt(dot(g, g));
+  }
+  if (CON && type == ODW_PRIM_CONICOID) {
+    // the cap, or the gradient of x^2 + y^2 + (1 + K) z^2 - 2 R z
+    if (face == 2) return mk(0, 0, 1);
+    const d3 g = mk(lp.x, lp.y, (1.0 + par[1]) * lp.z - par[0]);
     return g * frsqrt(dot(g, g));
   }
   const double f = 1.0 - par[0] * frsqrt(lp.x * lp.x + lp.y * lp.y);
@@ -2315,7 +2356,7 @@ __global__ __launch_bounds__(256) void odw_emit_kernel(const DeviceEmitter E, ui
         if (!ok) continue;
         const int qp = cond_operand(cw);
         const double* of = E.prim_f64 + (size_t)qp * 16;
-        // (the emitter's tables hold no ellipsoid: odw_upload_surface_source refuses them)
+        // (the emitter's tables hold neither ellipsoid nor conicoid: odw_upload_surface_source refuses them)
         const double sd = prim_sdist<ODW_RQ_PARAB>(E.prim_i32[4 * qp], of + 12, xf_point(of, gp));
         if (cw < 0 ? sd > E.dist_tol : sd < -E.dist_tol) ok = false;
       }

@@ -82,6 +82,18 @@ def makeParaboloid(doc, name='Paraboloid', focalLength=10.0, height=5.0, **pl):
                        FocalLength=float(focalLength), Height=float(height), Placement=_placement(**pl))
 
 
+def makeConicoid(doc, name='Conicoid', vertexRadius=10.0, conicConstant=-1.0, height=5.0, **pl):
+  """conic solid of revolution x^2 + y^2 + (1 + K) z^2 <= 2 R z, 0 <= z <= height in its own frame (vertex at the
+  origin, axis +z): the lens designer's surface rho^2 = 2 R z - (1 + K) z^2 with vertex radius R = vertexRadius and
+  conic constant K = conicConstant, closed by the plane z = height.  K < -1: one sheet of a hyperboloid, -1: the
+  paraboloid of focal length R / 2, -1 < K < 0: a prolate cap, 0: a spherical cap, K > 0: an oblate cap; for K > -1
+  the height ends at or before the equator, height <= R / (1 + K).  Traced as exact geometry (primitive kind 8)"""
+  return doc.addObject('Part::FeaturePython', name, Proxy={'module': 'freecad.optics_design_workbench_amd.scene.geometry',
+                                                             'class': 'Conicoid', 'state': {}},
+                       VertexRadius=float(vertexRadius), ConicConstant=float(conicConstant), Height=float(height),
+                       Placement=_placement(**pl))
+
+
 def makeCommon(doc, shapes, name='Common', **pl):
   return doc.addObject('Part::MultiCommon', name, Shapes=list(shapes), Placement=_placement(**pl))
 
@@ -92,6 +104,80 @@ def makeCut(doc, baseObject, toolObject, name='Cut', **pl):
 
 def makeFuse(doc, shapes, name='Fusion', **pl):
   return doc.addObject('Part::MultiFuse', name, Shapes=list(shapes), Placement=_placement(**pl))
+
+
+def _conicSag(rho, radius, conic):
+  """sag of the conic surface (signed radius, inf: flat) at the distance rho from the axis"""
+  if np.isinf(radius):
+    return 0.0
+  return rho * rho / (radius * (1.0 + np.sqrt(1.0 - (1.0 + conic) * rho * rho / (radius * radius))))
+
+
+def makeConicLens(doc, name='ConicLens', radius1=50.0, conic1=0.0, radius2=-50.0, conic2=0.0, thickness=5.0, diameter=20.0, **pl):
+  """a singlet on the local z axis, front vertex at the origin, back vertex at z = thickness: the solid
+  rho <= diameter / 2, sag1(rho) <= z <= thickness + sag2(rho), each surface the conic of its (radius, conic constant)
+  in lens design's sign convention -- a radius is positive when the centre of curvature lies towards +z from the
+  vertex, inf is flat.  Built from a cylinder blank: a convex face (radius1 > 0, radius2 < 0) by makeCommon with a
+  conicoid that holds the whole lens, a concave one by makeCut of a conicoid.  No two operand faces coincide: the blank
+  overshoots every vertex and edge it does not keep, the conicoids end beyond the blank.  ValueError when a surface
+  does not reach the edge, when a K > -1 surface would be needed beyond its equator (a conicoid is at most the half of
+  its spheroid), or when the edge thickness is not positive.  Returns the solid, placed by **pl: the caller puts it
+  into a lens group (makeLens)."""
+  r1, k1, r2, k2, t, a = float(radius1), float(conic1), float(radius2), float(conic2), float(thickness), float(diameter) / 2
+  if not (t > 0 and a > 0 and r1 != 0 and r2 != 0 and np.isfinite([k1, k2, t, a]).all()) or np.isnan(r1) or np.isnan(r2):
+    raise ValueError(f'{name}: thickness and diameter must be positive, radii non-zero, conic constants finite')
+  for r, k in ((r1, k1), (r2, k2)):
+    # the surface is real at the edge for (1 + K) a^2 <= R^2; at equality the edge is the equator itself, and the
+    # conicoid would have to go on beyond it
+    if not np.isinf(r) and (1.0 + k) * a * a > r * r:
+      raise ValueError(f'{name}: the surface R = {r}, K = {k} does not reach the edge at rho = {a}')
+  s1, s2 = float(_conicSag(a, r1, k1)), float(_conicSag(a, r2, k2))
+  if not t + s2 - s1 > 0:
+    raise ValueError(f'{name}: the edge thickness {t + s2 - s1} is not positive')
+  margin = 0.25 * max(t, a)
+
+  def equator(r, k):
+    return abs(r) / (1.0 + k) if k > -1.0 else np.inf
+
+  def overshoot(r, k, s):
+    # how far the blank passes the edge of a concave face: the tool has to pass the blank in turn, before its equator
+    return min(margin, 0.25 * (equator(r, k) - abs(s)))
+
+  def conicoid(tag, r, k, z, flip, need, over):
+    # the conicoid of a face, vertex at (0, 0, z), opening towards +z or (turned about x) -z, `need` high and `over`
+    # more (the caps of two conicoids that end on the same side of the blank must not coincide either)
+    if need + 0.01 * margin > equator(r, k):
+      raise ValueError(f'{name}: the surface R = {r}, K = {k} would be needed beyond its equator ({need} of {equator(r, k)} mm along the axis)')
+    return makeConicoid(doc, f'{name}{tag}', abs(r), k, min(need + over, equator(r, k)),
+                        base=(0.0, 0.0, z), quat=(1.0, 0.0, 0.0, 0.0) if flip else (0.0, 0.0, 0.0, 1.0))
+
+  # the blank: a flat face is the blank's own; past a convex vertex it overshoots by the margin (the Common takes that
+  # away), past the edge of a concave face by what the tool can still pass
+  z_lo = 0.0 if np.isinf(r1) else (-margin if r1 > 0 else s1 - overshoot(r1, k1, s1))
+  z_hi = t if np.isinf(r2) else (t + margin if r2 < 0 else t + s2 + overshoot(r2, k2, s2))
+  commons, cuts = [], []
+  if not np.isinf(r1):
+    if r1 > 0:    # convex: the lens lies inside the conicoid that opens towards +z from the front vertex
+      commons.append(conicoid('Front', r1, k1, 0.0, False, z_hi, margin))
+    else:         # concave: the conicoid that opens towards -z is taken out of the blank
+      cuts.append(conicoid('Front', r1, k1, 0.0, True, -z_lo, 2 * margin))
+  if not np.isinf(r2):
+    if r2 < 0:
+      commons.append(conicoid('Back', r2, k2, t, True, t - z_lo, margin))
+    else:
+      cuts.append(conicoid('Back', r2, k2, t, False, z_hi - t, 2 * margin))
+  steps = len(cuts) + (1 if commons else 0)
+  place = lambda last: pl if last else {}
+  blank_name = name if steps == 0 else f'{name}Blank'
+  solid = makeCylinder(doc, blank_name, a, z_hi - z_lo, **(dict(placement=_placement(**pl) * Placement(base=(0.0, 0.0, z_lo))) if steps == 0
+                                                            else dict(base=(0.0, 0.0, z_lo))))
+  if commons:
+    steps -= 1
+    solid = makeCommon(doc, [solid] + commons, name=name if steps == 0 else f'{name}Common', **place(steps == 0))
+  for tool in cuts:
+    steps -= 1
+    solid = makeCut(doc, solid, tool, name=name if steps == 0 else f'{name}Cut', **place(steps == 0))
+  return solid
 
 
 def makeOpticalGroup(doc, opticalType, elements, name=None, placement=None, **props):
@@ -169,7 +255,7 @@ def makeMesh(doc, vertices, triangles, vertexNormals=None, name='Mesh', **pl):
 
 
 def makeTessellated(doc, solid, segments=48, smooth=True, name=None):
-  """mesh of a primitive solid object (Part::Sphere / Ellipsoid / Cylinder / Cone / Torus / Box) at the same placement"""
+  """mesh of a primitive solid object (Part::Sphere / Ellipsoid / Cylinder / Cone / Torus / Box, paraboloid, conicoid) at the same placement"""
   from ..scene import geometry
   node = geometry._primitive_of(solid)
   if node is None:

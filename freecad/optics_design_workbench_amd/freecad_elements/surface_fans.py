@@ -106,6 +106,8 @@ def _primitive_face_table(kind, params, to_world, dist_tol):
                         lambda u, v: (wdir([1.0, 0.0, 0.0]), wdir([0.0, 1.0, 0.0])))
   elif kind == geometry.ELLIPSOID:
     raise geometry.UnsupportedGeometry('faces of an ellipsoid as fan grids are not built')
+  elif kind == geometry.CONICOID:
+    raise geometry.UnsupportedGeometry('faces of a conicoid as fan grids are not built')
   else:
     raise geometry.UnsupportedGeometry(f'no fan grid for primitive kind {kind}')
   return faces
@@ -140,6 +142,16 @@ def _ellipsoid_distance(q, p):
   return 0.5 * (np.sum((q / r)**2) - 1.0) / max(g, 1e-150)
 
 
+def _conicoid_distance(q, p):
+  """the kernels' trimming distance of the local point q from the conicoid (R, K, H, rim) (negative inside): first
+  order on the conic surface, exact on the planes z = 0 (which keeps a hyperboloid's other sheet out) and z = H"""
+  R, kk, h = p[0], 1.0 + p[1], p[2]
+  r2 = q[0] * q[0] + q[1] * q[1]
+  gz = kk * q[2] - R
+  lat = 0.5 * (r2 + (kk * q[2] - 2.0 * R) * q[2]) / max(np.sqrt(r2 + gz * gz), 1e-150)
+  return max(lat, q[2] - h, -q[2])
+
+
 def _inside_primitive(fp, x, tol):
   """is the point inside the (closed) primitive, or within tol of its boundary"""
   m = fp.to_world.m
@@ -151,6 +163,8 @@ def _inside_primitive(fp, x, tol):
     return bool(np.linalg.norm(q) <= p[0] + tol)
   if k == geometry.ELLIPSOID:
     return bool(_ellipsoid_distance(q, p) <= tol)
+  if k == geometry.CONICOID:
+    return bool(_conicoid_distance(q, p) <= tol)
   rho = np.hypot(q[0], q[1])
   if k == geometry.CYLINDER:
     return bool(rho <= p[0] + tol and -tol <= q[2] <= p[1] + tol)
@@ -174,6 +188,8 @@ def _strictly_inside_primitive(fp, x, tol):
     return bool(np.linalg.norm(q) < p[0] - tol)
   if k == geometry.ELLIPSOID:
     return bool(_ellipsoid_distance(q, p) < -tol)
+  if k == geometry.CONICOID:
+    return bool(_conicoid_distance(q, p) < -tol)
   rho = np.hypot(q[0], q[1])
   if k == geometry.CYLINDER:
     return bool(rho < p[0] - tol and tol < q[2] < p[1] - tol)
@@ -200,6 +216,8 @@ def _boolean_faces(tree, container, dist_tol):
   their common extent.  Order: operands depth-first, faces in the primitive's own order."""
   out = []
   for fp in geometry.flatten(tree, container):
+    if not fp.facemask:        # (an operand that only trims: of any kind the containment tests know, the ones without
+      continue                 #  fan grids of their own -- ellipsoid, conicoid -- included)
     table = _primitive_face_table(fp.kind, fp.params, fp.to_world, dist_tol)
     for f in sorted(table):
       if not (fp.facemask >> f) & 1:

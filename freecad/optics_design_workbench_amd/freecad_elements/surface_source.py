@@ -61,6 +61,8 @@ def faceArea(kind, params, face):
     raise geometry.UnsupportedGeometry('faces of a paraboloid as a surface source are not built')
   if kind == geometry.ELLIPSOID:
     raise geometry.UnsupportedGeometry('faces of an ellipsoid as a surface source are not built')
+  if kind == geometry.CONICOID:
+    raise geometry.UnsupportedGeometry('faces of a conicoid as a surface source are not built')
   if kind == geometry.BOX:
     a = face >> 1
     return p[(a + 1) % 3] * p[(a + 2) % 3]
@@ -136,6 +138,9 @@ def bakeSurfaceSource(doc, obj):
         if any(fp.kind == geometry.ELLIPSOID for fp in flat):
           raise geometry.UnsupportedGeometry(f'{obj.Name}: faces of an ellipsoid as a surface source are not built ({part.Name}), '
                                              f'nor faces trimmed by an ellipsoid')
+        if any(fp.kind == geometry.CONICOID for fp in flat):
+          raise geometry.UnsupportedGeometry(f'{obj.Name}: faces of a conicoid as a surface source are not built ({part.Name}), '
+                                             f'nor faces trimmed by a conicoid')
         base = len(prims)
         for k, fp in enumerate(flat):
           fp.index = base + k

@@ -16,12 +16,26 @@ import numpy as np
 
 from .placement import Placement
 
-BOX, SPHERE, CYLINDER, CONE, TORUS, TRIANGLE, PARABOLOID, ELLIPSOID = range(8)
-KIND_NAMES = ['box', 'sphere', 'cylinder', 'cone', 'torus', 'triangle', 'paraboloid', 'ellipsoid']
+BOX, SPHERE, CYLINDER, CONE, TORUS, TRIANGLE, PARABOLOID, ELLIPSOID, CONICOID = range(9)
+KIND_NAMES = ['box', 'sphere', 'cylinder', 'cone', 'torus', 'triangle', 'paraboloid', 'ellipsoid', 'conicoid']
 # (paraboloid: face 0 = the surface of revolution, face 2 = the cap at z = H as on cylinders and
-#  cones; there is no face 1)
-N_FACES = {BOX: 6, SPHERE: 1, CYLINDER: 3, CONE: 3, TORUS: 1, TRIANGLE: 1, PARABOLOID: 3, ELLIPSOID: 1}
+#  cones; there is no face 1;
+#  conicoid: the same two faces -- the conic surface and the cap at z = H)
+N_FACES = {BOX: 6, SPHERE: 1, CYLINDER: 3, CONE: 3, TORUS: 1, TRIANGLE: 1, PARABOLOID: 3, ELLIPSOID: 1, CONICOID: 3}
 PARABOLOID_FACES = 0b101
+CONICOID_FACES = 0b101
+
+
+def conicoid_rim(R, K, H):
+  """radius of the parallel at height H of the conic rho^2 = 2 R z - (1 + K) z^2"""
+  return float(np.sqrt(2.0 * R * H - (1.0 + K) * H * H))
+
+
+def conicoid_sag(rho, R, K):
+  """z of the conic surface above the point at distance rho from the axis (the branch through the vertex), in the
+  form without cancellation: rho^2 / (R + sqrt(R^2 - (1 + K) rho^2))"""
+  rho = np.asarray(rho, dtype=np.float64)
+  return rho * rho / (R + np.sqrt(R * R - (1.0 + K) * rho * rho))
 
 
 class UnsupportedGeometry(ValueError):
@@ -140,6 +154,15 @@ def _primitive_of(obj):
     if not (f > 0 and h > 0):
       raise UnsupportedGeometry(f'{obj.Name}: paraboloid needs a positive focal length and height')
     return Node('prim', kind=PARABOLOID, params=(f, h, 2.0 * np.sqrt(f * h), 0.0), source=obj.Name, facemask=PARABOLOID_FACES)
+  if t == 'Part::FeaturePython' and obj.ProxyClass == 'Conicoid':
+    # conic solid of revolution x^2 + y^2 + (1 + K) z^2 <= 2 R z, z <= Height (freecad_elements.make.makeConicoid):
+    # vertex radius R, conic constant K -- hyperboloid sheet, paraboloid, prolate / spherical / oblate cap
+    R, K, h = float(obj.VertexRadius), float(obj.ConicConstant), float(obj.Height)
+    if not (R > 0 and h > 0 and np.isfinite([R, K, h]).all()):
+      raise UnsupportedGeometry(f'{obj.Name}: conicoid needs a positive vertex radius and height and a finite conic constant')
+    if K > -1.0 and not h <= R / (1.0 + K):
+      raise UnsupportedGeometry(f'{obj.Name}: conicoid with K > -1 ends at or before its equator: Height <= VertexRadius / (1 + K)')
+    return Node('prim', kind=CONICOID, params=(R, K, h, conicoid_rim(R, K, h)), source=obj.Name, facemask=CONICOID_FACES)
   return None
 
 
@@ -444,7 +467,7 @@ def is_convex(node):
   """True for solids a straight line meets in one interval: box, sphere,
   cylinder, cone and intersections (Common) of such"""
   if node.op == 'prim':
-    return node.kind in (BOX, SPHERE, CYLINDER, CONE, PARABOLOID, ELLIPSOID)
+    return node.kind in (BOX, SPHERE, CYLINDER, CONE, PARABOLOID, ELLIPSOID, CONICOID)
   if node.op == 'common':
     return all(is_convex(c) for c in node.children)
   return False
@@ -573,6 +596,9 @@ def local_bounds(kind, params):
     return np.array([-r, -r, 0.0]), np.array([r, r, p[1]])
   if kind == ELLIPSOID:
     return np.array([-p[0], -p[1], -p[2]]), np.array([p[0], p[1], p[2]])
+  if kind == CONICOID:
+    r = conicoid_rim(p[0], p[1], p[2])
+    return np.array([-r, -r, 0.0]), np.array([r, r, p[2]])
   raise ValueError(kind)
 
 
@@ -586,6 +612,8 @@ def face_local_bounds(kind, params, face):
   elif kind == PARABOLOID and face == 2:
     r = 2.0 * np.sqrt(params[0] * params[1])
     lo = np.array([-r, -r, hi[2]]); hi = np.array([r, r, hi[2]])
+  elif kind == CONICOID and face == 2:
+    lo = np.array([lo[0], lo[1], hi[2]])
   elif kind in (CYLINDER, CONE) and face in (1, 2):
     r = params[0] if (face == 1 or kind == CYLINDER) else params[1]
     z = lo[2] if face == 1 else hi[2]
@@ -718,6 +746,23 @@ def tessellate(kind, params, segments=48):
     # (d/du) x (d/dv) must point outwards (away from the axis, downwards): u clockwise
     lat = _grid(n, max(2, n // 4), lambda U, V: pt(-U, V), lambda U, V: nr(-U, V))
     parts.append(lat)
+    dp = lambda U, V: st(rim * V * np.cos(-two_pi * U), rim * V * np.sin(-two_pi * U), h + 0 * V)
+    parts.append(_grid(n, max(1, n // 8), dp, lambda U, V: st(0 * U, 0 * U, 1.0 + 0 * V)))
+  elif kind == CONICOID:
+    R, K, h = params[0], params[1], params[2]
+    rim = conicoid_rim(R, K, h)
+    # as the paraboloid: v = radius / rim, z from the sag; normals from the gradient (x, y, (1 + K) z - R).  The rim
+    # row takes z = h itself (the sag at the rim is h up to rounding: lateral face and cap then share their vertices)
+    def pt(U, V):
+      rho = rim * V
+      return st(rho * np.cos(two_pi * U), rho * np.sin(two_pi * U), np.where(V >= 1.0, h, conicoid_sag(np.minimum(rho, rim), R, K)))
+    def nr(U, V):
+      p = pt(U, V)
+      g = st(p[..., 0], p[..., 1], (1.0 + K) * p[..., 2] - R)
+      return g / np.linalg.norm(g, axis=-1, keepdims=True)
+    # (d/du) x (d/dv) = tangent x meridian = (z' cos, z' sin, -1): outwards with u counter-clockwise; the cap's u runs
+    # clockwise for +z
+    parts.append(_grid(n, max(2, n // 4), pt, nr))
     dp = lambda U, V: st(rim * V * np.cos(-two_pi * U), rim * V * np.sin(-two_pi * U), h + 0 * V)
     parts.append(_grid(n, max(1, n // 8), dp, lambda U, V: st(0 * U, 0 * U, 1.0 + 0 * V)))
   elif kind == BOX:

@@ -316,7 +316,7 @@ class Tracer:
     """scenes that differ in their numbers only (a parameter sweep: the same primitives, trimming lists, groups and
     optical types) side by side in HBM (`odw_upload_scene_batch`; limits first).  Scene 0 becomes the tracer's scene.
     Raises NativeError (unsupported) when the scenes differ in structure or lie outside the flat kernels' domain --
-    the caller then traces them one by one.  Scenes with a paraboloid or an ellipsoid are in that domain only through
+    the caller then traces them one by one.  Scenes with a paraboloid, an ellipsoid or a conicoid are in that domain only through
     the kernel compiled against them: after compileScene('structure')."""
     if not len(scenes):
       raise ValueError('empty batch')

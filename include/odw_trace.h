@@ -57,6 +57,19 @@ enum {
 /*           else is ODW_ERR_INVALID), -.  One face, no caps (face mask bits */
 /*           above bit 0 are ODW_ERR_UNSUPPORTED).  Known to the             */
 /*           scene-compiled, grid and binary-tree kernels.                   */
+/*  CONICOID conic solid of revolution, vertex at the origin, axis +z:      */
+/*           x^2 + y^2 + (1 + K) z^2 - 2 R z <= 0, 0 <= z <= H -- the lens   */
+/*           designer's surface rho^2 = 2 R z - (1 + K) z^2 with vertex      */
+/*           radius R and conic constant K: K < -1 one sheet of a            */
+/*           hyperboloid, -1 the paraboloid of focal length R / 2, (-1, 0)   */
+/*           a prolate cap, 0 a spherical cap, > 0 an oblate cap.            */
+/*                                 params = R, K, H, rim = sqrt(2 R H -      */
+/*           (1 + K) H^2) (filled in by the library).  R > 0, H > 0, all     */
+/*           finite, and H <= R / (1 + K) for K > -1 (the solid ends at or   */
+/*           before the equator); anything else is ODW_ERR_INVALID.  Faces   */
+/*           0 (the surface) and 2 (the cap z = H); a face mask with bit 1   */
+/*           is ODW_ERR_UNSUPPORTED.  Known to the scene-compiled, grid and  */
+/*           binary-tree kernels; surface sources refuse it.                 */
 /*  TRIANGLE one facet of a tessellated face (shapes whose surfaces are not */
 /*           quadrics: STEP imports, B-splines -- what FreeCAD's            */
 /*           `Shape.tessellate(tol)` returns).  No local frame: prim_xform  */
@@ -73,12 +86,13 @@ enum {
   ODW_PRIM_TORUS = 4,
   ODW_PRIM_TRIANGLE = 5,
   ODW_PRIM_PARABOLOID = 6,
-  ODW_PRIM_ELLIPSOID = 7
+  ODW_PRIM_ELLIPSOID = 7,
+  ODW_PRIM_CONICOID = 8
 };
 
 /* face bit positions inside prim_flags >> ODW_FACEMASK_SHIFT               */
 /*  BOX: 0:-x 1:+x 2:-y 3:+y 4:-z 5:+z ; CYL/CONE: 0:lateral 1:z=0 2:z=H    */
-/*  SPHERE/TORUS/TRIANGLE/ELLIPSOID: 0 ; PARABOLOID: 0:lateral 2:z=H (bit 1 unused)    */
+/*  SPHERE/TORUS/TRIANGLE/ELLIPSOID: 0 ; PARABOLOID/CONICOID: 0:lateral 2:z=H (bit 1 unused)    */
 #define ODW_FLAG_FLIP_NORMAL 0x1 /* face normals point INTO the primitive   */
                                  /* (tool of a Part::Cut)                   */
 #define ODW_FLAG_CONVEX 0x2      /* the primitive's solid (prim_solid) is convex:*/
