@@ -28,7 +28,8 @@ CNT_NAMES = ['traced_rays', 'recorded_hits', 'segments', 'escaped', 'died', 'cap
 TRACE_RECORD_HITS, TRACE_HISTOGRAM, TRACE_RECORD_SEGMENTS, TRACE_POWER_HISTOGRAM = 1, 2, 4, 8
 POWER_QUANTUM_BITS = 32                   # ODW_POWER_QUANTUM_BITS: a hit's weight is rint(clamp(power, 0, 2^20) * 2^32)
 FLAG_FLIP_NORMAL, FLAG_CONVEX = 1, 2      # ODW_FLAG_* of prim_flags (include/odw_trace.h)
-PRIM_PARABOLOID, PRIM_ELLIPSOID, PRIM_CONICOID = 6, 7, 8    # ODW_PRIM_*: the rare quadrics (scene.geometry holds the whole list of kinds)
+PRIM_PARABOLOID, PRIM_ELLIPSOID, PRIM_CONICOID, PRIM_ASPHERE = 6, 7, 8, 9    # ODW_PRIM_*: the rare kinds (scene.geometry holds the whole list of kinds)
+ASPH_COEFS = 8                            # ODW_ASPH_COEFS: a_1 .. a_8 of an asphere's row of prim_coef
 COMPILE_OFF, COMPILE_STRUCTURE, COMPILE_AUTO = 0, 1, 2
 COMPILE_MODES = {None: 0, False: 0, 'off': 0, 0: 0, 'structure': 1, 1: 1, True: 1, 'auto': 2, 2: 2}
 ERRORS = {1: 'invalid argument', 2: 'device error', 3: 'no scene', 4: 'capacity', 5: 'unsupported'}
@@ -64,6 +65,19 @@ class SceneDesc(C.Structure):
               ('group_grating_lpm', _pd), ('group_grating_dir', _pd), ('group_grating_order', _pi),
               ('seq_enabled', C.c_int32), ('seq_len', C.c_int32), ('seq_mask', _pu),
               ('ignore_mask', C.c_uint64), ('tri_normals', _pd), ('tri_edges', _pi)]
+
+
+class SceneDescCoef(SceneDesc):
+  """odw_scene_desc as the library reads it: the fields above (the layout it shares with the oracle's descriptor) and,
+  behind them, the aspheres' coefficient table.  What scene_desc() returns and what arrays of scenes are made of.
+
+  Why two classes: SceneDesc stays, field for field, the oracle's descriptor (the frozen oracle does not know the new
+  field), and callers that declare POINTER(SceneDesc) keep working, since ctypes takes an instance of a subclass there.
+  Pass the library a SceneDescCoef, always.  A bare SceneDesc is 8 bytes short of what the library's struct is: the
+  library reads the last field only once a scene holds an asphere row (and the validation of the tables comes first),
+  so a bare one is read correctly as long as it describes no asphere -- but never put bare ones into an array for
+  odw_upload_scene_batch, whose stride is the full size."""
+  _fields_ = [('prim_coef', _pd)]
 
 
 class SourceDesc(C.Structure):
@@ -232,7 +246,7 @@ def scene_desc(sc):
     keep_tri = _arr(sc.tri_normals, np.float64).reshape(-1, 9)
     if len(keep_tri) != len(sc.prim_type):
       raise ValueError('tri_normals needs one row of 9 values per primitive')
-  d = SceneDesc()
+  d = SceneDescCoef()
   d.n_prims, d.n_conds, d.n_groups = len(keep['prim_type']), len(keep['cond_prim']), len(keep['group_type'])
   for name, typ in SceneDesc._fields_:
     if name in keep:
@@ -246,6 +260,12 @@ def scene_desc(sc):
     if len(keep['tri_edges']) != len(sc.prim_type):
       raise ValueError('tri_edges needs one entry per primitive')
     d.tri_edges = keep['tri_edges'].ctypes.data_as(_pi)
+  # the aspheres' polynomial coefficients; the field stays NULL for a scene without one
+  if getattr(sc, 'prim_coef', None) is not None:
+    keep['prim_coef'] = _arr(sc.prim_coef, np.float64).reshape(-1, ASPH_COEFS)
+    if len(keep['prim_coef']) != len(sc.prim_type):
+      raise ValueError('prim_coef needs one row of 8 values per primitive')
+    d.prim_coef = keep['prim_coef'].ctypes.data_as(_pd)
   return d, keep
 
 
@@ -261,7 +281,7 @@ def compile_check(scene, limits, mode='structure', arch=None, source=None):
   buf = C.create_string_buffer(1 << 20)
   size = C.c_uint64(0)
   f = lib().odw_compile_check_source
-  f.argtypes = [C.POINTER(SceneDesc), C.POINTER(LimitsDesc), C.c_int32, C.c_char_p, C.POINTER(SourceDesc), C.c_char_p,
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), C.c_int32, C.c_char_p, C.POINTER(SourceDesc), C.c_char_p,
                 C.c_uint64, C.POINTER(C.c_uint64)]
   sd, keep_source = source_desc(source) if source is not None else (None, None)
   rc = f(C.byref(d), C.byref(lim), COMPILE_MODES[mode], arch.encode() if arch else None,
@@ -282,7 +302,7 @@ def build_check(scene, limits, library=None):
   structure = C.c_int32(-1)
   sizes = (C.c_uint64 * 6)()
   f = (library or lib()).odw_build_check
-  f.argtypes = [C.POINTER(SceneDesc), C.POINTER(LimitsDesc), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)]
   rc = f(C.byref(d), C.byref(lim), C.byref(structure), sizes)
   if rc != 0:
     msg = (library or lib()).odw_last_error(None)
@@ -299,7 +319,7 @@ def spec_image(scene, limits):
   lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
                    float(limits.power_tol))
   f = lib().odw_spec_image
-  f.argtypes = [C.POINTER(SceneDesc), C.POINTER(LimitsDesc), _pd, C.c_uint64, C.POINTER(C.c_uint64), _pi, C.c_uint64,
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), _pd, C.c_uint64, C.POINTER(C.c_uint64), _pi, C.c_uint64,
                 _pd, C.POINTER(C.c_int32)]
   size, inside = C.c_uint64(0), C.c_int32(0)
   check(None, f(C.byref(d), C.byref(lim), None, 0, C.byref(size), None, 0, None, C.byref(inside)), 'odw_spec_image')

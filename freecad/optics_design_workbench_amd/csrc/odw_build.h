@@ -32,6 +32,7 @@ struct HostScene {
   std::vector<double> group_f64, group_gdir;
   std::vector<int32_t> group_i32;
   std::vector<uint64_t> seq;
+  std::vector<double> asph;               // ODW_ASPH_ROW doubles per primitive (aspheres: coefficients, bounds), or empty: no asphere
   bool lean = false;                      // no grating group, no finite absorption length: LEAN kernels
   // the scalars of DeviceScene that are known here
   int32_t n_prims = 0, n_groups = 0, seq_enabled = 0, seq_len = 0;
@@ -84,6 +85,44 @@ inline void append_slopes(std::vector<double>& tab, size_t n_tables, size_t n_kn
     }
 }
 
+// ---- even aspheres ---------------------------------------------------------------------------
+// sag s(u) of the asphere (c, K, a_1 .. a_8) at u = rho^2, as the definition reads (the radicand floored at 0)
+inline double asph_sag(double c, double K, const double* co, double u) {
+  double pl = 0.0;
+  for (int i = ODW_ASPH_COEFS - 1; i >= 0; --i) pl = pl * u + co[i];
+  return c * u / (1.0 + std::sqrt(std::max(1.0 - (1.0 + K) * c * c * u, 0.0))) + pl * u;
+}
+constexpr int kAsphSamples = 1024;       // samples of the sag on [0, rim]: the height check, the lowest sag
+
+// The row of the asphere table for par = c, K, H, rim and the coefficients co: a_1 .. a_8, then M >= max(|s_rr|, |s_r / r|)
+// and L >= |s_r| over the disc rho <= rim (1 + 1e-3), the conservative lowest sag (the box), a spare word.  Term by
+// term in absolute values: conic part s_r = c rho / q, s_r / rho = c / q, s_rr = c / q^3 with q >= q_min on the disc;
+// polynomial part s_r = sum 2 i a_i rho^(2i-1), s_rr = sum 2 i (2 i - 1) a_i rho^(2i-2) (which bounds s_r / rho too).
+// Returns the largest sampled sag plus the slope bound times half the sample pitch: what H must lie above.
+inline double asph_row(const double* par, const double* co, double* row) {
+  const double c = par[0], K = par[1], rim = par[3];
+  const double rmax = rim * (1.0 + 1e-3), umax = rmax * rmax;
+  const double qmin = std::sqrt(std::max(1.0 - std::max(1.0 + K, 0.0) * c * c * umax, 1e-4));
+  double M = std::fabs(c) / (qmin * qmin * qmin), L = std::fabs(c) * rmax / qmin;
+  double up = 1.0;                                   // u^(i-1)
+  for (int i = 1; i <= ODW_ASPH_COEFS; ++i) {
+    M += 2.0 * i * (2.0 * i - 1.0) * std::fabs(co[i - 1]) * up;
+    L += 2.0 * i * std::fabs(co[i - 1]) * up * rmax;
+    up *= umax;
+  }
+  M *= 1.0 + 1e-12; L *= 1.0 + 1e-12;                // (the sums' own rounding)
+  double smax = -INFINITY, smin = INFINITY;
+  for (int k = 0; k <= kAsphSamples; ++k) {
+    const double rho = rim * (double)k / (double)kAsphSamples, sg = asph_sag(c, K, co, rho * rho);
+    smax = std::max(smax, sg);
+    smin = std::min(smin, sg);
+  }
+  const double half = L * 0.5 * rim / (double)kAsphSamples;
+  for (int i = 0; i < ODW_ASPH_COEFS; ++i) row[i] = co[i];
+  row[8] = M; row[9] = L; row[10] = smin - half; row[11] = 0.0;
+  return smax + half;
+}
+
 // host half of odw_upload_scene: validation and the host copies of every table.  hs is complete only where the
 // answer is ODW_OK
 int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) {
@@ -104,7 +143,7 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
   hs.prim_i32.assign((size_t)n * 4, 0);
   for (int p = 0; p < n; ++p) {
     const int type = s->prim_type[p], group = s->prim_group[p];
-    if (type < ODW_PRIM_BOX || type > ODW_PRIM_CONICOID) return refuse(err, ODW_ERR_UNSUPPORTED, "unknown primitive type");
+    if (type < ODW_PRIM_BOX || type > ODW_PRIM_ASPHERE) return refuse(err, ODW_ERR_UNSUPPORTED, "unknown primitive type");
     if (group < 0 || group >= s->n_groups) return refuse(err, ODW_ERR_INVALID, "primitive group out of range");
     const int off = s->prim_cond_off[p], cnt = s->prim_cond_off[p + 1] - off;
     if (off < 0 || cnt < 0 || cnt > 255 || off + cnt > s->n_conds)
@@ -169,6 +208,27 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
         if (!(rim2 > 0) || !std::isfinite(rim2)) return refuse(err, ODW_ERR_INVALID, "conicoid: no rim at this height");
         par[3] = std::sqrt(rim2);                              // rim radius at z = H
       }
+      if (type == ODW_PRIM_ASPHERE) {
+        // faces 0 (the asphere), 1 (the wall rho = rim), 2 (the cap z = H)
+        if (((s->prim_flags[p] >> ODW_FACEMASK_SHIFT) & 0xff) & ~7)
+          return refuse(err, ODW_ERR_UNSUPPORTED, "asphere: faces 0 (surface), 1 (wall) and 2 (cap at z = H) only");
+        // (a descriptor without the table is the descriptor of before the field, in which the kind does not exist)
+        if (!s->prim_coef) return refuse(err, ODW_ERR_UNSUPPORTED, "asphere: the scene holds an asphere and no coefficients (prim_coef is null): unknown primitive type");
+        const double* par = &hs.prim_f64[16 * (size_t)p + 12];
+        const double* co = s->prim_coef + ODW_ASPH_COEFS * (size_t)p;
+        bool finite = true;
+        for (int k = 0; k < 4; ++k) finite &= std::isfinite(par[k]);
+        for (int k = 0; k < ODW_ASPH_COEFS; ++k) finite &= std::isfinite(co[k]);
+        if (!finite) return refuse(err, ODW_ERR_INVALID, "asphere: curvature, conic constant, height, semi-diameter and coefficients must be finite");
+        if (!(par[3] > 0)) return refuse(err, ODW_ERR_INVALID, "asphere: the semi-diameter must be positive");
+        // (the conic part stays a graph of finite slope over the whole disc, with room for the tolerance)
+        if (!((1.0 + par[1]) * par[0] * par[0] * par[3] * par[3] <= 0.98))
+          return refuse(err, ODW_ERR_INVALID, "asphere: (1 + K) c^2 rim^2 must not exceed 0.98");
+        if (hs.asph.empty()) hs.asph.assign((size_t)n * ODW_ASPH_ROW, 0.0);
+        const double top = asph_row(par, co, &hs.asph[ODW_ASPH_ROW * (size_t)p]);
+        if (!std::isfinite(top) || !(par[2] > top))
+          return refuse(err, ODW_ERR_INVALID, "asphere: the height must lie above the largest sag on [0, rim]");
+      }
     }
     hs.prim_i32[4 * p] = type;
     hs.prim_i32[4 * p + 1] = group;
@@ -176,7 +236,8 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
     // convex-solid shortcut, nothing else
     const int solid = s->prim_solid ? s->prim_solid[p] : 0;
     const bool fits = s->prim_solid && solid >= 0 && solid < 0x7fff && max_solid < 0x7fff;
-    hs.prim_i32[4 * p + 2] = ((s->prim_flags[p] & 0xffff & ~ODW_FLAG_ISOLATED) & (fits ? ~0 : ~ODW_FLAG_CONVEX)) | ((fits ? solid : 0x7fff) << ODW_SOLID_SHIFT);
+    // (an asphere never carries the convex-solid hint: a polynomial profile need not be convex)
+    hs.prim_i32[4 * p + 2] = ((s->prim_flags[p] & 0xffff & ~ODW_FLAG_ISOLATED) & (fits && type != ODW_PRIM_ASPHERE ? ~0 : ~ODW_FLAG_CONVEX)) | ((fits ? solid : 0x7fff) << ODW_SOLID_SHIFT);
     hs.prim_i32[4 * p + 3] = off | (cnt << 24);
   }
   std::vector<int32_t> cond((size_t)std::max(1, s->n_conds), 0);
@@ -226,7 +287,8 @@ int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) 
 }
 
 // ---- primitive bounding boxes in global coordinates -----------------------
-void local_bounds(int type, const double* par, double lo[3], double hi[3]) {
+// (z_min: an asphere's lowest sag, from its table row)
+void local_bounds(int type, const double* par, double lo[3], double hi[3], double z_min = 0.0) {
   switch (type) {
     case ODW_PRIM_BOX:
       lo[0] = lo[1] = lo[2] = 0; hi[0] = par[0]; hi[1] = par[1]; hi[2] = par[2];
@@ -253,6 +315,9 @@ void local_bounds(int type, const double* par, double lo[3], double hi[3]) {
     case ODW_PRIM_CONICOID:   // (0 <= z <= H lies at or before the equator: the rim is the widest parallel)
       lo[0] = lo[1] = -par[3]; hi[0] = hi[1] = par[3]; lo[2] = 0; hi[2] = par[2];
       break;
+    case ODW_PRIM_ASPHERE:    // the disc, from the conservative lowest sag to the cap
+      lo[0] = lo[1] = -par[3]; hi[0] = hi[1] = par[3]; lo[2] = z_min; hi[2] = par[2];
+      break;
     default: {  // torus
       const double r = par[0] + par[1];
       lo[0] = lo[1] = -r; hi[0] = hi[1] = r; lo[2] = -par[1]; hi[2] = par[1];
@@ -268,7 +333,7 @@ struct Box {
   }
 };
 
-Box world_box(const double* pf, int type, double slack) {
+Box world_box(const double* pf, int type, double slack, double z_min = 0.0) {
   Box b;
   b.reset();
   if (type == ODW_PRIM_TRIANGLE) {   // v0, e1, e2 in global coordinates
@@ -281,7 +346,7 @@ Box world_box(const double* pf, int type, double slack) {
     return b;
   }
   double lo[3], hi[3];
-  local_bounds(type, pf + 12, lo, hi);
+  local_bounds(type, pf + 12, lo, hi, z_min);
   for (int c = 0; c < 8; ++c) {
     const double l[3] = {(c & 1) ? hi[0] : lo[0], (c & 2) ? hi[1] : lo[1], (c & 4) ? hi[2] : lo[2]};
     // global = R^T (local - t)
@@ -946,7 +1011,8 @@ void compute_boxes(HostScene& hs, double dist_tol, std::vector<Box>& boxes) {
   std::vector<double>& flat = hs.prim_hdr;
   flat.assign((size_t)std::max(1, n) * 8, 0.0);   // 64-byte headers
   for (int p = 0; p < n; ++p)
-    boxes[p] = world_box(hs.prim_f64.data() + 16 * (size_t)p, hs.prim_i32[4 * p], slack);
+    boxes[p] = world_box(hs.prim_f64.data() + 16 * (size_t)p, hs.prim_i32[4 * p], slack,
+                         hs.prim_i32[4 * p] == ODW_PRIM_ASPHERE ? hs.asph[ODW_ASPH_ROW * (size_t)p + 10] : 0.0);
   // A face that exists only inside other primitives (operands of a Common, the base of a Cut for
   // its tool) lies in their boxes too: the box of a lens cap is the lens, not the sphere.
   // Primitives without faces (pure operands) and faces that cannot exist get a box no ray meets.
@@ -1100,7 +1166,7 @@ inline int spec_derived_count(int type) {
   switch (type) {
     case ODW_PRIM_BOX: return 3;
     case ODW_PRIM_CYLINDER: case ODW_PRIM_CONE: case ODW_PRIM_PARABOLOID: case ODW_PRIM_TORUS: return 4;
-    case ODW_PRIM_CONICOID: return 3;
+    case ODW_PRIM_CONICOID: case ODW_PRIM_ASPHERE: return 3;
     default: return 0;
   }
 }
@@ -1117,7 +1183,8 @@ inline SpecLayout spec_image_layout(const HostScene& hs) {
   for (int p = 0; p < n; ++p) {
     const bool faces = (((hs.prim_i32[4 * p + 2]) >> ODW_FACEMASK_SHIFT) & 0xff) != 0;
     L.frame[p] = at; at += __builtin_popcount(xf_stored(xf_pattern(&hs.prim_f64[16 * (size_t)p])));
-    L.par[p] = at; at += 4;
+    // (an asphere's row of the table -- coefficients, bounds -- lies behind its parameters)
+    L.par[p] = at; at += hs.prim_i32[4 * p] == ODW_PRIM_ASPHERE ? 4 + ODW_ASPH_ROW : 4;
     if (faces && L.box_of[p] == p) { L.box[p] = at; at += 6; }
     const int nd = faces ? spec_derived_count(hs.prim_i32[4 * p]) : 0;
     if (nd) { L.der[p] = at; at += nd; }
@@ -1161,6 +1228,8 @@ inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const
     for (int i = 0; i < 12; ++i)
       if ((stored >> i) & 1u) img[at++] = pf[i];
     for (int k = 0; k < 4; ++k) img[L.par[p] + k] = par[k];
+    if (hs.prim_i32[4 * p] == ODW_PRIM_ASPHERE)
+      for (int k = 0; k < ODW_ASPH_ROW; ++k) img[L.par[p] + 4 + k] = hs.asph[ODW_ASPH_ROW * (size_t)p + k];
     if (L.box[p] >= 0) {
       // centre and half extent of the box, the half extent rounded outward: [c - h, c + h] holds [lo, hi] in float64
       const double* b = &hs.prim_hdr[8 * (size_t)p];
@@ -1181,6 +1250,11 @@ inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const
       d[0] = par[2] + tol;                                                // the z window's upper end
       d[1] = (par[3] + tol) * (par[3] + tol);                             // the cap's disc
       d[2] = 1.0 + par[1];                                                // the z^2 coefficient
+    } else if (type == ODW_PRIM_ASPHERE) {
+      d[0] = par[2] + tol;                                                // the clip region's cap
+      const double wt = std::fmin(tol, 1e-3 * par[3]);                    // (the bounds M, L hold that far out, no farther)
+      d[1] = (par[3] + wt) * (par[3] + wt);                               // the clip region's cylinder
+      d[2] = par[3] * par[3];                                             // the wall
     } else {
       const bool parab = type == ODW_PRIM_PARABOLOID;
       const double R1 = parab ? 0.0 : par[0];
@@ -1194,14 +1268,14 @@ inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const
   }
 }
 
-// A scene the flat loop would take but for its rare quadrics (paraboloids, ellipsoids, conicoids: build_accel gives it a grid and a
+// A scene the flat loop would take but for its rare quadrics (paraboloids, ellipsoids, conicoids, aspheres: build_accel gives it a grid and a
 // tree, since the generic flat kernel leaves their code out): a kernel compiled against it needs neither
 bool flat_but_for_rare_quadrics(const HostScene& hs, int flat_limit) {
   bool rare = false;
   for (int p = 0; p < hs.n_prims; ++p) {
     const int t = hs.prim_i32[4 * p];
     if (t == ODW_PRIM_TRIANGLE) return false;
-    rare |= t == ODW_PRIM_PARABOLOID || t == ODW_PRIM_ELLIPSOID || t == ODW_PRIM_CONICOID;
+    rare |= t == ODW_PRIM_PARABOLOID || t == ODW_PRIM_ELLIPSOID || t == ODW_PRIM_CONICOID || t == ODW_PRIM_ASPHERE;
   }
   return rare && hs.n_prims <= flat_limit;
 }
@@ -1217,8 +1291,9 @@ int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, in
   for (int p = 0; p < n; ++p) {
     has_triangles |= hs.prim_i32[4 * p] == ODW_PRIM_TRIANGLE;
     has_paraboloids |= hs.prim_i32[4 * p] == ODW_PRIM_PARABOLOID;
-    // (conicoids go where ellipsoids go: known to the binary tree and the grid kernel's item branch)
-    has_ellipsoids |= hs.prim_i32[4 * p] == ODW_PRIM_ELLIPSOID || hs.prim_i32[4 * p] == ODW_PRIM_CONICOID;
+    // (conicoids and aspheres go where ellipsoids go: known to the binary tree and the grid kernel's item branch)
+    has_ellipsoids |= hs.prim_i32[4 * p] == ODW_PRIM_ELLIPSOID || hs.prim_i32[4 * p] == ODW_PRIM_CONICOID ||
+                      hs.prim_i32[4 * p] == ODW_PRIM_ASPHERE;
   }
   // (triangles are only known to the BVH kernels, paraboloids to the BVH and grid kernels, ellipsoids to the binary
   //  tree and the grid kernel: beside facets they take the binary tree, not the mesh kernel's eight-wide one)

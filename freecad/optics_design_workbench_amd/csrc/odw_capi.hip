@@ -100,7 +100,7 @@ struct odw_ctx {
   int flat_limit = kBvhThreshold;          // most primitives the flat kernels take (ODW_BVH_THRESHOLD at odw_create)
 
   DevBuf prim_f64, prim_hdr, prim_i32, cond_i32, group_f64, group_i32, group_gdir, seq_mask;
-  DevBuf bvh_nodes, bvh_prims, tri_nrm;
+  DevBuf bvh_nodes, bvh_prims, tri_nrm, asph;
   DevBuf bvh_leaf, bvh_wide;                         // leaf records and eight-wide tree of the mesh kernel (odw_mesh.hip)
   DevBuf grid_bounds, grid_cells, grid_items, dbg;   // rectilinear grid of big analytic scenes (odw_grid.hip)
   DevBuf phi_tab, t_tab, t_guide, phi_guide, d_source, d_det;
@@ -663,6 +663,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
                        const_cast<double*>(P.batch.gen_dirs), const_cast<double*>(P.batch.gen_origins), P.batch.gen_stride);
   }
   const bool stoch = ctx->n_samplers > 0;
+  const bool asph = P.asph != nullptr;       // the scene holds an asphere: the tree and grid instantiations of their own
   P.ray_order = nullptr;
   if (use_mesh && !explicit_rays) {
     int rc = presort_rays(ctx, first, n, seed);       // (inside the timed window: part of the launch's cost)
@@ -677,21 +678,23 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   } else if (use_grid) {
     const dim3 gb((unsigned)grid_blocks);
     const size_t glds = P.grid.lds_bytes;
-#define ODW_GRID_LAUNCH_(S, L, W)                                                                                 \
+#define ODW_GRID_LAUNCH_(S, L, W, A)                                                                              \
     do {                                                                                                       \
       /* (once per device and instantiation: a second context on another GPU of the process needs its own) */  \
       static uint64_t attr_set = 0;                                                                            \
       const uint64_t dev_bit = 1ull << (ctx->device & 63);                                                     \
       if (!(attr_set & dev_bit)) {                                                                             \
-        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&odw_grid_kernel<S, L, W>),              \
+        HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void*>(&odw_grid_kernel<S, L, W, A>),           \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, 155 * 1024));   /* + 4.5 KB static */ \
         attr_set |= dev_bit;                                                                                   \
       }                                                                                                        \
-      hipLaunchKernelGGL((odw_grid_kernel<S, L, W>), gb, dim3(ODW_GRID_THREADS), glds, ctx->stream, P);        \
+      hipLaunchKernelGGL((odw_grid_kernel<S, L, W, A>), gb, dim3(ODW_GRID_THREADS), glds, ctx->stream, P);     \
     } while (0)
-#define ODW_GRID_LAUNCH(S, L) do { if (pw) ODW_GRID_LAUNCH_(S, L, true); else ODW_GRID_LAUNCH_(S, L, false); } while (0)
-    if (P.grid.spheres) { if (P.grid.in_lds) ODW_GRID_LAUNCH(true, true); else ODW_GRID_LAUNCH(true, false); }
-    else { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true); else ODW_GRID_LAUNCH(false, false); }
+#define ODW_GRID_LAUNCH(S, L, A) do { if (pw) ODW_GRID_LAUNCH_(S, L, true, A); else ODW_GRID_LAUNCH_(S, L, false, A); } while (0)
+    // (a scene with an asphere: the item branch's instantiations that know the kind)
+    if (P.grid.spheres) { if (P.grid.in_lds) ODW_GRID_LAUNCH(true, true, false); else ODW_GRID_LAUNCH(true, false, false); }
+    else if (asph) { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true, true); else ODW_GRID_LAUNCH(false, false, true); }
+    else { if (P.grid.in_lds) ODW_GRID_LAUNCH(false, true, false); else ODW_GRID_LAUNCH(false, false, false); }
 #undef ODW_GRID_LAUNCH
 #undef ODW_GRID_LAUNCH_
   } else if (use_mesh) {
@@ -702,18 +705,29 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       if (pw) hipLaunchKernelGGL((odw_trace_kernel<__VA_ARGS__, false, true>), dim3(grid), dim3(256), lds_bytes, ctx->stream, P); \
       else hipLaunchKernelGGL((odw_trace_kernel<__VA_ARGS__, false, false>), dim3(grid), dim3(256), lds_bytes, ctx->stream, P);   \
     } while (0)
+#define ODW_TRACE_LAUNCH_ASPH(lds_bytes, ...)                                                                                     \
+    do {                                                                                                                        \
+      if (pw) hipLaunchKernelGGL((odw_trace_kernel<__VA_ARGS__, false, true, true>), dim3(grid), dim3(256), lds_bytes, ctx->stream, P); \
+      else hipLaunchKernelGGL((odw_trace_kernel<__VA_ARGS__, false, false, true>), dim3(grid), dim3(256), lds_bytes, ctx->stream, P);   \
+    } while (0)
     if (stoch) { if (pw) hipLaunchKernelGGL((odw_mesh_kernel<true, true>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
                  else hipLaunchKernelGGL((odw_mesh_kernel<true, false>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P); }
     else { if (pw) hipLaunchKernelGGL((odw_mesh_kernel<false, true>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P);
            else hipLaunchKernelGGL((odw_mesh_kernel<false, false>), dim3(grid), dim3(ODW_MESH_THREADS), mlds, ctx->stream, P); }
   } else if (flags & ODW_TRACE_RECORD_SEGMENTS) {
-    if (use_tree) {
+    if (use_tree && asph) {
+      if (stoch) ODW_TRACE_LAUNCH_ASPH(lds, true, true, true, false);
+      else ODW_TRACE_LAUNCH_ASPH(lds, true, false, true, false);
+    } else if (use_tree) {
       if (stoch) ODW_TRACE_LAUNCH(lds, true, true, true, false);
       else ODW_TRACE_LAUNCH(lds, true, false, true, false);
     } else {
       if (stoch) ODW_TRACE_LAUNCH(0, false, true, true, false);
       else ODW_TRACE_LAUNCH(0, false, false, true, false);
     }
+  } else if (use_tree && asph) {
+    if (stoch) ODW_TRACE_LAUNCH_ASPH(lds, true, true, false, false);
+    else ODW_TRACE_LAUNCH_ASPH(lds, true, false, false, false);
   } else if (use_tree) {
     if (stoch) ODW_TRACE_LAUNCH(lds, true, true, false, false);
     else ODW_TRACE_LAUNCH(lds, true, false, false, false);
@@ -723,6 +737,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     else ODW_TRACE_LAUNCH(0, false, false, false, false);
   }
 #undef ODW_TRACE_LAUNCH
+#undef ODW_TRACE_LAUNCH_ASPH
   HIPCHK(ctx, hipGetLastError());
   if (ctx->timing) {
     HIPCHK(ctx, hipEventRecord(ev.second, ctx->stream));
@@ -866,7 +881,7 @@ void odw_destroy(odw_ctx* ctx) {
                    &ctx->sort_tmp, &ctx->sorted_rows, &ctx->segs, &ctx->seg_count};
   for (DevBuf* b : all) release(*b);
   for (DevBuf* b : {&ctx->em_prim_f64, &ctx->em_prim_i32, &ctx->em_cond, &ctx->em_face_i32, &ctx->em_face_cdf,
-                    &ctx->em_t_tab, &ctx->em_t_guide, &ctx->em_o, &ctx->em_d, &ctx->em_tri_nrm, &ctx->tri_nrm, &ctx->phi_guide})
+                    &ctx->em_t_tab, &ctx->em_t_guide, &ctx->em_o, &ctx->em_d, &ctx->em_tri_nrm, &ctx->tri_nrm, &ctx->phi_guide, &ctx->asph})
     release(*b);
   for (auto& sb : ctx->surf_bufs) { release(sb.phi_tab); release(sb.t_tab); release(sb.t_guide); }
   release(ctx->d_samplers);
@@ -921,7 +936,10 @@ int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* s) {
   if (s->tri_normals && n > 0) {
     if ((rc = upload(ctx, ctx->tri_nrm, s->tri_normals, (size_t)n * 9 * sizeof(double)))) return rc;
   }
+  // (the asphere table: allocated only when the scene holds one)
+  if (!ctx->hs.asph.empty() && (rc = upload(ctx, ctx->asph, ctx->hs.asph.data(), ctx->hs.asph.size() * sizeof(double)))) return rc;
   if ((rc = upload_done(ctx))) return rc;
+  ctx->P.asph = ctx->hs.asph.empty() ? nullptr : (const double*)ctx->asph.p;
   DeviceScene& d = ctx->P.scene;
   d.n_prims = ctx->hs.n_prims;
   d.n_groups = ctx->hs.n_groups;
@@ -1319,8 +1337,11 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   std::vector<double> pf((size_t)n * 16);
   std::vector<int32_t> pi((size_t)n * 4);
   for (int p = 0; p < n; ++p) {
-    if (s->prim_type[p] < ODW_PRIM_BOX || s->prim_type[p] > ODW_PRIM_CONICOID)
+    if (s->prim_type[p] < ODW_PRIM_BOX || s->prim_type[p] > ODW_PRIM_ASPHERE)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: unknown primitive kind");
+    // (nor asphere code)
+    if (s->prim_type[p] == ODW_PRIM_ASPHERE)
+      return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: an asphere is not built, neither as emitting faces nor as a trimming operand");
     // (nor conicoid code: the emitter rides along in every compiled code object and stays what it is)
     if (s->prim_type[p] == ODW_PRIM_CONICOID)
       return fail(ctx, ODW_ERR_UNSUPPORTED, "surface source: a conicoid is not built, neither as emitting faces nor as a trimming operand");
@@ -1349,7 +1370,7 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   }
   if (!clauses_marked(s->prim_cond_off, n, cond))
     return fail(ctx, ODW_ERR_INVALID, "surface source: a trimming list of several clauses must mark its first condition too");
-  static const int n_faces_of[9] = {6, 1, 3, 3, 1, 1, 0, 0, 0};  // (paraboloid faces do not emit: rejected below; ellipsoids, conicoids: above)
+  static const int n_faces_of[10] = {6, 1, 3, 3, 1, 1, 0, 0, 0, 0};  // (paraboloid faces do not emit: rejected below; ellipsoids, conicoids, aspheres: above)
   std::vector<int32_t> fi((size_t)s->n_faces * 2);
   std::vector<double> fc((size_t)s->n_faces + 1, 0.0);
   double total = 0;
@@ -1596,7 +1617,7 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
   const bool rare_compiled = flat_but_for_rare_quadrics(ctx->hs, ctx->flat_limit) && compiled && ctx->compile_mode == ODW_COMPILE_STRUCTURE;
   if ((ctx->P.scene.n_nodes || ctx->P.grid.nx > 0) && !rare_compiled)
     return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: batches are traced by the flat kernels (analytic scenes of up to 64 primitives; "
-                                          "with paraboloids or ellipsoids: by the compiled one, ODW_COMPILE_STRUCTURE)");
+                                          "with paraboloids, ellipsoids, conicoids or aspheres: by the compiled one, ODW_COMPILE_STRUCTURE)");
   // (the header text of a scene a compiled kernel could take, whatever the mode is now: it also says whether the
   //  scenes share the layout of the value image)
   const bool eligible = spec_ineligible(ctx->hs).empty();

@@ -231,6 +231,9 @@ struct TraceParams {
                                 // the ray within the launch), or null: by number.  Which wave traces a ray never shows in
                                 // its rows (a ray depends on its number only); rays that start alike, traced side by side,
                                 // visit the same nodes and facets (odw_capi.hip: presort_rays)
+  const double* asph;           // [n_prims*ODW_ASPH_ROW] coefficients and bounds of ASPHERE primitives (odw_build.h), or null:
+                                // the scene holds none.  Read by the kernels that know the kind, behind ODW_RQ_ASPHERE
 };
+#define ODW_ASPH_ROW 12         // doubles per row: a_1 .. a_8, M (curvature bound), L (slope bound), z_min (lowest sag), spare
 
 }  // namespace odw

@@ -84,7 +84,9 @@ __device__ __forceinline__ int grid_slab(const double* b, int n, double v) {
 // lanes add with ds_add_u32 (a handful of events per ray)
 #define ODW_GCOUNT(k) atomicAdd(&wave_cnt[(k)], 1u)
 
-template <bool SPHERES, bool IN_LDS, bool POWER = false>     // POWER: the detector's power plane (record_hit)
+// ASPH: the instantiations (of the item branch) that scenes with an asphere are launched with; the others carry none of
+// its code
+template <bool SPHERES, bool IN_LDS, bool POWER = false, bool ASPH = false>     // POWER: the detector's power plane (record_hit)
 __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceParams P) {
   extern __shared__ double grid_lds[];
   const DeviceScene& sc = P.scene;
@@ -123,6 +125,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
   sv.prim_hdr = as_const(sc.prim_hdr);
   sv.prim_i32 = as_const(sc.prim_i32);
   sv.cond_i32 = as_const(sc.cond_i32);
+  if constexpr (ASPH) sv.asph = as_const(P.asph);
   // the groups' tables (64 x {ior, reflectivity, absorption length, lines per mm | optical type, record, grating type,
   // order | grating direction}: 4.5 KB) are read at every interaction with a per-lane index: from LDS, not through the
   // vector cache (a chain of two to three dependent global loads per interaction otherwise)
@@ -436,7 +439,7 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
             if (IN_LDS) p = (int)lds32[2 * item_off + first + k]; else p = (int)reinterpret_cast<const uint32_t*>(GD.items)[first + k];
             ci32 pi = sv.prim_i32 + 4 * p;
             const int g = pi[1];
-            if (((mask >> g) & 1) && (pi[2] >> ODW_SOLID_SHIFT) != skip) intersect_prim(sv, q, p, pi[0], g, pi[2], pi[3]);
+            if (((mask >> g) & 1) && (pi[2] >> ODW_SOLID_SHIFT) != skip) intersect_prim<ODW_RQ_TREE(ASPH)>(sv, q, p, pi[0], g, pi[2], pi[3]);
           }
         }
         cut = fmin_raw(q.tmax, q.any.t + 2.0 * q.tol);
@@ -479,7 +482,9 @@ __global__ __launch_bounds__(ODW_GRID_THREADS) void odw_grid_kernel(const TraceP
           } else {
             cf64 pf = sv.prim_f64 + (size_t)prim * 16;
             ci32 pi = sv.prim_i32 + 4 * prim;
-            n = face_normal(pi[0], pf + 12, face, xf_point(pf, point));
+            cf64 co = nullptr;
+            if constexpr (ASPH) co = sv.asph + (size_t)prim * ODW_ASPH_ROW;
+            n = face_normal<ODW_RQ_TREE(ASPH)>(pi[0], pf + 12, face, xf_point(pf, point), co);
             g = pi[1];
             pflags = pi[2];
             if (pflags & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;

@@ -333,17 +333,123 @@ __device__ __forceinline__ void make_ray(csource s, double t_or_r, double phi,
 }
 
 // ----------------------------------------------------------- primitives
-// RQ: the rare quadrics an instantiation knows (bit 0 paraboloids, bit 1 ellipsoids, bit 2 conicoids).  Paraboloids
-// are known to the BVH, grid and mesh kernels only (the flat kernel of the small benchmark scenes is sensitive to every
-// instruction in its loop: their branch cost it 1.1 %), ellipsoids and conicoids to the BVH and grid kernels; a
-// compiled kernel knows what its scene holds (Spec::rare()).
+// RQ: the rare kinds an instantiation knows (bit 0 paraboloids, bit 1 ellipsoids, bit 2 conicoids, bit 3 aspheres).
+// Paraboloids are known to the BVH, grid and mesh kernels only (the flat kernel of the small benchmark scenes is
+// sensitive to every instruction in its loop: their branch cost it 1.1 %), ellipsoids, conicoids and aspheres to the
+// BVH and grid kernels; a compiled kernel knows what its scene holds (Spec::rare()).
 #define ODW_RQ_PARAB 1
 #define ODW_RQ_ELLIPSOID 2
 #define ODW_RQ_CONICOID 4
-#define ODW_RQ_ALL 7
-template <int RQ, class PP>
-__device__ __forceinline__ double prim_sdist(int type, PP par, d3 p) {
+#define ODW_RQ_ASPHERE 8
+#define ODW_RQ_ALL 15
+// what the binary-tree and grid kernels know: every rare quadric, and -- in the instantiations of their own that scenes
+// with an asphere are launched with (ASPH) -- the asphere.  The others carry none of its code: they are what they were.
+#define ODW_RQ_TREE(ASPH) ((ASPH) ? ODW_RQ_ALL : (ODW_RQ_ALL & ~ODW_RQ_ASPHERE))
+
+// Sag of an even asphere and its derivative by u = x^2 + y^2: s = c u / (1 + q) + sum a_i u^i with
+// q = sqrt(1 - (1 + K) c^2 u), s' = c / (2 q) + sum i a_i u^(i-1).  par = c, K, H, rim; co = a_1 .. a_8 (a row of
+// the asphere table, or the words behind the parameters in a compiled kernel's image).  Horner in u, one square root
+// and one reciprocal shared by 1 / q and 1 / (1 + q); no arrays indexed by lane, no calls.  The library admits
+// (1 + K) c^2 rim^2 <= 0.98 only, so over the disc the radicand stays above 0.018; the floor (below any admitted
+// value) keeps a trimming test of a point far outside the disc free of NaN and infinity.
+template <class PP, class CP>
+__device__ __forceinline__ void asph_eval(PP par, CP co, double u, double& s, double& s1) {
+  const double c = par[0];
+  const double q = fsqrt(fmax(fma(-(1.0 + par[1]) * c * c, u, 1.0), 1e-4));
+  const double r = frcp(q * (1.0 + q));              // 1 / q = r (1 + q), 1 / (1 + q) = r q
+  double pl = co[7], p1 = 8.0 * co[7];
+#pragma unroll
+  for (int i = 6; i >= 0; --i) {
+    p1 = fma(p1, u, (double)(i + 1) * co[i]);
+    pl = fma(pl, u, co[i]);
+  }
+  s = fma(c * r, q, pl) * u;
+  s1 = fma(0.5 * c * r, 1.0 + q, p1);
+}
+
+// F(t) = z(t) - s(u(t)) and its derivative along the line o + t d of the asphere's frame
+template <class PP, class CP>
+__device__ __forceinline__ void asph_F(PP par, CP co, d3 o, d3 d, double t, double& F, double& DF) {
+  const double x = fma(t, d.x, o.x), y = fma(t, d.y, o.y);
+  double s, s1;
+  asph_eval(par, co, fma(x, x, y * y), s, s1);
+  F = fma(t, d.z, o.z) - s;
+  DF = fma(-2.0 * s1, fma(x, d.x, y * d.y), d.z);
+}
+
+// The march of intersect_prim's asphere branch, one crossing at a time: from tc (F is evaluated there afresh) towards
+// te in steps of max(0.99 h, step_min), h = (g + sqrt(g^2 + 2 M |F|)) / M the distance before which the curvature bound
+// M = co[8] allows no root (g = sign(F) F'; written 2 |F| / (sqrt(..) - g) where g <= 0, the form without
+// cancellation); the first change of sign is polished by the torus' bracketed Newton and returned, tc is left behind it.
+// INFINITY: none up to te, or the budget of steps (counted down across the calls for one primitive) is spent.
+template <class PP, class CP>
+__device__ __forceinline__ double asph_next_root(PP par, CP co, d3 o, d3 d, double& tc, double te, int& steps) {
+  const double M = fmax(co[8], 1e-300), iM = frcp(M), step_min = 1e-7 * par[3];
+  double fc, dfc;
+  asph_F(par, co, o, d, tc, fc, dfc);
+#pragma unroll 1
+  while (steps > 0 && tc < te) {
+    --steps;
+    const double g = fc > 0 ? dfc : -dfc, af = fabs(fc);
+    const double rr = fsqrt(fma(g, g, 2.0 * M * af));
+    const double h = g <= 0 ? 2.0 * af * frcp(rr - g) : (g + rr) * iM;     // (0 / 0 on a root: NaN drops out of fmax)
+    const double tn = fmin(tc + fmax(0.99 * h, step_min), te);
+    double fn, dfn;
+    asph_F(par, co, o, d, tn, fn, dfn);
+    if ((fc > 0) != (fn > 0)) {
+      double lo = tc, hi = tn, x = tn;
+      const bool lo_pos = fc > 0;
+      double f = fn, df = dfn;
+#pragma unroll 1
+      for (int j = 0; j < 48; ++j) {
+        if (f == 0) break;
+        if ((f > 0) == lo_pos) lo = x; else hi = x;
+        double xn = x - f * frcp(df);
+        if (!(xn >= lo && xn <= hi)) xn = 0.5 * (lo + hi);
+        // (the torus' rule: Newton has stopped moving -- the bracket test is inclusive -- or the bracket is empty)
+        const bool done = xn == x || (hi - lo) <= 4e-16 * (fabs(lo) + fabs(hi));
+        x = xn;
+        if (done) break;
+        asph_F(par, co, o, d, x, f, df);
+      }
+      tc = tn;
+      return x;
+    }
+    tc = tn;
+    fc = fn;
+    dfc = dfn;
+  }
+  return INFINITY;
+}
+// The same out of line, for the kernels that take the primitive per lane (binary tree, grid): their register file is
+// full across intersect_prim -- the ray, the query, the traversal -- and a march inlined there kept its loop values in
+// scratch memory.  As a function of its own the march has registers of its own: what the caller holds is put aside
+// once per call, around it, and the two loops run without scratch accesses (profiles/asphere.md).  A template, so that
+// code objects which never call it (the scene-compiled kernels inline the march: their operands are scalar) do not
+// carry it.
+struct AsphRoot { double t, tc; int steps; };
+template <int UNUSED>
+__device__ __noinline__ AsphRoot asph_next_root_lane(const double* par, const double* co, d3 o, d3 d, double tc, double te, int steps) {
+  AsphRoot r;
+  r.t = asph_next_root(par, co, o, d, tc, te, steps);
+  r.tc = tc;
+  r.steps = steps;
+  return r;
+}
+
+template <int RQ, class PP, class CP = PP>
+__device__ __forceinline__ double prim_sdist(int type, PP par, d3 p, CP co = CP()) {
   constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
+  constexpr bool ASPH = (RQ & ODW_RQ_ASPHERE) != 0;
+  if (ASPH && type == ODW_PRIM_ASPHERE) {
+    // the slug u <= rim^2, s(u) <= z <= H: below the surface by s - z over the length of the gradient (-2 s' x, -2 s' y, 1)
+    // of z - s, the distance to first order as for the other rare kinds; exact on the wall and on the cap
+    const double u = p.x * p.x + p.y * p.y;
+    double sg, s1;
+    asph_eval(par, co, u, sg, s1);
+    const double lat = (sg - p.z) * frsqrt(fma(4.0 * u * s1, s1, 1.0));
+    return fmax(lat, fmax(fsqrt(u) - par[3], p.z - par[2]));
+  }
   if (CON && type == ODW_PRIM_CONICOID) {
     // q = x^2 + y^2 + (1 + K) z^2 - 2 R z over the length of its gradient g = (x, y, (1 + K) z - R): half of it is the
     // distance to first order, as for the paraboloid and the ellipsoid (the floor: the gradient vanishes at the
@@ -460,6 +566,7 @@ struct SceneView {    // constant-address-space views of the scene tables
   cf64 prim_f64, prim_hdr;
   ci32 prim_i32, cond_i32;
   cf64 img, lim;      // (compiled kernels, which read nothing of the above) the value image and its limits section
+  cf64 asph;          // (kernels that know aspheres, not the compiled ones) TraceParams.asph: rows of ODW_ASPH_ROW doubles
 };
 
 // One candidate intersection of primitive p: range test, then -- only if it
@@ -491,7 +598,9 @@ __device__ __forceinline__ void consider(const SceneView& sv, Query& q, double t
       if (!held) continue;
       const int qp = cond_operand(cw);
       cf64 pf = sv.prim_f64 + (size_t)qp * 16;
-      const double sd = prim_sdist<RQ>(sv.prim_i32[4 * qp], pf + 12, xf_point(pf, gp));
+      cf64 co = nullptr;
+      if constexpr ((RQ & ODW_RQ_ASPHERE) != 0) co = sv.asph + (size_t)qp * ODW_ASPH_ROW;
+      const double sd = prim_sdist<RQ>(sv.prim_i32[4 * qp], pf + 12, xf_point(pf, gp), co);
       if (cw < 0 ? sd > q.tol : sd < -q.tol) {    // must be inside / must be outside
         if (!dnf) return;
         held = false;
@@ -513,7 +622,8 @@ __device__ __forceinline__ bool trim_all(const SceneView& sv, const Query& q, d3
     constexpr int cw = SPEC::cond(C);
     constexpr int qp = cond_operand(cw);
     const PackedFrame<SPEC::xf(qp)> pf{sv.img + SPEC::frame(qp)};
-    const double sd = prim_sdist<RQ>(SPEC::type(qp), sv.img + SPEC::par(qp), xf_point_nz<SPEC::xf(qp)>(pf, gp));
+    // (an asphere's coefficients and bounds lie behind its parameters: spec_image_layout)
+    const double sd = prim_sdist<RQ>(SPEC::type(qp), sv.img + SPEC::par(qp), xf_point_nz<SPEC::xf(qp)>(pf, gp), sv.img + SPEC::par(qp) + 4);
     if (cw < 0) { if (sd > q.tol) return false; }     // must be inside
     else { if (sd < -q.tol) return false; }           // must be outside
     return trim_all<RQ, SPEC, C + 1, END>(sv, q, gp);
@@ -600,6 +710,7 @@ template <int RQ = ODW_RQ_ALL, class SPEC = NoSpec, int PI = 0>
 __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, int p, int type, int group,
                                                int flags, int cond_word) {
   constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
+  constexpr bool ASPH = (RQ & ODW_RQ_ASPHERE) != 0;
   cf64 pf = sv.prim_f64 + (size_t)p * 16;
   const int cond_off = cond_word & 0xffffff, cond_cnt = (cond_word >> 24) & 0xff;
   const int fmask = (flags >> ODW_FACEMASK_SHIFT) & 0xff;
@@ -807,6 +918,88 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       c.t3 = w_ ? tb : c.t3;
       c.f3 = w_ ? 2 : c.f3;
     }
+  } else if (ASPH && type == ODW_PRIM_ASPHERE) {
+    // The slug u <= rim^2, s(u) <= z <= H of an even asphere (params c, K, H, rim; faces 0 surface, 1 wall, 2 cap).  A
+    // crossing of the surface has no closed form.  The ray is clipped to the convex region u <= (rim + tol)^2,
+    // z <= H + tol; the ends of the exact region (wall rho = rim, cap z = H) are candidates where they lie on or above
+    // the surface; between the ends F(t) = z(t) - s(u(t)) is marched.  Along a unit-speed line |F''| <= M (the host's
+    // bound of max(|s_rr|, |s_r / r|) over the disc: the two eigenvalues of the sag's Hessian), so from a point with
+    // value F and slope F' no root lies before h = (g + sqrt(g^2 + 2 M |F|)) / M, g = sign(F) F'.  Steps of
+    // max(0.99 h, step_min) approach a transversal root at a rate of 100 per step without crossing it, step_min carries
+    // the march across; a sign change is polished by the torus' bracketed Newton (asph_next_root).  A loose M costs
+    // steps, never a root.  M holds over rho <= rim (1 + 1e-3): the widening of the disc is the tolerance, and at most
+    // that thousandth of the rim.
+    cf64 co;
+    if constexpr (SPEC::enabled) co = par + 4; else co = sv.asph + (size_t)p * ODW_ASPH_ROW;
+    const double H = par[2], rim = par[3];
+    const double ht = ODW_DER(0, H + tol), r2 = ODW_DER(2, rim * rim);
+    const double rt2 = ODW_DER(1, (rim + fmin(tol, 1e-3 * rim)) * (rim + fmin(tol, 1e-3 * rim)));
+    const double a = d.x * d.x + d.y * d.y, bh = o.x * d.x + o.y * d.y, u0 = o.x * o.x + o.y * o.y;
+    // the clip interval: the widened cylinder (a line along the axis has a = bh = 0: inside or outside for good) ...
+    double t_lo = -INFINITY, t_hi = INFINITY;
+    bool open;
+    {
+      double w0 = 0, w1 = 0;
+      const bool two = quad_roots(a, bh, u0 - rt2, w0, w1) == 2;
+      t_lo = two ? w0 : t_lo;
+      t_hi = two ? w1 : t_hi;
+      open = (bool)((int)two | ((int)(a == 0) & (int)(u0 <= rt2)));
+    }
+    // ... and the half space below the widened cap
+    const double iz = frcp(d.z);
+    const double tp = (H - o.z) * iz, tpt = (ht - o.z) * iz;
+    t_hi = d.z > 0 ? fmin(t_hi, tpt) : t_hi;
+    t_lo = d.z < 0 ? fmax(t_lo, tpt) : t_lo;
+    open = (bool)((int)open & ((int)(d.z != 0) | (int)(o.z <= ht)));
+    if (!open) return;
+    // the ends: the exact wall's two roots where s(rim^2) - tol <= z <= H + tol, the exact cap inside the widened disc
+    // and not below the surface.  Slots 2 and 3 in ascending order; a line within the tolerance of the rim circle can
+    // pass all three tests, the cap then repeats one of the wall's roots and is left out.
+    if (fmask & 6) {
+      double w0 = 0, w1 = 0;
+      const bool two = quad_roots(a, bh, u0 - r2, w0, w1) == 2;
+      double s_rim, s_cap, s1_;
+      asph_eval(par, co, r2, s_rim, s1_);
+      const double z0 = fma(w0, d.z, o.z), z1 = fma(w1, d.z, o.z);
+      const double xp = fma(tp, d.x, o.x), yp = fma(tp, d.y, o.y), up = fma(xp, xp, yp * yp);
+      asph_eval(par, co, up, s_cap, s1_);
+      const bool wall = (bool)((int)two & (int)((fmask & 2) != 0));
+      const bool v0 = (bool)((int)wall & (int)(z0 >= s_rim - tol) & (int)(z0 <= ht));
+      const bool v1 = (bool)((int)wall & (int)(z1 >= s_rim - tol) & (int)(z1 <= ht));
+      const bool vp = (bool)((int)((fmask & 4) != 0) & (int)(up <= rt2) & (int)(H >= s_cap - tol));
+      c.t2 = v0 ? w0 : (vp ? tp : c.t2);
+      c.f2 = v0 ? 1 : (vp ? 2 : c.f2);
+      const bool p3 = (bool)((int)vp & (int)v0 & (int)!v1);
+      c.t3 = v1 ? w1 : (p3 ? tp : c.t3);
+      c.f3 = v1 ? 1 : (p3 ? 2 : c.f3);
+    }
+    // the march: from tol / 2 (roots before it are rejected anyway) to the end of the interval, or to where no
+    // candidate can be selected any more (nearest so far + 2 tol: the cut of the box tests)
+    double tc = fmax(t_lo, 0.5 * tol);
+    double te;
+    if constexpr (SPEC::enabled) te = fmin(t_hi, q.cut); else te = fmin(t_hi, fmin(q.tmax, q.any.t + 2.0 * tol));
+    if ((fmask & 1) && te > tc) {
+      int steps = 4096;
+#pragma unroll 1
+      for (int nfound = 0; nfound < ODW_ASPH_MAX_ROOTS; ++nfound) {
+        double x;
+        if constexpr (SPEC::enabled) {
+          x = asph_next_root(par, co, o, d, tc, te, steps);
+        } else {
+          const AsphRoot r = asph_next_root_lane<0>((const double*)(uintptr_t)par, (const double*)(uintptr_t)co, o, d, tc, te, steps);
+          x = r.t; tc = r.tc; steps = r.steps;
+        }
+        if (!(x < INFINITY)) break;
+        // crossings in ascending order: the first two in slots 0 and 1, the third to the eighth judged here by one
+        // more copy of consider (a non-convex profile has them, and a trimmed lens may keep only a later one); the
+        // ninth and later are dropped (ODW_ASPH_MAX_ROOTS)
+        if (nfound == 0) c.t0 = x;
+        else if (nfound == 1) c.t1 = x;
+        else if constexpr (SPEC::enabled) consider_spec<RQ, SPEC, PI>(sv, q, x, 0);
+        else consider<RQ>(sv, q, x, p, 0, group, cond_off, cond_cnt);
+        if (cond_cnt == 0 && x > tol) break;          // untrimmed: only the nearest admissible crossing can win
+      }
+    }
   } else {  // torus
     if (!(fmask & 1)) return;
     const double R1 = par[0], R2 = par[1];
@@ -917,14 +1110,15 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       // slot holds (INF, 0), which never wins, but judging it is not free -- the compiler cannot tell
       constexpr int ty = SPEC::type(PI), fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
       constexpr bool quadric = ty == ODW_PRIM_CYLINDER || ty == ODW_PRIM_CONE || ty == ODW_PRIM_PARABOLOID || ty == ODW_PRIM_CONICOID;
+      constexpr bool asph = ty == ODW_PRIM_ASPHERE;                   // (wall and cap share slots 2 and 3)
       constexpr bool pair = ty == ODW_PRIM_BOX || (fm & 1) != 0;      // box: entry / exit face; else the surface's two roots
       constexpr bool caps = ty != ODW_PRIM_BOX && ty != ODW_PRIM_SPHERE && ty != ODW_PRIM_ELLIPSOID;
       if constexpr (pair) {
         ODW_PICK(c.t0, c.f0)
         ODW_PICK(c.t1, c.f1)
       }
-      if constexpr (caps && (quadric ? (fm & 2) != 0 : (fm & 1) != 0)) ODW_PICK(c.t2, c.f2)
-      if constexpr (caps && (quadric ? (fm & 4) != 0 : (fm & 1) != 0)) ODW_PICK(c.t3, c.f3)
+      if constexpr (caps && (asph ? (fm & 6) != 0 : quadric ? (fm & 2) != 0 : (fm & 1) != 0)) ODW_PICK(c.t2, c.f2)
+      if constexpr (caps && (asph ? (fm & 6) != 0 : quadric ? (fm & 4) != 0 : (fm & 1) != 0)) ODW_PICK(c.t3, c.f3)
     } else {
     ODW_PICK(c.t0, c.f0)
     ODW_PICK(c.t1, c.f1)
@@ -938,15 +1132,16 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
     // (a sphere has two candidates; the trimming code exists once per candidate slot)
     // (faces that the boolean left nothing of produce no candidate: their slots are not looked at)
     constexpr int fm = (SPEC::flags(PI) >> ODW_FACEMASK_SHIFT) & 0xff;
+    constexpr bool asph = SPEC::type(PI) == ODW_PRIM_ASPHERE;         // (wall and cap share slots 2 and 3)
     constexpr bool quadric = SPEC::type(PI) == ODW_PRIM_CYLINDER || SPEC::type(PI) == ODW_PRIM_CONE || SPEC::type(PI) == ODW_PRIM_PARABOLOID ||
-                             SPEC::type(PI) == ODW_PRIM_CONICOID;
+                             SPEC::type(PI) == ODW_PRIM_CONICOID || asph;
     if constexpr (!quadric || (fm & 1) != 0) {
       consider_spec<RQ, SPEC, PI>(sv, q, c.t0, c.f0);
       consider_spec<RQ, SPEC, PI>(sv, q, c.t1, c.f1);
     }
     if constexpr (SPEC::type(PI) != ODW_PRIM_SPHERE && SPEC::type(PI) != ODW_PRIM_ELLIPSOID) {
-      if constexpr (!quadric || (fm & 2) != 0) consider_spec<RQ, SPEC, PI>(sv, q, c.t2, c.f2);
-      if constexpr (!quadric || (fm & 4) != 0) consider_spec<RQ, SPEC, PI>(sv, q, c.t3, c.f3);
+      if constexpr (!quadric || (fm & (asph ? 6 : 2)) != 0) consider_spec<RQ, SPEC, PI>(sv, q, c.t2, c.f2);
+      if constexpr (!quadric || (fm & (asph ? 6 : 4)) != 0) consider_spec<RQ, SPEC, PI>(sv, q, c.t3, c.f3);
     }
   } else {
 #pragma unroll 1
@@ -1017,9 +1212,21 @@ __device__ __forceinline__ d3 tri_normal(cf64 pf, const double* __restrict__ vn,
 }
 
 // outward normal of face `face` of primitive p at local point lp
+// (co: an asphere's coefficients, as for prim_sdist)
 template <int RQ = ODW_RQ_ALL>
-__device__ __forceinline__ d3 face_normal(int type, cf64 par, int face, d3 lp) {
+__device__ __forceinline__ d3 face_normal(int type, cf64 par, int face, d3 lp, cf64 co = nullptr) {
   constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
+  constexpr bool ASPH = (RQ & ODW_RQ_ASPHERE) != 0;
+  if (ASPH && type == ODW_PRIM_ASPHERE) {
+    // the cap, the wall, or minus the gradient of z - s(u): (2 s' x, 2 s' y, -1), down out of the material -- no
+    // division by rho, the vertex is a point like any other
+    if (face == 2) return mk(0, 0, 1);
+    if (face == 1) return mk(lp.x, lp.y, 0) * frsqrt(lp.x * lp.x + lp.y * lp.y);
+    double sg, s1;
+    asph_eval(par, co, lp.x * lp.x + lp.y * lp.y, sg, s1);
+    const d3 g = mk(2.0 * s1 * lp.x, 2.0 * s1 * lp.y, -1.0);
+    return g * frsqrt(dot(g, g));
+  }
   if (type == ODW_PRIM_BOX) {
     const double s = (face & 1) ? 1.0 : -1.0;
     const int a = face >> 1;
@@ -1144,7 +1351,7 @@ __device__ __forceinline__ void spec_prims(const SceneView& sv, Query& q, d3 oi,
   (spec_prim<SPEC, PI>(sv, q, oi, inv, skip_solid, only_solid, mask, boxhit), ...);
 }
 
-template <bool BVH, class SPEC = NoSpec>
+template <bool BVH, class SPEC = NoSpec, bool ASPH = false>
 __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& sv,
                                        const DeviceLimits& lim, d3 start, d3 dn, int medium,
                                        uint64_t mask, double& t_hit, int& face,
@@ -1285,7 +1492,7 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
         const int g = pi[1];
         if (((mask >> g) & 1) && (pi[2] >> ODW_SOLID_SHIFT) != skip_solid) {
           if (pi[0] == ODW_PRIM_TRIANGLE) intersect_tri(sv, q, p, g);
-          else intersect_prim<ODW_RQ_ALL>(sv, q, p, pi[0], g, pi[2], pi[3]);
+          else intersect_prim<ODW_RQ_TREE(ASPH)>(sv, q, p, pi[0], g, pi[2], pi[3]);
         }
       }
     }
@@ -1800,12 +2007,12 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   constexpr int flags = SPEC::flags(PI), g = SPEC::group(PI);
   const PackedFrame<SPEC::xf(PI)> pf{sv.img + SPEC::frame(PI)};
   cf64 par = sv.img + SPEC::par(PI);
-  d3 n = face_normal<SPEC::rare()>(SPEC::type(PI), par, face, xf_point_nz<SPEC::xf(PI)>(pf, point));
+  d3 n = face_normal<SPEC::rare()>(SPEC::type(PI), par, face, xf_point_nz<SPEC::xf(PI)>(pf, point), par + 4);
   if constexpr ((flags & ODW_FLAG_FLIP_NORMAL) != 0) n = n * -1.0;
   n = xf_vec_t_nz<SPEC::xf(PI)>(pf, n);
 #if ODW_DOUBLE == 6
   {
-    d3 n2 = face_normal<SPEC::rare()>(SPEC::type(PI), par, face, xf_point_nz<SPEC::xf(PI)>(pf, mk(opq(point.x), point.y, point.z)));
+    d3 n2 = face_normal<SPEC::rare()>(SPEC::type(PI), par, face, xf_point_nz<SPEC::xf(PI)>(pf, mk(opq(point.x), point.y, point.z)), par + 4);
     if constexpr ((flags & ODW_FLAG_FLIP_NORMAL) != 0) n2 = n2 * -1.0;
     n2 = xf_vec_t_nz<SPEC::xf(PI)>(pf, n2);
     n = n2.x == n.x ? n : n2;
@@ -1889,9 +2096,11 @@ template <> struct HitBlockState<false> {
 // LEAN: the scene has no grating group and no finite absorption length (the host checks): their code
 // -- line_grating's chain of IEEE divisions and square roots, exp() -- is left out of the binary
 // BATCH (flat kernels): scenes of one structure side by side in one launch (DeviceBatch)
+// ASPH (binary tree): the instantiations scenes with an asphere are launched with
 template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false,
-          class SRC = NoSource>
+          class SRC = NoSource, bool ASPH = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P) {
+  static_assert(!ASPH || BVH, "aspheres: the binary tree (or a compiled kernel, which knows its scene from Spec::rare())");
   static_assert(!BATCH || (!BVH && !SEG), "batch launches: flat kernels, no segment rows");
   extern __shared__ int bvh_stack[];  // ODW_BVH_STACK x 256 ints (BVH variant only)
   // per-thread event counters live in LDS (one column per thread, ds_add_u32
@@ -1907,6 +2116,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   sv.prim_hdr = as_const(sc.prim_hdr);
   sv.prim_i32 = as_const(sc.prim_i32);
   sv.cond_i32 = as_const(sc.cond_i32);
+  if constexpr (ASPH) sv.asph = as_const(P.asph);
   cf64 group_f64 = as_const(sc.group_f64);
   ci32 group_i32 = as_const(sc.group_i32);
   cf64 group_gdir = as_const(sc.group_gdir);
@@ -2069,7 +2279,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       mask &= ~sc.ignore_mask;
       double t_hit;
       int face;
-      const int prim = nearest<BVH, SPEC>(sc, sv, lim, point, dir, medium, mask, t_hit, face,
+      const int prim = nearest<BVH, SPEC, ASPH>(sc, sv, lim, point, dir, medium, mask, t_hit, face,
                                           bvh_stack + threadIdx.x, skip, BVH ? -1 : only);
       // A ray that has entered an isolated solid within distTol beyond one of its edges can pass it by: then, and
       // only then, the solid's own primitives yield nothing -- the segment is done again with every primitive, in
@@ -2108,7 +2318,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         n = tri_normal(pf, sc.tri_nrm ? sc.tri_nrm + (size_t)prim * 9 : nullptr, point);
         if (pi[2] & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;
       } else {
-        n = face_normal<BVH ? ODW_RQ_ALL : 0>(pi[0], pf + 12, face, xf_point(pf, point));
+        cf64 co = nullptr;
+        if constexpr (ASPH) co = sv.asph + (size_t)prim * ODW_ASPH_ROW;
+        n = face_normal<BVH ? ODW_RQ_TREE(ASPH) : 0>(pi[0], pf + 12, face, xf_point(pf, point), co);
         if (pi[2] & ODW_FLAG_FLIP_NORMAL) n = n * -1.0;
         n = xf_vec_t(pf, n);
       }
@@ -2174,9 +2386,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   }
 }
 
-template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, bool BATCH = false, bool POWER = false>
+template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, bool BATCH = false, bool POWER = false, bool ASPH = false>
 __global__ __launch_bounds__(256, BVH ? ODW_WAVES_PER_SIMD_BVH : ODW_WAVES_PER_SIMD) void odw_trace_kernel(const TraceParams P) {
-  trace_body<BVH, STOCH, SEG, LEAN, NoSpec, BATCH, POWER>(P);
+  trace_body<BVH, STOCH, SEG, LEAN, NoSpec, BATCH, POWER, NoSource, ASPH>(P);
 }
 
 #ifdef ODW_SPEC_HEADER
@@ -2356,7 +2568,7 @@ __global__ __launch_bounds__(256) void odw_emit_kernel(const DeviceEmitter E, ui
         if (!ok) continue;
         const int qp = cond_operand(cw);
         const double* of = E.prim_f64 + (size_t)qp * 16;
-        // (the emitter's tables hold neither ellipsoid nor conicoid: odw_upload_surface_source refuses them)
+        // (the emitter's tables hold neither ellipsoid nor conicoid nor asphere: odw_upload_surface_source refuses them)
         const double sd = prim_sdist<ODW_RQ_PARAB>(E.prim_i32[4 * qp], of + 12, xf_point(of, gp));
         if (cw < 0 ? sd > E.dist_tol : sd < -E.dist_tol) ok = false;
       }

@@ -197,8 +197,8 @@ MeshRay mesh_interact(ckargs kargs, d3 point, d3 dir, double power, int medium, 
 }
 
 // an analytic primitive listed in a leaf (a screen behind the mesh), a function of its own for the same reason:
-// intersect_prim<> holds every kind of primitive this kernel knows (build_accel hands scenes with an ellipsoid or a
-// conicoid to the binary tree), the quartic of the torus included
+// intersect_prim<> holds every kind of primitive this kernel knows (build_accel hands scenes with an ellipsoid, a
+// conicoid or an asphere to the binary tree), the quartic of the torus included
 struct MeshBest { Best any, oth; };
 __device__ __forceinline__
 MeshBest mesh_intersect_prim(ckargs kargs, d3 start, d3 dn, double tol, double tmax, int medium, Best any, Best oth, int p) {

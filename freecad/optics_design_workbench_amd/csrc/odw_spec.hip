@@ -183,9 +183,10 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
        table("bool", "record", ng, grec.data(), fi);
   // (rare quadrics -- paraboloids, ellipsoids: the generic flat kernel leaves their code out -- it costs every scene
   //  1 % -- and hands such documents to the grid kernel; a compiled kernel carries the code of exactly the kinds its
-  //  scene holds: ODW_RQ_PARAB | ODW_RQ_ELLIPSOID | ODW_RQ_CONICOID of odw_kernels.hip)
+  //  scene holds: ODW_RQ_PARAB | ODW_RQ_ELLIPSOID | ODW_RQ_CONICOID | ODW_RQ_ASPHERE of odw_kernels.hip)
   int rare = 0;
-  for (int p = 0; p < n; ++p) rare |= (type[p] == ODW_PRIM_PARABOLOID ? 1 : 0) | (type[p] == ODW_PRIM_ELLIPSOID ? 2 : 0) | (type[p] == ODW_PRIM_CONICOID ? 4 : 0);
+  for (int p = 0; p < n; ++p) rare |= (type[p] == ODW_PRIM_PARABOLOID ? 1 : 0) | (type[p] == ODW_PRIM_ELLIPSOID ? 2 : 0) | (type[p] == ODW_PRIM_CONICOID ? 4 : 0) |
+                                      (type[p] == ODW_PRIM_ASPHERE ? 8 : 0);
   s += "  static constexpr int rare() { return " + std::to_string(rare) + "; }\n";
   // ODW_FLAG_ISOLATED (a ray that has entered an isolated solid tests that solid only) is left to the generic
   // flat kernel, which gains 3 % on lensesAndMirrors from it: in a compiled kernel a skipped box test saves less

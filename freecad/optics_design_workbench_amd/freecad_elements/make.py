@@ -94,6 +94,29 @@ def makeConicoid(doc, name='Conicoid', vertexRadius=10.0, conicConstant=-1.0, he
                        Placement=_placement(**pl))
 
 
+def makeAsphere(doc, name='Asphere', curvature=None, conicConstant=0.0, coefficients=(), semiDiameter=10.0, height=5.0,
+                vertexRadius=None, **pl):
+  """slug under an even asphere in its own frame (vertex at the origin, axis +z): rho <= semiDiameter,
+  sag(rho) <= z <= height with sag = c rho^2 / (1 + sqrt(1 - (1 + K) c^2 rho^2)) + a_1 rho^2 + a_2 rho^4 + .. + a_8 rho^16
+  -- the "even asphere" of lens-design programs: c = curvature (or 1 / vertexRadius: exactly one of the two; negative
+  bends the surface away from the material, 0 is flat), K = conicConstant, coefficients = (a_1, a_2, ..) up to eight.
+  The material lies above the surface, out to the wall rho = semiDiameter, up to the flat back z = height, which has to
+  lie above the highest point of the surface.  Traced as exact geometry (primitive kind 9)"""
+  if (curvature is None) == (vertexRadius is None):
+    raise ValueError(f'{name}: give curvature or vertexRadius, one of the two')
+  if curvature is None:
+    if float(vertexRadius) == 0.0:
+      raise ValueError(f'{name}: a vertex radius of 0')
+    curvature = 0.0 if np.isinf(vertexRadius) else 1.0 / float(vertexRadius)
+  coefficients = [float(a) for a in coefficients]
+  if len(coefficients) > 8:
+    raise ValueError(f'{name}: at most eight polynomial coefficients (rho^2 .. rho^16)')
+  return doc.addObject('Part::FeaturePython', name, Proxy={'module': 'freecad.optics_design_workbench_amd.scene.geometry',
+                                                             'class': 'Asphere', 'state': {}},
+                       Curvature=float(curvature), ConicConstant=float(conicConstant), Coefficients=coefficients,
+                       SemiDiameter=float(semiDiameter), Height=float(height), Placement=_placement(**pl))
+
+
 def makeCommon(doc, shapes, name='Common', **pl):
   return doc.addObject('Part::MultiCommon', name, Shapes=list(shapes), Placement=_placement(**pl))
 
@@ -180,6 +203,49 @@ def makeConicLens(doc, name='ConicLens', radius1=50.0, conic1=0.0, radius2=-50.0
   return solid
 
 
+def makeAsphericLens(doc, name='AsphericLens', front=None, back=None, thickness=5.0, diameter=20.0, **pl):
+  """a singlet on the local z axis between two even aspheres: the solid rho <= diameter / 2,
+  sag_front(rho) <= z <= thickness + sag_back(rho).  front and back are dicts with the keys curvature (or vertexRadius),
+  conicConstant and coefficients of makeAsphere, in lens design's sign convention -- z towards +z from each surface's
+  own vertex (front vertex at the origin, back vertex at z = thickness); None is a flat face.  The Common of two slugs,
+  the back one turned round; each slug's height reaches past the other's surface, so no cut is needed, and the back
+  slug is one per cent wider than the lens (its surface has to be admissible out to there), so no two operand faces
+  coincide: the lens's edge is the front slug's wall.  ValueError when the surfaces meet inside the diameter.  Returns the solid, placed by **pl:
+  the caller puts it into a lens group (makeLens)."""
+  from ..scene import geometry
+
+  def prescription(d):
+    d = dict(d or {})
+    if 'vertexRadius' in d and 'curvature' in d:
+      raise ValueError(f'{name}: give curvature or vertexRadius, one of the two')
+    if 'vertexRadius' in d:
+      r = float(d.pop('vertexRadius'))
+      d['curvature'] = 0.0 if np.isinf(r) else 1.0 / r
+    co = [float(a) for a in d.get('coefficients', ())]
+    return float(d.get('curvature', 0.0)), float(d.get('conicConstant', 0.0)), co
+
+  t, a = float(thickness), float(diameter) / 2
+  if not (t > 0 and a > 0):
+    raise ValueError(f'{name}: thickness and diameter must be positive')
+  (c1, k1, co1), (c2, k2, co2) = prescription(front), prescription(back)
+  # the back surface seen from its own slug (turned about x: z -> thickness - z) has the opposite sag
+  c2, co2 = -c2, [-x for x in co2]
+  rho = a * np.arange(geometry.ASPHERE_SAMPLES + 1) / geometry.ASPHERE_SAMPLES
+  s1, s2 = geometry.asphere_sag(rho, c1, k1, co1), geometry.asphere_sag(rho, c2, k2, co2)
+  if not np.all(np.isfinite(s1)) or not np.all(np.isfinite(s2)) or not np.min(t - s2 - s1) > 0:
+    raise ValueError(f'{name}: the two surfaces meet inside the diameter (thickness {t})')
+  # each slug ends a margin beyond the other's farthest point (and beyond its own highest)
+  margin = 0.25 * max(t, a)
+  a2 = 1.01 * a
+  top1, top2 = geometry.asphere_bounds(c1, k1, a, co1)[3], geometry.asphere_bounds(c2, k2, a2, co2)[3]
+  h1 = max(t - float(s2.min()), top1) + margin
+  h2 = max(t - float(s1.min()), top2) + 2 * margin
+  f = makeAsphere(doc, f'{name}Front', curvature=c1, conicConstant=k1, coefficients=co1, semiDiameter=a, height=h1)
+  b = makeAsphere(doc, f'{name}Back', curvature=c2, conicConstant=k2, coefficients=co2, semiDiameter=a2, height=h2,
+                  base=(0.0, 0.0, t), quat=(1.0, 0.0, 0.0, 0.0))
+  return makeCommon(doc, [f, b], name=name, **pl)
+
+
 def makeOpticalGroup(doc, opticalType, elements, name=None, placement=None, **props):
   """`OpticalType` in Mirror|Lens|Grating|Absorber|Vacuum; RecordHits follows
   OpticalGroupProxy.onChanged (optical_group.py:141-160) unless given"""
@@ -255,7 +321,7 @@ def makeMesh(doc, vertices, triangles, vertexNormals=None, name='Mesh', **pl):
 
 
 def makeTessellated(doc, solid, segments=48, smooth=True, name=None):
-  """mesh of a primitive solid object (Part::Sphere / Ellipsoid / Cylinder / Cone / Torus / Box, paraboloid, conicoid) at the same placement"""
+  """mesh of a primitive solid object (Part::Sphere / Ellipsoid / Cylinder / Cone / Torus / Box, paraboloid, conicoid, asphere) at the same placement"""
   from ..scene import geometry
   node = geometry._primitive_of(solid)
   if node is None:

@@ -108,6 +108,8 @@ def _primitive_face_table(kind, params, to_world, dist_tol):
     raise geometry.UnsupportedGeometry('faces of an ellipsoid as fan grids are not built')
   elif kind == geometry.CONICOID:
     raise geometry.UnsupportedGeometry('faces of a conicoid as fan grids are not built')
+  elif kind == geometry.ASPHERE:
+    raise geometry.UnsupportedGeometry('faces of an asphere as fan grids are not built')
   else:
     raise geometry.UnsupportedGeometry(f'no fan grid for primitive kind {kind}')
   return faces
@@ -165,6 +167,8 @@ def _inside_primitive(fp, x, tol):
     return bool(_ellipsoid_distance(q, p) <= tol)
   if k == geometry.CONICOID:
     return bool(_conicoid_distance(q, p) <= tol)
+  if k == geometry.ASPHERE:
+    raise geometry.UnsupportedGeometry('faces trimmed by an asphere as fan grids are not built')
   rho = np.hypot(q[0], q[1])
   if k == geometry.CYLINDER:
     return bool(rho <= p[0] + tol and -tol <= q[2] <= p[1] + tol)
@@ -190,6 +194,8 @@ def _strictly_inside_primitive(fp, x, tol):
     return bool(_ellipsoid_distance(q, p) < -tol)
   if k == geometry.CONICOID:
     return bool(_conicoid_distance(q, p) < -tol)
+  if k == geometry.ASPHERE:
+    raise geometry.UnsupportedGeometry('faces trimmed by an asphere as fan grids are not built')
   rho = np.hypot(q[0], q[1])
   if k == geometry.CYLINDER:
     return bool(rho < p[0] - tol and tol < q[2] < p[1] - tol)

@@ -63,6 +63,8 @@ def faceArea(kind, params, face):
     raise geometry.UnsupportedGeometry('faces of an ellipsoid as a surface source are not built')
   if kind == geometry.CONICOID:
     raise geometry.UnsupportedGeometry('faces of a conicoid as a surface source are not built')
+  if kind == geometry.ASPHERE:
+    raise geometry.UnsupportedGeometry('faces of an asphere as a surface source are not built')
   if kind == geometry.BOX:
     a = face >> 1
     return p[(a + 1) % 3] * p[(a + 2) % 3]
@@ -141,6 +143,9 @@ def bakeSurfaceSource(doc, obj):
         if any(fp.kind == geometry.CONICOID for fp in flat):
           raise geometry.UnsupportedGeometry(f'{obj.Name}: faces of a conicoid as a surface source are not built ({part.Name}), '
                                              f'nor faces trimmed by a conicoid')
+        if any(fp.kind == geometry.ASPHERE for fp in flat):
+          raise geometry.UnsupportedGeometry(f'{obj.Name}: faces of an asphere as a surface source are not built ({part.Name}), '
+                                             f'nor faces trimmed by an asphere')
         base = len(prims)
         for k, fp in enumerate(flat):
           fp.index = base + k

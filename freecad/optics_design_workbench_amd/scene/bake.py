@@ -205,6 +205,7 @@ class BakedScene:
   surface_samplers: list = field(default_factory=list)   # freecad_elements.optical_group.BakedSurfaceSampler
   tri_normals: np.ndarray = None                         # (n_prims, 9) vertex normals of TRIANGLE primitives, or None
   tri_edges: np.ndarray = None                           # (n_prims,) bits: which facet edges are edges of the face
+  prim_coef: np.ndarray = None                           # (n_prims, 8) polynomial coefficients of ASPHERE primitives, or None: no asphere
 
   @property
   def n_prims(self):
@@ -365,8 +366,16 @@ def bakeScene(doc, source=None, surfaceFamily=None):
     at += k
   cond_off = cond_off + [cond_off[-1]] * n_tri
 
+  # the aspheres' coefficients a_1 .. a_8 (behind the four parameters of such a primitive); None without an asphere
+  prim_coef = None
+  if any(p.kind == geometry.ASPHERE for p in prims):
+    prim_coef = np.zeros((n + n_tri, geometry.ASPHERE_COEFS))
+    for k, p in enumerate(prims):
+      if p.kind == geometry.ASPHERE:
+        prim_coef[k] = p.params[4:4 + geometry.ASPHERE_COEFS]
+
   return BakedScene(
-      tri_normals=tri_normals, tri_edges=tri_edges,
+      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef,
       prim_type=np.concatenate([np.array([p.kind for p in prims], dtype=np.int32),
                                 np.full(n_tri, geometry.TRIANGLE, dtype=np.int32)]),
       prim_group=np.concatenate([np.array(prim_group, dtype=np.int32), tri_group]),
@@ -376,7 +385,7 @@ def bakeScene(doc, source=None, surfaceFamily=None):
                                  tri_flags]),
       prim_xform=np.concatenate([_snapFrames(np.array([p.to_world.inverse().rows12() for p in prims],
                                                       dtype=np.float64).reshape(n, 12)), tri_xform]),
-      prim_params=np.concatenate([np.array([p.params for p in prims], dtype=np.float64).reshape(n, 4),
+      prim_params=np.concatenate([np.array([p.params[:4] for p in prims], dtype=np.float64).reshape(n, 4),
                                   np.zeros((n_tri, 4))]),
       prim_cond_off=np.array(cond_off, dtype=np.int32),
       cond_prim=np.array(cond_prim, dtype=np.int32),

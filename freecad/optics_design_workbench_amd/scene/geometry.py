@@ -16,12 +16,13 @@ import numpy as np
 
 from .placement import Placement
 
-BOX, SPHERE, CYLINDER, CONE, TORUS, TRIANGLE, PARABOLOID, ELLIPSOID, CONICOID = range(9)
-KIND_NAMES = ['box', 'sphere', 'cylinder', 'cone', 'torus', 'triangle', 'paraboloid', 'ellipsoid', 'conicoid']
+BOX, SPHERE, CYLINDER, CONE, TORUS, TRIANGLE, PARABOLOID, ELLIPSOID, CONICOID, ASPHERE = range(10)
+KIND_NAMES = ['box', 'sphere', 'cylinder', 'cone', 'torus', 'triangle', 'paraboloid', 'ellipsoid', 'conicoid', 'asphere']
 # (paraboloid: face 0 = the surface of revolution, face 2 = the cap at z = H as on cylinders and
 #  cones; there is no face 1;
-#  conicoid: the same two faces -- the conic surface and the cap at z = H)
-N_FACES = {BOX: 6, SPHERE: 1, CYLINDER: 3, CONE: 3, TORUS: 1, TRIANGLE: 1, PARABOLOID: 3, ELLIPSOID: 1, CONICOID: 3}
+#  conicoid: the same two faces -- the conic surface and the cap at z = H;
+#  asphere: face 0 = the aspheric surface, 1 = the wall rho = rim, 2 = the cap at z = H)
+N_FACES = {BOX: 6, SPHERE: 1, CYLINDER: 3, CONE: 3, TORUS: 1, TRIANGLE: 1, PARABOLOID: 3, ELLIPSOID: 1, CONICOID: 3, ASPHERE: 3}
 PARABOLOID_FACES = 0b101
 CONICOID_FACES = 0b101
 
@@ -36,6 +37,65 @@ def conicoid_sag(rho, R, K):
   form without cancellation: rho^2 / (R + sqrt(R^2 - (1 + K) rho^2))"""
   rho = np.asarray(rho, dtype=np.float64)
   return rho * rho / (R + np.sqrt(R * R - (1.0 + K) * rho * rho))
+
+
+ASPHERE_COEFS = 8             # a_1 .. a_8: the coefficients of rho^2, rho^4, .. rho^16
+ASPHERE_SAMPLES = 1024        # samples of the sag on [0, rim] in the height check (the library's kAsphSamples)
+
+
+def asphere_sag(rho, c, K, coefs):
+  """sag of the even asphere at the distance rho from the axis: with u = rho^2,
+  c u / (1 + sqrt(1 - (1 + K) c^2 u)) + sum a_i u^i, i = 1 .. 8 (coefs = a_1 .. a_8, fewer: the rest are 0)"""
+  u = np.asarray(rho, dtype=np.float64)**2
+  pl = np.zeros_like(u)
+  for a in tuple(coefs)[::-1]:
+    pl = pl * u + float(a)
+  return c * u / (1.0 + np.sqrt(np.maximum(1.0 - (1.0 + K) * c * c * u, 0.0))) + pl * u
+
+
+def asphere_sag_du(rho, c, K, coefs):
+  """derivative of the sag by u = rho^2: c / (2 q) + sum i a_i u^(i-1); the slope by rho is 2 rho times this"""
+  u = np.asarray(rho, dtype=np.float64)**2
+  p1 = np.zeros_like(u)
+  for i in range(len(tuple(coefs)), 0, -1):
+    p1 = p1 * u + i * float(coefs[i - 1])
+  return 0.5 * c / np.sqrt(np.maximum(1.0 - (1.0 + K) * c * c * u, 1e-4)) + p1
+
+
+def asphere_bounds(c, K, rim, coefs):
+  """(M, L, z_min, top) as the library works them out (odw_build.h: asph_row): M >= max(|s_rr|, |s_r / r|) and
+  L >= |s_r| over the disc rho <= rim (1 + 1e-3), term by term in absolute values; the conservative lowest sag; and
+  what the height must lie above -- the largest sampled sag plus L times half the sample pitch"""
+  co = list(coefs) + [0.0] * (ASPHERE_COEFS - len(tuple(coefs)))
+  rmax = rim * (1.0 + 1e-3)
+  umax = rmax * rmax
+  qmin = np.sqrt(max(1.0 - max(1.0 + K, 0.0) * c * c * umax, 1e-4))
+  M, L, up = abs(c) / qmin**3, abs(c) * rmax / qmin, 1.0
+  for i in range(1, ASPHERE_COEFS + 1):
+    M += 2.0 * i * (2.0 * i - 1.0) * abs(co[i - 1]) * up
+    L += 2.0 * i * abs(co[i - 1]) * up * rmax
+    up *= umax
+  M, L = M * (1.0 + 1e-12), L * (1.0 + 1e-12)
+  sg = asphere_sag(rim * np.arange(ASPHERE_SAMPLES + 1) / ASPHERE_SAMPLES, c, K, co)
+  half = L * 0.5 * rim / ASPHERE_SAMPLES
+  return float(M), float(L), float(sg.min() - half), float(sg.max() + half)
+
+
+def asphere_refusal(c, K, H, rim, coefs):
+  """why the library refuses this asphere (scene_host_tables), in words; None: it is taken"""
+  vals = [c, K, H, rim] + list(coefs)
+  if len(tuple(coefs)) > ASPHERE_COEFS:
+    return f'at most {ASPHERE_COEFS} polynomial coefficients (rho^2 .. rho^16)'
+  if not np.isfinite(vals).all():
+    return 'curvature, conic constant, height, semi-diameter and coefficients must be finite'
+  if not rim > 0:
+    return 'the semi-diameter must be positive'
+  if not (1.0 + K) * c * c * rim * rim <= 0.98:
+    return '(1 + K) c^2 rim^2 must not exceed 0.98: the conic part has to stay a graph of finite slope over the whole disc'
+  top = asphere_bounds(c, K, rim, coefs)[3]
+  if not (np.isfinite(top) and H > top):
+    return f'the height must lie above the largest sag on [0, rim] (above {top})'
+  return None
 
 
 class UnsupportedGeometry(ValueError):
@@ -163,6 +223,16 @@ def _primitive_of(obj):
     if K > -1.0 and not h <= R / (1.0 + K):
       raise UnsupportedGeometry(f'{obj.Name}: conicoid with K > -1 ends at or before its equator: Height <= VertexRadius / (1 + K)')
     return Node('prim', kind=CONICOID, params=(R, K, h, conicoid_rim(R, K, h)), source=obj.Name, facemask=CONICOID_FACES)
+  if t == 'Part::FeaturePython' and obj.ProxyClass == 'Asphere':
+    # even asphere (freecad_elements.make.makeAsphere): the slug rho <= SemiDiameter, sag(rho) <= z <= Height.  The node
+    # carries its coefficients behind the four parameters: params = c, K, H, rim, a_1 .. a_8
+    c, K, h, rim = float(obj.Curvature), float(obj.ConicConstant), float(obj.Height), float(obj.SemiDiameter)
+    coefs = [float(a) for a in obj.Coefficients]
+    why = asphere_refusal(c, K, h, rim, coefs)
+    if why:
+      raise UnsupportedGeometry(f'{obj.Name}: asphere: {why}')
+    coefs += [0.0] * (ASPHERE_COEFS - len(coefs))
+    return Node('prim', kind=ASPHERE, params=(c, K, h, rim) + tuple(coefs), source=obj.Name)
   return None
 
 
@@ -199,7 +269,12 @@ def _scaled(nodes, s, name=''):
     mesh = n.mesh
     if mesh is not None:
       mesh = (np.asarray(mesh[0]) * s,) + tuple(mesh[1:3])       # (face table and payload describe the unscaled shape)
-    return Node(n.op, pl, mesh, n.kind, tuple(p * s for p in n.params), [one(c) for c in n.children], n.source, n.facemask)
+    params = tuple(p * s for p in n.params)
+    if n.op == 'prim' and n.kind == ASPHERE:
+      # (z = sag(rho) magnified: the curvature is a reciprocal length, K a number, a_i a length^(1 - 2 i))
+      q = n.params
+      params = (q[0] / s, q[1], q[2] * s, q[3] * s) + tuple(a * s**(1 - 2 * i) for i, a in enumerate(q[4:], start=1))
+    return Node(n.op, pl, mesh, n.kind, params, [one(c) for c in n.children], n.source, n.facemask)
   return [one(n) for n in nodes]
 
 
@@ -599,6 +674,8 @@ def local_bounds(kind, params):
   if kind == CONICOID:
     r = conicoid_rim(p[0], p[1], p[2])
     return np.array([-r, -r, 0.0]), np.array([r, r, p[2]])
+  if kind == ASPHERE:      # the disc, from the conservative lowest sag to H
+    return np.array([-p[3], -p[3], asphere_bounds(p[0], p[1], p[3], p[4:])[2]]), np.array([p[3], p[3], p[2]])
   raise ValueError(kind)
 
 
@@ -612,7 +689,7 @@ def face_local_bounds(kind, params, face):
   elif kind == PARABOLOID and face == 2:
     r = 2.0 * np.sqrt(params[0] * params[1])
     lo = np.array([-r, -r, hi[2]]); hi = np.array([r, r, hi[2]])
-  elif kind == CONICOID and face == 2:
+  elif kind in (CONICOID, ASPHERE) and face == 2:
     lo = np.array([lo[0], lo[1], hi[2]])
   elif kind in (CYLINDER, CONE) and face in (1, 2):
     r = params[0] if (face == 1 or kind == CYLINDER) else params[1]
@@ -763,6 +840,21 @@ def tessellate(kind, params, segments=48):
     # (d/du) x (d/dv) = tangent x meridian = (z' cos, z' sin, -1): outwards with u counter-clockwise; the cap's u runs
     # clockwise for +z
     parts.append(_grid(n, max(2, n // 4), pt, nr))
+    dp = lambda U, V: st(rim * V * np.cos(-two_pi * U), rim * V * np.sin(-two_pi * U), h + 0 * V)
+    parts.append(_grid(n, max(1, n // 8), dp, lambda U, V: st(0 * U, 0 * U, 1.0 + 0 * V)))
+  elif kind == ASPHERE:
+    c, K, h, rim, co = params[0], params[1], params[2], params[3], tuple(params[4:])
+    # rings on the surface (v = radius / rim), the wall from the sag at the rim to h, the cap; as on the conicoid
+    # (d/du) x (d/dv) = (z' cos, z' sin, -1) points down out of the material with u counter-clockwise
+    pt = lambda U, V: st(rim * V * np.cos(two_pi * U), rim * V * np.sin(two_pi * U), asphere_sag(rim * V, c, K, co) + 0 * U)
+    def nr(U, V):
+      s1 = 2.0 * asphere_sag_du(rim * V, c, K, co)
+      g = st(s1 * rim * V * np.cos(two_pi * U), s1 * rim * V * np.sin(two_pi * U), -1.0 + 0 * V)
+      return g / np.linalg.norm(g, axis=-1, keepdims=True)
+    parts.append(_grid(n, max(2, n // 4), pt, nr))
+    z0 = float(asphere_sag(rim, c, K, co))
+    wp = lambda U, V: st(rim * np.cos(two_pi * U), rim * np.sin(two_pi * U), z0 + (h - z0) * V)
+    parts.append(_grid(n, max(1, n // 8), wp, lambda U, V: st(np.cos(two_pi * U), np.sin(two_pi * U), 0 * V)))
     dp = lambda U, V: st(rim * V * np.cos(-two_pi * U), rim * V * np.sin(-two_pi * U), h + 0 * V)
     parts.append(_grid(n, max(1, n // 8), dp, lambda U, V: st(0 * U, 0 * U, 1.0 + 0 * V)))
   elif kind == BOX:

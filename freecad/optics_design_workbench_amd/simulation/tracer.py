@@ -316,7 +316,8 @@ class Tracer:
     """scenes that differ in their numbers only (a parameter sweep: the same primitives, trimming lists, groups and
     optical types) side by side in HBM (`odw_upload_scene_batch`; limits first).  Scene 0 becomes the tracer's scene.
     Raises NativeError (unsupported) when the scenes differ in structure or lie outside the flat kernels' domain --
-    the caller then traces them one by one.  Scenes with a paraboloid, an ellipsoid or a conicoid are in that domain only through
+    the caller then traces them one by one.  Scenes with a paraboloid, an ellipsoid, a conicoid or an asphere (whose coefficients travel in
+    the scene's prim_coef, the last field of the descriptor) are in that domain only through
     the kernel compiled against them: after compileScene('structure')."""
     if not len(scenes):
       raise ValueError('empty batch')
@@ -332,7 +333,7 @@ class Tracer:
       d, keep = _native.scene_desc(sc)
       descs.append(d)
       keeps.append(keep)
-    arr = (_native.SceneDesc * len(descs))(*descs)
+    arr = (_native.SceneDescCoef * len(descs))(*descs)
     self._chk(self._lib.odw_upload_scene_batch(self._ctx, arr, C.c_int32(len(descs))), 'odw_upload_scene_batch')
     arr0, n0, keep0 = _native.surface_sampler_descs(None)
     self._chk(self._lib.odw_upload_surface_samplers(self._ctx, arr0, C.c_int32(n0)), 'odw_upload_surface_samplers')

@@ -70,6 +70,26 @@ enum {
 /*           0 (the surface) and 2 (the cap z = H); a face mask with bit 1   */
 /*           is ODW_ERR_UNSUPPORTED.  Known to the scene-compiled, grid and  */
 /*           binary-tree kernels; surface sources refuse it.                 */
+/*  ASPHERE  even asphere of lens design, vertex at the origin, axis +z.     */
+/*           With u = x^2 + y^2 the sag is                                   */
+/*             s(u) = c u / (1 + sqrt(1 - (1 + K) c^2 u)) + sum a_i u^i,     */
+/*           i = 1..8: vertex curvature c (any sign, or 0), conic constant   */
+/*           K, a_1..a_8 the coefficients of rho^2, rho^4, .. rho^16.  The   */
+/*           solid is the slug u <= rim^2, s(u) <= z <= H: the material      */
+/*           above the surface out to the semi-diameter rim, up to a flat    */
+/*           back.                   params = c, K, H, rim; the coefficients */
+/*           in prim_coef.  All finite, rim > 0, (1 + K) c^2 rim^2 <= 0.98,  */
+/*           H above the largest sag on [0, rim] (judged conservatively: a   */
+/*           sampled maximum plus the slope bound times half the pitch);     */
+/*           anything else is ODW_ERR_INVALID.  Without prim_coef the kind   */
+/*           is unknown (ODW_ERR_UNSUPPORTED).                      Faces 0   */
+/*           (the asphere), 1 (the wall rho = rim), 2 (the cap z = H); face  */
+/*           mask bits above bit 2 are ODW_ERR_UNSUPPORTED.  Never           */
+/*           ODW_FLAG_CONVEX (the flag is dropped).  A ray / asphere         */
+/*           crossing has no closed form: a marching solver, at most         */
+/*           ODW_ASPH_MAX_ROOTS crossings per ray.  Known to the             */
+/*           scene-compiled, grid and binary-tree kernels; surface sources   */
+/*           refuse it.                                                      */
 /*  TRIANGLE one facet of a tessellated face (shapes whose surfaces are not */
 /*           quadrics: STEP imports, B-splines -- what FreeCAD's            */
 /*           `Shape.tessellate(tol)` returns).  No local frame: prim_xform  */
@@ -87,12 +107,16 @@ enum {
   ODW_PRIM_TRIANGLE = 5,
   ODW_PRIM_PARABOLOID = 6,
   ODW_PRIM_ELLIPSOID = 7,
-  ODW_PRIM_CONICOID = 8
+  ODW_PRIM_CONICOID = 8,
+  ODW_PRIM_ASPHERE = 9
 };
+#define ODW_ASPH_COEFS 8      /* polynomial terms of an asphere: rho^2 .. rho^16 */
+#define ODW_ASPH_MAX_ROOTS 8  /* crossings of one asphere a ray is judged on; later ones are dropped */
 
 /* face bit positions inside prim_flags >> ODW_FACEMASK_SHIFT               */
 /*  BOX: 0:-x 1:+x 2:-y 3:+y 4:-z 5:+z ; CYL/CONE: 0:lateral 1:z=0 2:z=H    */
 /*  SPHERE/TORUS/TRIANGLE/ELLIPSOID: 0 ; PARABOLOID/CONICOID: 0:lateral 2:z=H (bit 1 unused)    */
+/*  ASPHERE: 0:the aspheric surface 1:the wall rho=rim 2:z=H                 */
 #define ODW_FLAG_FLIP_NORMAL 0x1 /* face normals point INTO the primitive   */
                                  /* (tool of a Part::Cut)                   */
 #define ODW_FLAG_CONVEX 0x2      /* the primitive's solid (prim_solid) is convex:*/
@@ -178,6 +202,20 @@ typedef struct odw_scene_desc {
    * across those only; across edges it shares with a neighbouring facet of the same face it is
    * closed up to rounding (1e-9 in barycentric units).  NULL: every edge is a face edge.      */
   const int32_t* tri_edges;     /* [n_prims] or NULL                          */
+  /* polynomial coefficients a_1 .. a_8 of each ASPHERE primitive (rows of
+   * other primitives are ignored); NULL: the scene holds no asphere.  Appended
+   * at the end: a zero-filled descriptor that never sets it describes what it
+   * always did, and the ABI version stays -- a descriptor without the table
+   * is the descriptor of before, in which kind 9 does not exist: an ASPHERE
+   * row beside a NULL prim_coef is ODW_ERR_UNSUPPORTED, like any unknown kind.
+   * CAUTION: sizeof(odw_scene_desc) grew by this pointer under the unchanged
+   * version number.  odw_upload_scene, odw_build_check, odw_compile_check and
+   * odw_spec_image read the field only when a scene holds an ASPHERE row, but
+   * odw_upload_scene_batch steps through its array by the new size: a caller
+   * compiled against the header of before the field must be rebuilt before
+   * it uploads batches (its scenes would be misread silently).  The version
+   * is to be raised with the next change of the ABI.                          */
+  const double* prim_coef;      /* [n_prims*8] or NULL                        */
 } odw_scene_desc;
 
 /* Point source = PointSourceProxy (point_source.py:32-70) after
