@@ -49,7 +49,16 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_upload_scene_batch', 'odw_trace_batch', 'odw_batch_select', 'odw_batch_rows',
            'odw_plane_screen_batch', 'odw_archive_append', 'odw_archive_select', 'odw_archive_reset', 'odw_batch_hits_select', 'odw_batch_hits_sample', 'odw_batch_hits_project', 'odw_batch_hits_bin',
            'odw_batch_reserve', 'odw_batch_hits_begin', 'odw_batch_hits_sampled', 'odw_batch_hits_measure', 'odw_batch_hits_measured',
-           'odw_enable_power_histogram', 'odw_fetch_power_histogram', 'odw_device_power_histogram', 'odw_hits_bin_power', 'odw_compiled_power_info']
+           'odw_enable_power_histogram', 'odw_fetch_power_histogram', 'odw_device_power_histogram', 'odw_hits_bin_power', 'odw_compiled_power_info',
+           'odw_set_dispersion', 'odw_set_spectrum', 'odw_trace_rays_spectral', 'odw_ray_wavelengths', 'odw_dispersion_index',
+           'odw_dispersion_check', 'odw_spectrum_check', 'odw_compiled_chroma_info', 'odw_compile_check_chroma']
+
+# dispersion of a group (ODW_DISP_*) and spectrum of a point source (ODW_SPECTRUM_*)
+DISP_NONE, DISP_SELLMEIER, DISP_CAUCHY = 0, 1, 2
+DISP_KINDS = {'': 0, None: 0, 'Sellmeier': 1, 'Cauchy': 2}
+DISP_COEFS = 6                            # ODW_DISP_COEFS
+SPECTRUM_MODES = {'lines': 1, 'density': 2}
+STREAM_WAVELENGTH = 6                     # ODW_STREAM_WAVELENGTH: word 3 of the Philox counter of the wavelength draw
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
@@ -269,6 +278,25 @@ def scene_desc(sc):
   return d, keep
 
 
+def compile_check_chroma(scene, limits, arch=None, source=None):
+  """Host only (no GPU): header and code size of the compiled kernel's CHROMA variant (spectral launches) for `scene`
+  under its group_disp_kind (`odw_compile_check_chroma`)"""
+  d, keep = scene_desc(scene)
+  lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
+                   float(limits.power_tol))
+  kinds = _arr(scene.group_disp_kind, np.int32)
+  buf = C.create_string_buffer(1 << 20)
+  size = C.c_uint64(0)
+  f = lib().odw_compile_check_chroma
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), C.c_char_p, C.POINTER(SourceDesc), _pi, C.c_char_p, C.c_uint64,
+                C.POINTER(C.c_uint64)]
+  sd, keep_source = source_desc(source) if source is not None else (None, None)
+  rc = f(C.byref(d), C.byref(lim), arch.encode() if arch else None, C.byref(sd) if sd is not None else None,
+         kinds.ctypes.data_as(_pi), buf, len(buf), C.byref(size))
+  check(None, rc, 'odw_compile_check_chroma')
+  return buf.value.decode(), int(size.value)
+
+
 def compile_check(scene, limits, mode='structure', arch=None, source=None):
   """Host only (no GPU): the header of constants the library writes for `scene` and the size of the
   code object hiprtc builds from it for `arch` (default gfx950).  Raises NativeError when the scene
@@ -346,6 +374,43 @@ def table_slopes(cdf, edges):
   rc = f(cdf.ctypes.data_as(_pd), edges.ctypes.data_as(_pd), cdf.shape[0], cdf.shape[1], out.ctypes.data_as(_pd))
   check(None, rc, 'odw_table_slopes')
   return out
+
+
+def dispersion_index(kind, coef, wavelengths):
+  """Host only (no GPU): the index of the glass (kind: 'Sellmeier' / 'Cauchy' or ODW_DISP_*, coef: up to 6 numbers) at
+  `wavelengths` (nm) -- the library's disp_index (`odw_dispersion_index` without a context)"""
+  k = DISP_KINDS[kind] if isinstance(kind, str) else int(kind)
+  c = np.zeros(DISP_COEFS, np.float64)
+  cc = np.asarray(coef, dtype=np.float64).reshape(-1)
+  if len(cc) > DISP_COEFS:
+    raise ValueError('DispersionCoefficients: at most 6 numbers')
+  c[:len(cc)] = cc
+  w = _arr(wavelengths, np.float64).reshape(-1)
+  out = np.empty(len(w), np.float64)
+  f = lib().odw_dispersion_index
+  f.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _pd, C.c_uint64, _pd, _pd, C.c_int32]
+  check(None, f(None, 0, k, c.ctypes.data_as(_pd), len(w), w.ctypes.data_as(_pd), out.ctypes.data_as(_pd), 0), 'odw_dispersion_index')
+  return out
+
+
+def dispersion_check(kind, coef, lo_nm, hi_nm):
+  """Host only (no GPU): the checks a launch runs on a dispersion (`odw_dispersion_check`): kinds and coefficients, then
+  every index finite and >= 1 and no Sellmeier pole over [lo_nm, hi_nm].  Raises NativeError naming the group."""
+  k = _arr(kind, np.int32).reshape(-1)
+  c = _arr(coef, np.float64).reshape(len(k), DISP_COEFS)
+  f = lib().odw_dispersion_check
+  f.argtypes = [C.c_int32, _pi, _pd, C.c_double, C.c_double]
+  check(None, f(len(k), k.ctypes.data_as(_pi), c.ctypes.data_as(_pd), float(lo_nm), float(hi_nm)), 'odw_dispersion_check')
+
+
+def spectrum_check(mode, wavelengths, cdf):
+  """Host only (no GPU): `odw_set_spectrum`'s validation of a table; raises NativeError"""
+  w, c = _arr(wavelengths, np.float64).reshape(-1), _arr(cdf, np.float64).reshape(-1)
+  if len(w) != len(c):
+    raise ValueError('Spectrum: wavelengths and cdf differ in length')
+  f = lib().odw_spectrum_check
+  f.argtypes = [C.c_int32, C.c_int32, _pd, _pd]
+  check(None, f(SPECTRUM_MODES.get(mode, mode), len(w), w.ctypes.data_as(_pd), c.ctypes.data_as(_pd)), 'odw_spectrum_check')
 
 
 def source_desc(src):

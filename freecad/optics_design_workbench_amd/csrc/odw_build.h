@@ -123,6 +123,127 @@ inline double asph_row(const double* par, const double* co, double* row) {
   return smax + half;
 }
 
+// ---- dispersion and spectra -------------------------------------------------------------------
+// The index of a glass at wavelength_nm.  The order of IEEE operations is fixed, none of them contracted -- the
+// device twin (odw_kernels.hip: disp_index_dev) performs the same sequence, and so does the numpy expression
+// the tests hold both against:
+//   l  = wavelength_nm / 1000          l2 = l * l
+//   Sellmeier: s = 1; for i = 0, 1, 2 in this order: s = s + (B_i * l2) / (l2 - C_i);  n = sqrt(s)
+//   Cauchy:    l4 = l2 * l2;  n = (A + B / l2) + C / l4
+// kind 0 (and anything unknown, which the validation refuses before it gets here): NaN.
+inline double disp_index(int kind, const double* coef, double wavelength_nm) {
+#pragma clang fp contract(off)
+  const double l = wavelength_nm / 1000.0;
+  const double l2 = l * l;
+  if (kind == ODW_DISP_SELLMEIER) {
+    double s = 1.0;
+    for (int i = 0; i < 3; ++i) {
+      const double num = coef[i] * l2, den = l2 - coef[3 + i];
+      s = s + num / den;
+    }
+    return std::sqrt(s);
+  }
+  if (kind == ODW_DISP_CAUCHY) {
+    const double l4 = l2 * l2;
+    const double t1 = coef[1] / l2, t2 = coef[2] / l4;
+    return (coef[0] + t1) + t2;
+  }
+  return std::numeric_limits<double>::quiet_NaN();
+}
+
+// odw_set_dispersion's check of kind / coef; group_i32 (may be null: no scene at hand) adds the groups' types
+inline int disp_validate(int n_groups, const int32_t* kind, const double* coef, const int32_t* group_i32, std::string& err) {
+  if (n_groups < 0 || n_groups > ODW_MAX_GROUPS || (n_groups && (!kind || !coef)))
+    return refuse(err, ODW_ERR_INVALID, "odw_set_dispersion: bad argument");
+  for (int g = 0; g < n_groups; ++g) {
+    if (kind[g] == ODW_DISP_NONE) continue;
+    char buf[160];
+    if (kind[g] != ODW_DISP_SELLMEIER && kind[g] != ODW_DISP_CAUCHY) {
+      std::snprintf(buf, sizeof buf, "odw_set_dispersion: group %d: unknown dispersion kind %d", g, (int)kind[g]);
+      err = buf;
+      return ODW_ERR_INVALID;
+    }
+    for (int k = 0; k < ODW_DISP_COEFS; ++k)
+      if (!std::isfinite(coef[ODW_DISP_COEFS * g + k])) {
+        std::snprintf(buf, sizeof buf, "odw_set_dispersion: group %d: non-finite dispersion coefficient", g);
+        err = buf;
+        return ODW_ERR_INVALID;
+      }
+    if (group_i32) {
+      const int t = group_i32[4 * g], gt = group_i32[4 * g + 2];
+      if (!(t == ODW_OPT_LENS || (t == ODW_OPT_GRATING && gt == 1))) {
+        std::snprintf(buf, sizeof buf, "odw_set_dispersion: group %d: a dispersion on a group that is neither a lens nor a transmission grating", g);
+        err = buf;
+        return ODW_ERR_INVALID;
+      }
+    }
+  }
+  return ODW_OK;
+}
+
+// The check before a launch: every dispersive group's index finite and >= 1 over [lo_nm, hi_nm] (kDispSamples evenly
+// spaced wavelengths, the ends included; a Sellmeier index is monotone between its poles for positive B, C, so the ends
+// decide there -- the samples between are for signs a catalogue does not print), no Sellmeier pole sqrt(C_i) inside
+constexpr int kDispSamples = 33;
+inline int disp_check_range(int n_groups, const int32_t* kind, const double* coef, double lo_nm, double hi_nm, std::string& err) {
+  if (!(lo_nm > 0) || !(hi_nm >= lo_nm) || !std::isfinite(hi_nm)) return refuse(err, ODW_ERR_INVALID, "dispersion: wavelengths must be finite and > 0");
+  for (int g = 0; g < n_groups; ++g) {
+    if (kind[g] == ODW_DISP_NONE) continue;
+    const double* c = coef + ODW_DISP_COEFS * g;
+    char buf[200];
+    if (kind[g] == ODW_DISP_SELLMEIER)
+      for (int i = 0; i < 3; ++i) {
+        if (!(c[3 + i] > 0)) continue;
+        const double pole = 1000.0 * std::sqrt(c[3 + i]);
+        if (pole >= lo_nm && pole <= hi_nm) {
+          std::snprintf(buf, sizeof buf, "dispersion: group %d: Sellmeier pole at %.6g nm inside the wavelength range [%.6g, %.6g] nm", g, pole, lo_nm, hi_nm);
+          err = buf;
+          return ODW_ERR_INVALID;
+        }
+      }
+    // (Cauchy: n = A + B x + C x^2 in x = 1 / lambda^2 has one extremum, at x = -B / (2 C): with the ends, it decides
+    //  exactly -- judged in place of the last sample but one)
+    double extremum_nm = 0.0;
+    if (kind[g] == ODW_DISP_CAUCHY && c[2] != 0.0) {
+      const double x = -c[1] / (2.0 * c[2]);
+      if (x > 0.0) extremum_nm = 1000.0 / std::sqrt(x);
+      if (!(extremum_nm >= lo_nm && extremum_nm <= hi_nm)) extremum_nm = 0.0;
+    }
+    for (int k = 0; k < kDispSamples; ++k) {
+      double w = k == kDispSamples - 1 ? hi_nm : lo_nm + (hi_nm - lo_nm) * (double)k / (double)(kDispSamples - 1);
+      if (k == kDispSamples - 2 && extremum_nm > 0.0) w = extremum_nm;
+      const double n = disp_index(kind[g], c, w);
+      if (!std::isfinite(n) || !(n >= 1.0)) {
+        std::snprintf(buf, sizeof buf, "dispersion: group %d: index %.6g at %.6g nm (must be finite and >= 1)", g, n, w);
+        err = buf;
+        return ODW_ERR_INVALID;
+      }
+    }
+  }
+  return ODW_OK;
+}
+
+// odw_set_spectrum's validation (include/odw_trace.h says what the two modes hold)
+inline int spectrum_validate(int mode, int n, const double* wl, const double* cdf, std::string& err) {
+  if (mode != ODW_SPECTRUM_LINES && mode != ODW_SPECTRUM_DENSITY) return refuse(err, ODW_ERR_INVALID, "odw_set_spectrum: unknown mode");
+  if (n < (mode == ODW_SPECTRUM_DENSITY ? 2 : 1) || !wl || !cdf) return refuse(err, ODW_ERR_INVALID, "odw_set_spectrum: bad argument");
+  for (int j = 0; j < n; ++j) {
+    if (!(wl[j] > 0) || !std::isfinite(wl[j])) return refuse(err, ODW_ERR_INVALID, "odw_set_spectrum: wavelengths must be finite and > 0");
+    if (j && !(wl[j] > wl[j - 1])) return refuse(err, ODW_ERR_INVALID, "odw_set_spectrum: wavelengths not ascending");
+    if (!(cdf[j] >= 0.0 && cdf[j] <= 1.0) || (j && cdf[j] < cdf[j - 1])) return refuse(err, ODW_ERR_INVALID, "odw_set_spectrum: cdf not monotone within [0, 1]");
+  }
+  if ((mode == ODW_SPECTRUM_DENSITY && cdf[0] != 0.0) || cdf[n - 1] != 1.0)
+    return refuse(err, ODW_ERR_INVALID, "odw_set_spectrum: the cdf must run from 0 to 1");
+  return ODW_OK;
+}
+
+// the device table of a spectrum: n interleaved (cdf, wavelength) pairs, then the segment slopes (append_slopes)
+inline void spectrum_table(int n, const double* wl, const double* cdf, std::vector<double>& tab) {
+  tab.assign((size_t)n * 2, 0.0);
+  for (int j = 0; j < n; ++j) { tab[2 * (size_t)j] = cdf[j]; tab[2 * (size_t)j + 1] = wl[j]; }
+  append_slopes(tab, 1, (size_t)n);
+}
+
 // host half of odw_upload_scene: validation and the host copies of every table.  hs is complete only where the
 // answer is ODW_OK
 int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) {
@@ -853,6 +974,7 @@ struct BuildOptions {
   bool mesh_kernel = true;                  // the eight-wide tree for scenes with facets
   bool cones = true;                        // normal cones in its nodes
   bool cone_stats = false;                  // diagnostics on stderr: how many slots carry a cone
+  bool force_tree = false;                  // a binary tree also for a scene the flat loop takes (spectral launches)
 };
 
 // ---- rectilinear grid for big analytic scenes (odw_grid.hip) ---------------------------------
@@ -1159,6 +1281,7 @@ struct SpecLayout {
   int gf = 0, gd = 0, gi = 0;                       // group_f64, group_gdir, group_i32 rows
   std::vector<int> frame, par, box, der;            // per primitive (box, der: -1 = none)
   std::vector<int> box_of, box_shared;
+  std::vector<int> dc;                              // spectral variant: per group, its six dispersion coefficients (-1: none); else empty
   bool fits(size_t params_bytes) const { return ((params_bytes + 7) & ~(size_t)7) + 8 + (size_t)size * 8 <= kSpecArgBytes; }
 };
 
@@ -1171,7 +1294,9 @@ inline int spec_derived_count(int type) {
   }
 }
 
-inline SpecLayout spec_image_layout(const HostScene& hs) {
+// disp_kind (spectral variant of the compiled kernel): six coefficient words per dispersive group, behind everything
+// else -- the offsets of every other piece are those of the plain layout
+inline SpecLayout spec_image_layout(const HostScene& hs, const int32_t* disp_kind = nullptr) {
   SpecLayout L;
   const int n = L.n = hs.n_prims, ng = L.ng = hs.n_groups;
   spec_box_sharing(hs, L.box_of, L.box_shared);
@@ -1188,6 +1313,11 @@ inline SpecLayout spec_image_layout(const HostScene& hs) {
     if (faces && L.box_of[p] == p) { L.box[p] = at; at += 6; }
     const int nd = faces ? spec_derived_count(hs.prim_i32[4 * p]) : 0;
     if (nd) { L.der[p] = at; at += nd; }
+  }
+  if (disp_kind) {
+    L.dc.assign(std::max(1, ng), -1);
+    for (int g = 0; g < ng; ++g)
+      if (disp_kind[g]) { L.dc[g] = at; at += ODW_DISP_COEFS; }
   }
   L.size = at;
   return L;
@@ -1208,10 +1338,14 @@ inline void box_centre_half(double lo, double hi, double& c, double& h) {
 // sequence of IEEE operations intersect_prim performs on the device for it (odw_kernels.hip, compiled with
 // -ffp-contract=on): std::fma where a product and a sum of ONE expression fuse there, plain operations elsewhere --
 // and nothing else fuses here.
-inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const SpecLayout& L, double* img) {
+inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const SpecLayout& L, double* img,
+                             const double* disp_coef = nullptr) {
 #pragma clang fp contract(off)
   const double tol = lim.dist_tol;
   std::fill(img, img + L.size, 0.0);
+  if (disp_coef)
+    for (int g = 0; g < (int)L.dc.size() && g < L.ng; ++g)
+      if (L.dc[g] >= 0) std::memcpy(&img[L.dc[g]], disp_coef + ODW_DISP_COEFS * g, ODW_DISP_COEFS * sizeof(double));
   img[0] = tol;
   img[1] = lim.max_ray_length + tol;
   img[2] = 2.0 * tol;
@@ -1297,8 +1431,8 @@ int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, in
   }
   // (triangles are only known to the BVH kernels, paraboloids to the BVH and grid kernels, ellipsoids to the binary
   //  tree and the grid kernel: beside facets they take the binary tree, not the mesh kernel's eight-wide one)
-  if (n <= flat_limit && !has_triangles && !has_paraboloids && !has_ellipsoids) return ODW_OK;
-  if (!has_triangles) build_grid(hs, boxes, A);
+  if (n <= flat_limit && !has_triangles && !has_paraboloids && !has_ellipsoids && !opt.force_tree) return ODW_OK;
+  if (!has_triangles && !opt.force_tree) build_grid(hs, boxes, A);
   // float32 traversal boxes: enlarge by what float rounding of the ray origin
   // and of the slab arithmetic can cost (see ray_box_f32 in odw_kernels.hip)
   for (int p = 0; p < n; ++p)

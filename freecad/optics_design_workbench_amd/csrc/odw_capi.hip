@@ -195,6 +195,22 @@ struct odw_ctx {
   TraceParams P;
   odw_detector_desc det_desc;
 
+  // dispersion of the scene's groups (odw_set_dispersion) and spectrum of the point source (odw_set_spectrum)
+  bool disp_on = false;
+  int32_t disp_kind[ODW_MAX_GROUPS] = {};
+  double disp_coef[ODW_MAX_GROUPS * ODW_DISP_COEFS] = {};
+  std::vector<double> base_ior;            // the groups' constants as uploaded (hs.group_f64[4 g] holds the folded values)
+  bool fold_dirty = false;                 // dispersion or scene changed since the fold
+  double fold_wl = 0;                      // wavelength the table words of dispersive groups were folded at
+  DevBuf d_disp_kind, d_disp_coef, spec_tab, ray_wl, wl_rays, wl_out;
+  int spec_n = 0, spec_mode = 0;           // the bound spectrum (0 knots: none)
+  double spec_lo = 0, spec_hi = 0;         // its ends (nm)
+  hipFunction_t spec_chroma_fn[2] = {nullptr, nullptr};   // the compiled kernel's variants for spectral launches: without / with the power plane
+  bool spec_chroma_failed = false;         // ... could not be built for this binding: spectral launches walk the tree
+  SpecLayout spec_chroma_layout;           // ... and their value image (the plain one + the dispersion coefficients)
+  DevBuf chroma_nodes, chroma_prims;       // the binary tree spectral launches walk in a scene that has none of its own
+  int chroma_n_nodes = 0;                  // 0: to be built
+
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> free_events;
@@ -348,6 +364,7 @@ int upload_accel(odw_ctx* ctx, const SceneAccel& A) {
 int build_bvh(odw_ctx* ctx) {
   ctx->bvh_dirty = false;
   ctx->spec_dirty = true;
+  ctx->chroma_n_nodes = 0;
   std::vector<Box> boxes;
   compute_boxes(ctx->hs, ctx->P.lim.dist_tol, boxes);
   SceneAccel A;
@@ -461,6 +478,58 @@ int presort_rays(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed) {
 // compiled or flat; or scenes that have structures only because of their paraboloids or ellipsoids: compiled.)
 enum class TraceKernel { flat = kAccelFlat, grid = kAccelGrid, tree = kAccelTree, mesh = kAccelWide, compiled };
 
+// Monochromatic launches and dispersion: the index of every dispersive group at the launch wavelength goes into its table
+// word (hs.group_f64[4 g], from which a compiled scene's image is built per launch, and the device table the generic
+// kernels read) -- on the host, before the launch, again when wavelength, dispersion or scene have changed.  No kernel
+// knows about it.
+int fold_dispersion(odw_ctx* ctx) {
+  if (!ctx->disp_on && !ctx->fold_dirty) return ODW_OK;
+  const double wl = ctx->P.wavelength;
+  if (!ctx->fold_dirty && wl == ctx->fold_wl) return ODW_OK;
+  const int G = ctx->hs.n_groups;
+  if (ctx->disp_on) {
+    std::string err;
+    const int rc = disp_check_range(G, ctx->disp_kind, ctx->disp_coef, wl, wl, err);
+    if (rc) return fail(ctx, rc, err);
+  }
+  for (int g = 0; g < G && g < (int)ctx->base_ior.size(); ++g)
+    ctx->hs.group_f64[4 * (size_t)g] = (ctx->disp_on && ctx->disp_kind[g]) ? disp_index(ctx->disp_kind[g], ctx->disp_coef + ODW_DISP_COEFS * g, wl)
+                                                                           : ctx->base_ior[(size_t)g];
+  int rc = upload(ctx, ctx->group_f64, ctx->hs.group_f64.data(), ctx->hs.group_f64.size() * sizeof(double));
+  if (rc) return rc;
+  ctx->fold_wl = wl;
+  ctx->fold_dirty = false;
+  return ODW_OK;
+}
+
+// the context's dispersion as the CHROMA kernels read it (all kinds 0 while none is set)
+int upload_dispersion(odw_ctx* ctx) {
+  int rc;
+  if ((rc = upload(ctx, ctx->d_disp_kind, ctx->disp_kind, sizeof ctx->disp_kind))) return rc;
+  return upload(ctx, ctx->d_disp_coef, ctx->disp_coef, sizeof ctx->disp_coef);
+}
+
+// Spectral launches walk the binary tree.  A scene the flat loop takes has none: one is built for them, kept beside the
+// scene's own structures (which stay what they are: the monochromatic launches of the same scene keep their kernel).
+int chroma_tree(odw_ctx* ctx) {
+  if (ctx->chroma_n_nodes) return ODW_OK;
+  std::vector<Box> boxes;
+  HostScene hs = ctx->hs;                  // (compute_boxes writes headers and flags: the context's stay as build_bvh left them)
+  compute_boxes(hs, ctx->P.lim.dist_tol, boxes);
+  SceneAccel A;
+  std::string err;
+  BuildOptions opt = build_options();
+  opt.force_tree = true;
+  int rc = build_accel(hs, std::move(boxes), ctx->P.lim.dist_tol, ctx->flat_limit, opt, A, err);
+  if (rc) return fail(ctx, rc, err);
+  if (A.nodes.empty()) return fail(ctx, ODW_ERR_DEVICE, "spectral launch: no binary tree could be built for the scene");
+  if ((rc = upload(ctx, ctx->chroma_nodes, A.nodes.data(), A.nodes.size() * sizeof(BvhNode)))) return rc;
+  if ((rc = upload(ctx, ctx->chroma_prims, A.order.data(), A.order.size() * sizeof(int)))) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (A goes out of scope)
+  ctx->chroma_n_nodes = (int)A.nodes.size();
+  return ODW_OK;
+}
+
 TraceKernel choose_kernel(const odw_ctx* ctx, uint32_t flags, bool batch) {
   const DeviceScene& S = ctx->P.scene;
   const bool segments = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0, stoch = ctx->n_samplers > 0;
@@ -469,12 +538,34 @@ TraceKernel choose_kernel(const odw_ctx* ctx, uint32_t flags, bool batch) {
   return (TraceKernel)accel_kind(ctx->P.grid.nx > 0 && !stoch && !segments, S.n_nodes != 0, S.bvh_leaf != nullptr && !segments);
 }
 
+// ray_wl: a wavelength per explicit ray (device array).  A launch with it, or one that generates its rays under a bound
+// spectrum, is SPECTRAL: the CHROMA variant of the compiled kernel where one is bound for the scene as it is, else the
+// CHROMA instantiations of the binary tree.  Every other launch is monochromatic: the dispersion is folded into the
+// tables, the kernels are those of before.  wl_lo, wl_hi: the smallest and largest of ray_wl.
 int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32_t flags,
-                 const double* ray_o, const double* ray_d, const double* ray_p) {
+                 const double* ray_o, const double* ray_d, const double* ray_p, const double* ray_wl = nullptr,
+                 double wl_lo = 0.0, double wl_hi = 0.0) {
   const bool explicit_rays = ray_o != nullptr;
   if (!ctx->have_scene || !ctx->have_limits) return fail(ctx, ODW_ERR_NO_SCENE, "scene/limits not uploaded");
   if (!explicit_rays && !ctx->have_source) return fail(ctx, ODW_ERR_NO_SCENE, "source not uploaded");
   if (n == 0) return ODW_OK;
+  const bool spectral = ray_wl != nullptr || (!explicit_rays && ctx->spec_n > 0);
+  if (ctx->batch_launch && ctx->disp_on)
+    return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: a batch with a dispersion set (per-scene dispersion is out of scope)");
+  if (spectral) {
+    if (ctx->batch_launch) return fail(ctx, ODW_ERR_UNSUPPORTED, "spectral launch: batches carry no spectrum (spectral batches are out of scope)");
+    if (ctx->n_samplers > 0) return fail(ctx, ODW_ERR_UNSUPPORTED, "spectral launch: scenes with stochastic surfaces are not supported");
+    if (!ray_wl && ctx->emitter_active) return fail(ctx, ODW_ERR_UNSUPPORTED, "spectral launch: surface sources carry no spectrum");
+    if (ctx->disp_on) {
+      std::string err;
+      const int rc = disp_check_range(ctx->hs.n_groups, ctx->disp_kind, ctx->disp_coef, ray_wl ? wl_lo : ctx->spec_lo,
+                                      ray_wl ? wl_hi : ctx->spec_hi, err);
+      if (rc) return fail(ctx, rc, err);
+    }
+  } else {
+    const int rc = fold_dispersion(ctx);
+    if (rc) return rc;
+  }
   ctx->ph_valid = false;           // the hit list is about to change
   if (!ctx->batch_launch) {
     ctx->hit_ray_begin = ctx->hit_ray_end ? std::min<uint64_t>(ctx->hit_ray_begin, first) : first;
@@ -551,7 +642,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // chunks of ODW_CHUNK rays are handed out dynamically inside the kernel
   constexpr int grid_mult = 8;
   const bool pw = (flags & ODW_TRACE_POWER_HISTOGRAM) != 0;     // the <..., POWER = true> instantiation of whichever kernel runs
-  if (pw && ctx->spec_fn && !ctx->spec_power_fn && !ctx->spec_power_failed &&
+  if (pw && !spectral && ctx->spec_fn && !ctx->spec_power_fn && !ctx->spec_power_failed &&
       !(ctx->spec_power_wait && !ctx->spec_power_wait->load())) {
     // the compiled kernel's POWER variant: bound on the first weighted launch of the structure (a compilation of its own,
     // cached like the other).  ODW_COMPILE_STRUCTURE: that launch waits for it.  ODW_COMPILE_AUTO: the structure has earned
@@ -580,7 +671,37 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       ctx->err = keep_err;
     }
   }
-  const TraceKernel kernel = choose_kernel(ctx, flags, batch);   // (after the two bindings above: they decide `compiled`)
+  // The compiled kernel's CHROMA variant (its header carries the context's dispersion): bound on the first spectral launch
+  // while the single-scene kernel is bound, ODW_COMPILE_STRUCTURE only; one attempt per binding, and a variant that cannot
+  // be built does not become the error of a launch that succeeds on the tree
+  const bool segments = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0;
+  if (spectral && !segments && ctx->spec_fn && !ctx->spec_chroma_fn[pw] && !ctx->spec_chroma_failed) {
+    const std::string keep_err = ctx->err;
+    if (spec_bind(ctx, pw ? kSpecChromaPower : kSpecChroma) != ODW_OK) {
+      ctx->spec_chroma_fn[pw] = nullptr;
+      ctx->spec_chroma_failed = true;
+      ctx->err = keep_err;
+    }
+  }
+  // (after the bindings above: they decide `compiled`.)  A spectral launch goes to the compiled kernel when its CHROMA
+  // variant is bound for the scene as it is, else to the binary tree -- never to the flat, grid or mesh kernel, which know
+  // no wavelength per ray
+  const bool chroma_compiled = spectral && !segments && ctx->spec_fn && ctx->spec_chroma_fn[pw] && ctx->spec_lean == ctx->hs.lean;
+  const TraceKernel kernel = spectral ? (chroma_compiled ? TraceKernel::compiled : TraceKernel::tree) : choose_kernel(ctx, flags, batch);
+  DeviceChroma chroma;
+  std::memset(&chroma, 0, sizeof chroma);
+  TraceParams Pc;                          // the spectral launch's arguments: P, with the tree built for it where the scene has none
+  if (spectral) {
+    int rc;
+    if (!ctx->d_disp_kind.p && (rc = upload_dispersion(ctx))) return rc;
+    if (!chroma_compiled && !P.scene.n_nodes && (rc = chroma_tree(ctx))) return rc;
+    chroma.ray_wl = ray_wl;
+    chroma.spec_tab = ray_wl ? nullptr : (const double*)ctx->spec_tab.p;
+    chroma.spec_n = ctx->spec_n;
+    chroma.spec_mode = ctx->spec_mode;
+    chroma.disp_kind = (const int32_t*)ctx->d_disp_kind.p;
+    chroma.disp_coef = (const double*)ctx->d_disp_coef.p;
+  }
   if (batch && kernel != TraceKernel::compiled && flat_but_for_rare_quadrics(ctx->hs, ctx->flat_limit))
     return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: a batch with paraboloids or ellipsoids needs the kernel compiled against the scene, "
                                           "which is not bound (odw_compile_scene: ODW_COMPILE_STRUCTURE)");
@@ -669,7 +790,24 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     int rc = presort_rays(ctx, first, n, seed);       // (inside the timed window: part of the launch's cost)
     if (rc) return rc;
   }
-  if (use_spec) {
+  if (chroma_compiled) {
+    int rc = spec_launch(ctx, grid, ctx->spec_chroma_fn[pw], false, &chroma);
+    if (rc) return rc;
+  } else if (spectral) {
+    Pc = P;
+    if (!P.scene.n_nodes) {
+      Pc.scene.bvh_nodes = (const float*)ctx->chroma_nodes.p;
+      Pc.scene.bvh_prims = (const int32_t*)ctx->chroma_prims.p;
+      Pc.scene.n_nodes = ctx->chroma_n_nodes;
+    }
+    const bool seg = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0;
+#define ODW_CHROMA_LAUNCH(S, W, A) hipLaunchKernelGGL((odw_trace_chroma_kernel<S, W, A>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma)
+#define ODW_CHROMA_LAUNCH_A(S, W) do { if (asph) ODW_CHROMA_LAUNCH(S, W, true); else ODW_CHROMA_LAUNCH(S, W, false); } while (0)
+    if (seg) { if (pw) ODW_CHROMA_LAUNCH_A(true, true); else ODW_CHROMA_LAUNCH_A(true, false); }
+    else { if (pw) ODW_CHROMA_LAUNCH_A(false, true); else ODW_CHROMA_LAUNCH_A(false, false); }
+#undef ODW_CHROMA_LAUNCH_A
+#undef ODW_CHROMA_LAUNCH
+  } else if (use_spec) {
     int rc = spec_launch(ctx, grid, batch ? ctx->spec_batch_fn : pw ? ctx->spec_power_fn : ctx->spec_fn, batch);
     if (rc) return rc;
   } else if (batch) {
@@ -883,6 +1021,9 @@ void odw_destroy(odw_ctx* ctx) {
   for (DevBuf* b : {&ctx->em_prim_f64, &ctx->em_prim_i32, &ctx->em_cond, &ctx->em_face_i32, &ctx->em_face_cdf,
                     &ctx->em_t_tab, &ctx->em_t_guide, &ctx->em_o, &ctx->em_d, &ctx->em_tri_nrm, &ctx->tri_nrm, &ctx->phi_guide, &ctx->asph})
     release(*b);
+  for (DevBuf* b : {&ctx->d_disp_kind, &ctx->d_disp_coef, &ctx->spec_tab, &ctx->ray_wl, &ctx->wl_rays, &ctx->wl_out, &ctx->chroma_nodes,
+                    &ctx->chroma_prims})
+    release(*b);
   for (auto& sb : ctx->surf_bufs) { release(sb.phi_tab); release(sb.t_tab); release(sb.t_guide); }
   release(ctx->d_samplers);
   release(ctx->d_group_sampler);
@@ -962,6 +1103,172 @@ int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* s) {
   ctx->spec_fn = nullptr;
   ctx->n_samplers = 0;   // surface samplers belong to the previous scene's groups
   ctx->batch_n = 0;      // an uploaded batch belonged to the previous scene (odw_upload_scene_batch sets it again after this call)
+  // ... and so did a dispersion: cleared; the tables just uploaded hold the groups' constants
+  ctx->base_ior.assign((size_t)ctx->hs.n_groups, 1.0);
+  for (int g = 0; g < ctx->hs.n_groups; ++g) ctx->base_ior[(size_t)g] = ctx->hs.group_f64[4 * (size_t)g];
+  ctx->fold_dirty = false;
+  ctx->chroma_n_nodes = 0;
+  if (ctx->disp_on) {
+    ctx->disp_on = false;
+    std::memset(ctx->disp_kind, 0, sizeof ctx->disp_kind);
+    std::memset(ctx->disp_coef, 0, sizeof ctx->disp_coef);
+    if (ctx->d_disp_kind.p && (rc = upload_dispersion(ctx))) return rc;
+  }
+  return ODW_OK;
+}
+
+int odw_set_dispersion(odw_ctx* ctx, int32_t n_groups, const int32_t* kind, const double* coef) {
+  if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_dispersion: null ctx");
+  if (n_groups == 0) {
+    if (!ctx->disp_on) return ODW_OK;
+  } else {
+    if (!ctx->have_scene) return fail(ctx, ODW_ERR_NO_SCENE, "odw_set_dispersion before odw_upload_scene");
+    if (n_groups != ctx->hs.n_groups) return fail(ctx, ODW_ERR_INVALID, "odw_set_dispersion: n_groups is not the scene's");
+    std::string err;
+    const int rc = disp_validate(n_groups, kind, coef, ctx->hs.group_i32.data(), err);
+    if (rc) return fail(ctx, rc, err);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::memset(ctx->disp_kind, 0, sizeof ctx->disp_kind);
+  std::memset(ctx->disp_coef, 0, sizeof ctx->disp_coef);
+  ctx->disp_on = false;
+  for (int g = 0; g < n_groups; ++g) {
+    ctx->disp_kind[g] = kind[g];
+    if (kind[g]) {
+      ctx->disp_on = true;
+      std::memcpy(ctx->disp_coef + ODW_DISP_COEFS * g, coef + ODW_DISP_COEFS * g, ODW_DISP_COEFS * sizeof(double));
+    }
+  }
+  ctx->fold_dirty = true;
+  // (the groups' formulas are part of the compiled CHROMA variant's header: bound again by the next spectral launch)
+  ctx->spec_chroma_fn[0] = ctx->spec_chroma_fn[1] = nullptr;
+  ctx->spec_chroma_failed = false;
+  return upload_dispersion(ctx);
+}
+
+int odw_compiled_chroma_info(odw_ctx* ctx, int32_t* bound) {
+  if (!ctx || !bound) return fail(ctx, ODW_ERR_INVALID, "odw_compiled_chroma_info: bad argument");
+  *bound = (ctx->spec_fn && (ctx->spec_chroma_fn[0] || ctx->spec_chroma_fn[1]) && !ctx->spec_dirty && !ctx->bvh_dirty) ? ctx->compile_mode : 0;
+  return ODW_OK;
+}
+
+int odw_compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                             const int32_t* disp_kind, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
+  if (!scene || !limits || !disp_kind) return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check_chroma: bad argument");
+  HostScene tmp;
+  std::string refusal;
+  int rc = scene_host_tables(scene, tmp, refusal);
+  if (rc) return fail(nullptr, rc, refusal);
+  std::vector<Box> boxes;
+  compute_boxes(tmp, limits->dist_tol, boxes);
+  const std::string why = spec_ineligible(tmp);
+  if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_compile_check_chroma: " + why);
+  const std::string text = spec_text(tmp, 0, disp_kind) +
+      (source ? spec_source_text(spec_source_key(source->xform, source->n_t_rows, true, std::isfinite(source->focal_length))) : "");
+  if (header_out && header_capacity) {
+    const size_t k = std::min<size_t>(text.size(), (size_t)header_capacity - 1);
+    std::memcpy(header_out, text.data(), k);
+    header_out[k] = 0;
+  }
+  std::vector<char> code;
+  std::string err;
+  if (!spec_compile(text, arch && *arch ? arch : "gfx950", code, err)) return fail(nullptr, ODW_ERR_DEVICE, err);
+  if (code_bytes) *code_bytes = code.size();
+  return ODW_OK;
+}
+
+int odw_set_spectrum(odw_ctx* ctx, int32_t mode, int32_t n_knots, const double* wavelength_nm, const double* cdf) {
+  if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_spectrum: null ctx");
+  if (n_knots == 0) { ctx->spec_n = 0; ctx->spec_mode = 0; return ODW_OK; }
+  std::string err;
+  int rc = spectrum_validate(mode, n_knots, wavelength_nm, cdf, err);
+  if (rc) return fail(ctx, rc, err);
+  if (!ctx->have_source || ctx->emitter_active)
+    return fail(ctx, ctx->emitter_active ? ODW_ERR_UNSUPPORTED : ODW_ERR_NO_SCENE,
+                ctx->emitter_active ? "odw_set_spectrum: surface sources carry no spectrum" : "odw_set_spectrum before odw_upload_source");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<double> tab;
+  spectrum_table(n_knots, wavelength_nm, cdf, tab);
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // a running launch may still read the old table
+  if ((rc = upload(ctx, ctx->spec_tab, tab.data(), tab.size() * sizeof(double)))) return rc;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // (tab goes out of scope)
+  ctx->spec_n = n_knots;
+  ctx->spec_mode = mode;
+  ctx->spec_lo = wavelength_nm[0];
+  ctx->spec_hi = wavelength_nm[n_knots - 1];
+  return ODW_OK;
+}
+
+int odw_spectrum_check(int32_t mode, int32_t n_knots, const double* wavelength_nm, const double* cdf) {
+  std::string err;
+  const int rc = spectrum_validate(mode, n_knots, wavelength_nm, cdf, err);
+  return rc ? fail(nullptr, rc, err) : ODW_OK;
+}
+
+int odw_dispersion_check(int32_t n_groups, const int32_t* kind, const double* coef, double lo_nm, double hi_nm) {
+  std::string err;
+  int rc = disp_validate(n_groups, kind, coef, nullptr, err);
+  if (!rc) rc = disp_check_range(n_groups, kind, coef, lo_nm, hi_nm, err);
+  return rc ? fail(nullptr, rc, err) : ODW_OK;
+}
+
+int odw_dispersion_index(odw_ctx* ctx, int32_t group, int32_t kind, const double* coef, uint64_t n,
+                         const double* wavelength_nm, double* out, int32_t on_device) {
+  if ((n && (!wavelength_nm || !out)) || (!ctx && on_device)) return fail(ctx, ODW_ERR_INVALID, "odw_dispersion_index: bad argument");
+  double constant = 1.0;
+  if (ctx) {
+    if (!ctx->have_scene || group < 0 || group >= ctx->hs.n_groups) return fail(ctx, ODW_ERR_INVALID, "odw_dispersion_index: group out of range");
+    kind = ctx->disp_kind[group];
+    coef = ctx->disp_coef + ODW_DISP_COEFS * group;
+    constant = ctx->base_ior[(size_t)group];
+  } else {
+    int32_t k1 = kind;
+    std::string err;
+    const int rc = kind == ODW_DISP_NONE ? ODW_ERR_INVALID : disp_validate(1, &k1, coef, nullptr, err);
+    if (rc) return fail(nullptr, rc, kind == ODW_DISP_NONE ? "odw_dispersion_index: a glass without a context needs a dispersion kind" : err);
+  }
+  if (kind == ODW_DISP_NONE) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = constant;
+    return ODW_OK;
+  }
+  if (!on_device) {
+    for (uint64_t i = 0; i < n; ++i) out[i] = disp_index(kind, coef, wavelength_nm[i]);
+    return ODW_OK;
+  }
+  if (n == 0) return ODW_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // (the staging buffers are shared with odw_ray_wavelengths)
+  int rc;
+  if ((rc = ensure(ctx, ctx->wl_rays, n * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, ctx->wl_out, n * sizeof(double)))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->wl_rays.p, wavelength_nm, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  DispCoefs dc;
+  std::memcpy(dc.c, coef, sizeof dc.c);
+  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->n_cu * 16));
+  hipLaunchKernelGGL(odw_disp_index_kernel, dim3(grid), dim3(256), 0, ctx->stream, (int)kind, dc, (const double*)ctx->wl_rays.p, n,
+                     (double*)ctx->wl_out.p);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->wl_out.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return ODW_OK;
+}
+
+int odw_ray_wavelengths(odw_ctx* ctx, uint64_t n, const uint64_t* rays, uint64_t seed, double* out) {
+  if (!ctx || (n && (!rays || !out))) return fail(ctx, ODW_ERR_INVALID, "odw_ray_wavelengths: bad argument");
+  if (ctx->spec_n <= 0) return fail(ctx, ODW_ERR_INVALID, "odw_ray_wavelengths: no spectrum bound (odw_set_spectrum)");
+  if (n == 0) return ODW_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  int rc;
+  if ((rc = ensure(ctx, ctx->wl_rays, n * sizeof(uint64_t)))) return rc;
+  if ((rc = ensure(ctx, ctx->wl_out, n * sizeof(double)))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->wl_rays.p, rays, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->n_cu * 16));
+  hipLaunchKernelGGL(odw_ray_wavelengths_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const double*)ctx->spec_tab.p, (int)ctx->spec_n,
+                     (int)ctx->spec_mode, (const uint64_t*)ctx->wl_rays.p, n, seed, (double*)ctx->wl_out.p);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(out, ctx->wl_out.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return ODW_OK;
 }
 
@@ -1319,6 +1626,7 @@ static int upload_source(odw_ctx* ctx, const odw_source_desc* s, bool guides) {
   ctx->P.wavelength = s->wavelength;
   ctx->have_source = true;
   ctx->emitter_active = false;
+  ctx->spec_n = ctx->spec_mode = 0;        // (a spectrum belonged to the previous source)
   ctx->source_key = spec_source_key(ctx->h_source);
   if (ctx->spec_source_key && ctx->spec_source_key != ctx->source_key) ctx->spec_dirty = true;   // a source of another structure
   return ODW_OK;
@@ -1429,7 +1737,8 @@ int odw_upload_surface_source(odw_ctx* ctx, const odw_surface_source_desc* s) {
   ctx->P.wavelength = s->wavelength;
   ctx->have_source = true;
   ctx->emitter_active = true;
-  ctx->source_key = 0;                     // (emitted rays reach the trace kernels through buffers, like explicit ones)
+  ctx->spec_n = ctx->spec_mode = 0;        // (a spectrum belonged to the previous source; surface sources carry none)
+  ctx->source_key = 0;                   // (emitted rays reach the trace kernels through buffers, like explicit ones)
   return ODW_OK;
 }
 
@@ -1895,9 +2204,29 @@ int odw_archive_reset(odw_ctx* ctx) {
   return ODW_OK;
 }
 
+static int trace_rays(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, const double* origins, const double* directions,
+                      const double* powers, const double* wavelengths, double wl_lo, double wl_hi, uint32_t flags);
+
 int odw_trace_rays(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, const double* origins,
                    const double* directions, const double* powers, uint32_t flags) {
   if (!ctx || !origins || !directions) return fail(ctx, ODW_ERR_INVALID, "odw_trace_rays: null argument");
+  return trace_rays(ctx, first_ray, n_rays, origins, directions, powers, nullptr, 0.0, 0.0, flags);
+}
+
+int odw_trace_rays_spectral(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, const double* origins,
+                            const double* directions, const double* powers, const double* wavelengths, uint32_t flags) {
+  if (!ctx || !origins || !directions || !wavelengths) return fail(ctx, ODW_ERR_INVALID, "odw_trace_rays_spectral: null argument");
+  double lo = INFINITY, hi = -INFINITY;
+  for (uint64_t i = 0; i < n_rays; ++i) {
+    if (!(wavelengths[i] > 0) || !std::isfinite(wavelengths[i])) return fail(ctx, ODW_ERR_INVALID, "odw_trace_rays_spectral: wavelengths must be finite and > 0");
+    lo = std::min(lo, wavelengths[i]);
+    hi = std::max(hi, wavelengths[i]);
+  }
+  return trace_rays(ctx, first_ray, n_rays, origins, directions, powers, wavelengths, lo, hi, flags);
+}
+
+static int trace_rays(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, const double* origins, const double* directions,
+                      const double* powers, const double* wavelengths, double wl_lo, double wl_hi, uint32_t flags) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   batch_unselect(ctx);
   if (n_rays == 0) return ODW_OK;
@@ -1921,8 +2250,12 @@ int odw_trace_rays(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, const doub
   if (powers) {
     if ((rc = upload(ctx, ctx->ray_p, powers, n_rays * sizeof(double)))) return rc;
   }
+  if (wavelengths) {
+    if ((rc = upload(ctx, ctx->ray_wl, wavelengths, n_rays * sizeof(double)))) return rc;
+  }
   rc = launch_trace(ctx, first_ray, n_rays, ctx->surface_seed, flags, (const double*)ctx->ray_o.p,
-                    (const double*)ctx->ray_d.p, powers ? (const double*)ctx->ray_p.p : nullptr);
+                    (const double*)ctx->ray_d.p, powers ? (const double*)ctx->ray_p.p : nullptr,
+                    wavelengths ? (const double*)ctx->ray_wl.p : nullptr, wl_lo, wl_hi);
   if (rc) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // caller's arrays may go away
   return ODW_OK;

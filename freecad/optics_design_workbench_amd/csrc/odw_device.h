@@ -236,4 +236,21 @@ struct TraceParams {
 };
 #define ODW_ASPH_ROW 12         // doubles per row: a_1 .. a_8, M (curvature bound), L (slope bound), z_min (lowest sag), spare
 
+// Word 3 of the Philox counter says which draw a number belongs to.  In use: 0 ray generation (ray_uniforms), 1 + kind
+// (1, 2) the two angles of a surface draw and 17 + kind (17, 18) its family member (surface_draw), 3 and 4 the emitter's
+// face / acceptance and face coordinates, 5 its angles (odw_emit_kernel).  The wavelength of a ray under a spectrum:
+// u = u53(c0, c1) of counter (ray_lo, ray_hi, 0, ODW_STREAM_WAVELENGTH) under the launch's seed -- a stream of its own,
+// so the geometric draws of a ray are the same with and without a spectrum.
+#define ODW_STREAM_WAVELENGTH 6u
+
+// Second kernel argument of the CHROMA instantiations (spectral launches: one wavelength per ray).  The other
+// instantiations never see it: TraceParams is what it was.
+struct DeviceChroma {
+  const double* ray_wl;         // [n_rays] wavelength (nm) of every explicit ray, or null: drawn from the spectrum
+  const double* spec_tab;       // the spectrum: n interleaved (cdf, wavelength nm) pairs, then n segment slopes; or null
+  int32_t spec_n, spec_mode;    // knots; ODW_SPECTRUM_LINES / ODW_SPECTRUM_DENSITY
+  const int32_t* disp_kind;     // [ODW_MAX_GROUPS] ODW_DISP_* (0: the constant of group_f64)
+  const double* disp_coef;      // [ODW_MAX_GROUPS * ODW_DISP_COEFS]
+};
+
 }  // namespace odw

@@ -1555,6 +1555,49 @@ __device__ __forceinline__ d3 line_grating(d3 ray, double n1, double n2, d3 norm
   return S * -1.0;
 }
 
+// ------------------------------------------- dispersion and spectra (CHROMA)
+// The index of a glass at wavelength_nm: the device twin of disp_index (odw_build.h) -- the same IEEE operations in the
+// same order, none contracted; `/` and sqrt() of float64 are correctly rounded here as on the host.
+template <class CP>
+__device__ __forceinline__ double disp_index_dev(int kind, CP coef, double wavelength_nm) {
+#pragma clang fp contract(off)
+  const double l = wavelength_nm / 1000.0;
+  const double l2 = l * l;
+  if (kind == ODW_DISP_SELLMEIER) {
+    double s = 1.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double num = coef[i] * l2, den = l2 - coef[3 + i];
+      s = s + num / den;
+    }
+    return sqrt(s);
+  }
+  const double l4 = l2 * l2;
+  const double t1 = coef[1] / l2, t2 = coef[2] / l4;
+  return (coef[0] + t1) + t2;
+}
+
+// the index of group g for a ray of wavelength wl: the formula where the group has one, the table word where not
+__device__ __forceinline__ double chroma_index(const DeviceChroma& C, cf64 group_f64, int g, double wl) {
+  const int kind = C.disp_kind[g];
+  return kind ? disp_index_dev(kind, C.disp_coef + ODW_DISP_COEFS * g, wl) : group_f64[4 * g];
+}
+
+// the wavelength the spectrum (tab: n (cdf, wavelength) pairs, then slopes) gives ray `ray` under `seed`
+__device__ __forceinline__ double spectrum_wavelength(const double* __restrict__ tab, int n, int mode, uint64_t ray, uint64_t seed) {
+  uint32_t c0 = (uint32_t)ray, c1 = (uint32_t)(ray >> 32), c2 = 0u, c3 = ODW_STREAM_WAVELENGTH;
+  philox4x32_10(c0, c1, c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32));
+  const double u = u53(c0, c1);
+  if (mode == ODW_SPECTRUM_DENSITY) return inv_cdf(tab, tab + 2 * n, 0, n - 1, u);
+  // lines: j = the number of entries cdf[.] <= u (cdf[n - 1] = 1 > u)
+  int lo = -1, hi = n - 1;             // cdf[lo] <= u < cdf[hi]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (u >= tab[2 * mid]) lo = mid; else hi = mid;
+  }
+  return tab[2 * hi + 1];
+}
+
 // ------------------------------------------- stochastic surfaces (N3)
 // FreeCAD Rotation(axis, angle) * v; a zero axis is the identity
 __device__ __forceinline__ d3 rotate(d3 axis, double angle, d3 v) {
@@ -1920,15 +1963,49 @@ __device__ __forceinline__ double medium_word(cf64 group_f64, int medium) {
   else return group_f64[4 * medium + K];
 }
 
+// A scene compiled for spectral launches (Spec::chroma()) knows every group's formula (constexpr Spec::disp(G)) and finds
+// its six coefficients in the value image at Spec::dc(G): a select over the groups that can be a medium, as
+// spec_medium_word -- the formula of a group that has one, its table word where it has none; for a group index known at
+// compile time (the group entered) everything but one branch folds.
+template <class SPEC, int G = 0>
+__device__ __forceinline__ double spec_chroma_index(cf64 group_f64, int g, double wl, double v) {
+  if constexpr (G < SPEC::NG) {
+    v = spec_chroma_index<SPEC, G + 1>(group_f64, g, wl, v);
+    if constexpr (can_be_medium(SPEC::gtype(G))) {
+      if constexpr (SPEC::disp(G) != 0) {
+        if (g == G) v = disp_index_dev(SPEC::disp(G), group_f64 + (SPEC::dc(G) - SPEC::gf), wl);
+      } else {
+        v = g == G ? group_f64[4 * G] : v;
+      }
+    }
+  }
+  return v;
+}
+// the index of the medium a ray travels in (medium >= 0) and of the group g it meets
+template <class SPEC, bool CHROMA>
+__device__ __forceinline__ double medium_index(cf64 group_f64, int medium, const DeviceChroma* C, double wl) {
+  if constexpr (CHROMA && SPEC::enabled) return spec_chroma_index<SPEC>(group_f64, medium, wl, 0.0);
+  else if constexpr (CHROMA) return chroma_index(*C, group_f64, medium, wl);
+  else return medium_word<SPEC, 0>(group_f64, medium);
+}
+template <class SPEC, bool CHROMA>
+__device__ __forceinline__ double group_index(cf64 group_f64, int g, const DeviceChroma* C, double wl) {
+  if constexpr (CHROMA && SPEC::enabled) return spec_chroma_index<SPEC>(group_f64, g, wl, 0.0);
+  else if constexpr (CHROMA) return chroma_index(*C, group_f64, g, wl);
+  else return group_f64[4 * g];
+}
+
 // K3 for one hit, the part that depends on the optical group: recording, mirror / Snell / absorb /
 // vacuum / grating, medium and sequence state (ray.py:91-281).  The generic kernels pass the group's
 // words as read from the tables; a compiled scene passes constants and the branches fold.
 // n: surface normal along the travel direction; cnt: the thread's column of event counters.
-template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec>
+// CHROMA (spectral launches): the ray carries its wavelength wl; the index of the current medium and of the group
+// entered come from the group's formula where it has one (chroma_index), and the gratings diffract by wl.
+template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec, bool CHROMA = false>
 __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, ci32 group_i32, cf64 group_gdir, int g,
                                          int gtype, bool record, d3 n, bool entering, uint64_t ray, int nint,
                                          uint32_t* cnt, uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power,
-                                         int& medium, int& seq, bool& alive) {
+                                         int& medium, int& seq, bool& alive, const DeviceChroma* C = nullptr, double wl = 0.0) {
   if (record) {
     cnt[ODW_CNT_RECORDED_HITS * 256] += 1u;
     // (block reservations and the histogram window only in the flat kernels: in the BVH kernels
@@ -1950,9 +2027,9 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
     power *= group_f64[4 * g + 1];
     ++seq;
   } else if (gtype == ODW_OPT_LENS) {
-    const double n1 = (medium >= 0) ? medium_word<SPEC, 0>(group_f64, medium) : 1.0;
+    const double n1 = (medium >= 0) ? medium_index<SPEC, CHROMA>(group_f64, medium, C, wl) : 1.0;
     double n2 = 1.0;
-    if (entering) { medium = g; n2 = group_f64[4 * g]; }
+    if (entering) { medium = g; n2 = group_index<SPEC, CHROMA>(group_f64, g, C, wl); }
     bool tir;
 #if ODW_DOUBLE == 7
     d3 ideal = snells_law(dir, n1, n2, n, tir);
@@ -1975,8 +2052,8 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
     const int order = group_i32[4 * g + 3];
     if (group_i32[4 * g + 2] == 0) {
       if (entering) {
-        const double nn = (medium >= 0) ? medium_word<SPEC, 0>(group_f64, medium) : 1.0;
-        dir = line_grating(dir, nn, nn, n, P.wavelength, order, lpm, gd, false);
+        const double nn = (medium >= 0) ? medium_index<SPEC, CHROMA>(group_f64, medium, C, wl) : 1.0;
+        dir = line_grating(dir, nn, nn, n, CHROMA ? wl : P.wavelength, order, lpm, gd, false);
         ++seq;
       }
     } else if (entering) {
@@ -1987,9 +2064,9 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
         alive = false;
       }
       medium = g;
-      dir = line_grating(dir, 1.0, group_f64[4 * g], n, P.wavelength, order, lpm, gd, true);
+      dir = line_grating(dir, 1.0, group_index<SPEC, CHROMA>(group_f64, g, C, wl), n, CHROMA ? wl : P.wavelength, order, lpm, gd, true);
     } else {
-      const double n1 = (medium >= 0) ? medium_word<SPEC, 0>(group_f64, medium) : 1.0;
+      const double n1 = (medium >= 0) ? medium_index<SPEC, CHROMA>(group_f64, medium, C, wl) : 1.0;
       bool tir;
       dir = snells_law(dir, n1, 1.0, n, tir);
       if (!tir) { medium = -1; ++seq; }
@@ -1999,11 +2076,11 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
 
 // the hit is on primitive PI of a compiled scene: its type, frame pattern, flags, group and the group's
 // optical type / recording switch are constants
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, int PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, int PI>
 __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                          cf64 group_gdir, int face, uint64_t ray, int nint, uint32_t* cnt,
                                          uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
-                                         int& skip, int& only, bool& alive) {
+                                         int& skip, int& only, bool& alive, const DeviceChroma* C, double wl) {
   constexpr int flags = SPEC::flags(PI), g = SPEC::group(PI);
   const PackedFrame<SPEC::xf(PI)> pf{sv.img + SPEC::frame(PI)};
   cf64 par = sv.img + SPEC::par(PI);
@@ -2020,8 +2097,8 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
 #endif
   const bool entering = dot(dir, n) < 0;
   if (entering) n = n * -1.0;
-  interact<false, STOCH, LEAN, POWER, SPEC>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
-                               nint, cnt, hit_state, win, point, dir, power, medium, seq, alive);
+  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
+                               nint, cnt, hit_state, win, point, dir, power, medium, seq, alive, C, wl);
   // n points along the incoming travel direction: out of the solid when leaving it, into it when entering
   const double out = entering ? -dot(dir, n) : dot(dir, n);
   if constexpr ((flags & ODW_FLAG_CONVEX) != 0) skip = out > 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
@@ -2029,13 +2106,13 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   if constexpr ((flags & ODW_FLAG_ISOLATED) != 0) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else only = -1;
 }
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, int... PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, int... PI>
 __device__ __forceinline__ void spec_hits(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                           cf64 group_gdir, int prim, int face, uint64_t ray, int nint, uint32_t* cnt,
                                           uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
-                                          int& skip, int& only, bool& alive, IndexList<int, PI...>) {
-  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
-                                                  point, dir, power, medium, seq, skip, only, alive), true)
+                                          int& skip, int& only, bool& alive, const DeviceChroma* C, double wl, IndexList<int, PI...>) {
+  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
+                                                  point, dir, power, medium, seq, skip, only, alive, C, wl), true)
                      : false) || ...);
 }
 
@@ -2097,10 +2174,13 @@ template <> struct HitBlockState<false> {
 // -- line_grating's chain of IEEE divisions and square roots, exp() -- is left out of the binary
 // BATCH (flat kernels): scenes of one structure side by side in one launch (DeviceBatch)
 // ASPH (binary tree): the instantiations scenes with an asphere are launched with
+// CHROMA (binary tree): spectral launches -- a wavelength per lane, set at every (re)generation of the lane from the
+//   explicit array or the spectrum draw (DeviceChroma), handed to interact()
 template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false,
-          class SRC = NoSource, bool ASPH = false>
-__device__ __forceinline__ void trace_body(const TraceParams& P) {
+          class SRC = NoSource, bool ASPH = false, bool CHROMA = false>
+__device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChroma* C = nullptr) {
   static_assert(!ASPH || BVH, "aspheres: the binary tree (or a compiled kernel, which knows its scene from Spec::rare())");
+  static_assert(!CHROMA || ((BVH || SPEC::enabled) && !STOCH && !BATCH), "spectral launches: the binary tree or a kernel compiled for them, no stochastic surfaces, no batches");
   static_assert(!BATCH || (!BVH && !SEG), "batch launches: flat kernels, no segment rows");
   extern __shared__ int bvh_stack[];  // ODW_BVH_STACK x 256 ints (BVH variant only)
   // per-thread event counters live in LDS (one column per thread, ds_add_u32
@@ -2149,6 +2229,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
   uint64_t i = 0;
   d3 point = mk(0, 0, 0), dir = mk(0, 0, 1);
   double power = 0;
+  double wl = 0;     // CHROMA: the ray's wavelength in nm (unused, and gone, in every other instantiation)
   int seq = 0, nint = 0, medium = -1;
   int skip = -1;     // solid the ray has just left, if that solid is convex (it cannot be met again)
   int only = -1;     // solid the ray has just entered, if that solid is isolated (it is met before anything else)
@@ -2263,6 +2344,9 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
         // renormalises every segment (ray.py:377), a no-op up to rounding
         seq = 0; nint = 0; medium = -1; skip = -1; only = -1;
         alive = true;
+        // (with the rest of the lane's state: a refilled lane must not keep its predecessor's colour)
+        if constexpr (CHROMA)
+          wl = C->ray_wl ? C->ray_wl[i] : spectrum_wavelength(C->spec_tab, C->spec_n, C->spec_mode, P.first_ray + i, P.seed);
       }
       next += take;
       if (take == 0 && idle == ~0ull) break;               // nothing live, nothing left (BATCH: a waiting unit is taken above once all lanes idle)
@@ -2307,8 +2391,8 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       uint32_t* cnt = cnt_lds + threadIdx.x;
       uint32_t* hit_state = hit_lds + (threadIdx.x >> 6) * 4;
       if constexpr (SPEC::enabled) {
-        spec_hits<STOCH, LEAN, POWER, SPEC>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
-                              hist_win, point, dir, power, medium, seq, skip, only, alive, __make_integer_seq<IndexList, int, SPEC::N>{});
+        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
+                              hist_win, point, dir, power, medium, seq, skip, only, alive, C, wl, __make_integer_seq<IndexList, int, SPEC::N>{});
       } else {
       cf64 pf = sv.prim_f64 + (size_t)prim * 16;
       ci32 pi = sv.prim_i32 + 4 * prim;
@@ -2327,8 +2411,8 @@ __device__ __forceinline__ void trace_body(const TraceParams& P) {
       const bool entering = dot(dir, n) < 0;
       if (entering) n = n * -1.0;
       const int g = pi[1];
-      interact<BVH, STOCH, LEAN, POWER>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
-                                 entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive);
+      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
+                                 entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive, C, wl);
       // outward normal of the solid = n against the travel direction when entering; for a facet of a convex
       // tessellated solid the FACET's own normal decides (the interpolated one of smooth shading can point out of
       // the solid where the ray still runs into it)
@@ -2391,6 +2475,33 @@ __global__ __launch_bounds__(256, BVH ? ODW_WAVES_PER_SIMD_BVH : ODW_WAVES_PER_S
   trace_body<BVH, STOCH, SEG, LEAN, NoSpec, BATCH, POWER, NoSource, ASPH>(P);
 }
 
+#ifndef ODW_SPEC_HEADER       // (the library's own build: a kernel compiled against a scene has no use for these)
+// Spectral launches: the binary tree with a wavelength per ray (CHROMA), deterministic surfaces; SEG x POWER x ASPH.
+// The wavelength tables arrive in a second argument, so TraceParams -- and with it every other instantiation -- stays
+// what it is.
+template <bool SEG, bool POWER, bool ASPH>
+__global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_chroma_kernel(const TraceParams P, const DeviceChroma C) {
+  trace_body<true, false, SEG, false, NoSpec, false, POWER, NoSource, ASPH, true>(P, &C);
+}
+
+// the wavelengths a spectrum gives the rays rays[0 .. n) (odw_ray_wavelengths): the ray loop's own draw
+__global__ __launch_bounds__(256) void odw_ray_wavelengths_kernel(const double* __restrict__ tab, int n_knots, int mode,
+                                                                  const uint64_t* __restrict__ rays, uint64_t n, uint64_t seed,
+                                                                  double* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+    out[i] = spectrum_wavelength(tab, n_knots, mode, rays[i], seed);
+}
+
+// the index of one glass at n wavelengths (odw_dispersion_index, on_device): the ray loop's own evaluation
+struct DispCoefs { double c[ODW_DISP_COEFS]; };
+__global__ __launch_bounds__(256) void odw_disp_index_kernel(int kind, const DispCoefs coef, const double* __restrict__ wl, uint64_t n,
+                                                             double* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = disp_index_dev(kind, coef.c, wl[i]);
+}
+#endif
+
 #ifdef ODW_SPEC_HEADER
 // the scene-compiled flat kernel: ODW_SPEC_HEADER defines `struct Spec` (written by the host library
 // from the uploaded scene, odw_spec.hip: spec_text), ODW_SPEC_LEAN and ODW_SPEC_STOCH
@@ -2418,11 +2529,22 @@ struct SpecTail {
   const double* image;
   double v[N];
 };
+#ifdef ODW_SPEC_CHROMA
+// the variant for spectral launches (the header's Spec has chroma(), disp(G), dc(G)): a wavelength per lane, the
+// wavelength tables in a third argument behind the tail
+extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(
+    const TraceParams P, const SpecTail<Spec::img_fits ? Spec::IMG : 4> T, const DeviceChroma C) {
+  (void)T;
+  static_assert(Spec::chroma(), "ODW_SPEC_CHROMA with a header that is not a spectral one");
+  trace_body<false, false, false, ODW_SPEC_LEAN, Spec, false, ODW_SPEC_POWER, ODW_SPEC_SOURCE, false, true>(P, &C);
+}
+#else
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(
     const TraceParams P, const SpecTail<(Spec::img_fits && !ODW_SPEC_BATCH) ? Spec::IMG : 4> T) {
   (void)T;
   trace_body<false, ODW_SPEC_STOCH, false, ODW_SPEC_LEAN, Spec, ODW_SPEC_BATCH, ODW_SPEC_POWER, ODW_SPEC_SOURCE>(P);
 }
+#endif
 #endif
 
 // sampler only: theta-or-radius and phi per ray (diagnostics / parity tests)

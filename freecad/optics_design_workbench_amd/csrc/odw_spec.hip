@@ -149,7 +149,10 @@ std::string spec_source_text(uint64_t key) {
 
 // `struct Spec` of the uploaded scene (tables of scene_host_tables / compute_boxes).  The text is the
 // cache key: equal text = equal kernel.
-std::string spec_text(const HostScene& hs, int n_samplers) {
+// disp_kind: the header of the variant for spectral launches -- Spec::chroma(), every group's formula as a constexpr
+// Spec::disp(G), where its coefficients lie in the (longer) value image as Spec::dc(G), and ODW_SPEC_CHROMA; part of the
+// text, so part of the cache key.  Null: the text of before, byte for byte.
+std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_kind = nullptr) {
   const int n = hs.n_prims, ng = hs.n_groups;
   std::vector<int> type(n), group(n), flags(n), condw(n), dead(n);
   std::vector<unsigned long long> xf(n);
@@ -164,7 +167,7 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
     xf[p] = xf_pattern(&hs.prim_f64[16 * (size_t)p]);
   }
   // primitives with the same box, and where the kernel finds every value it reads (odw_build.h: the value image)
-  const SpecLayout L = spec_image_layout(hs);
+  const SpecLayout L = spec_image_layout(hs, disp_kind);
   const std::vector<int>&box_of = L.box_of, &box_shared = L.box_shared;
   std::vector<int> gtype(std::max(1, ng)), grec(std::max(1, ng));
   for (int g = 0; g < ng; ++g) { gtype[g] = hs.group_i32[4 * g]; grec[g] = hs.group_i32[4 * g + 1]; }
@@ -195,7 +198,13 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
   s += "  static constexpr bool isolated() { return false; }\n";
   // the value image: its size, whether it travels in the kernel arguments, and the offset of every piece
   s += "  static constexpr int IMG = " + std::to_string(L.size) + ";\n";
-  s += std::string("  static constexpr bool img_fits = ") + (L.fits(sizeof(TraceParams)) ? "true" : "false") + ";\n";
+  s += std::string("  static constexpr bool img_fits = ") + (L.fits(sizeof(TraceParams) + (disp_kind ? sizeof(DeviceChroma) : 0)) ? "true" : "false") + ";\n";
+  if (disp_kind) {
+    std::vector<int> kinds(std::max(1, ng), 0);
+    for (int g = 0; g < ng; ++g) kinds[g] = disp_kind[g];
+    s += "  static constexpr bool chroma() { return true; }\n";
+    s += table("int", "disp", ng, kinds.data(), fi) + table("int", "dc", ng, L.dc.data(), fi);
+  }
   s += "  static constexpr int gf = " + std::to_string(L.gf) + ", gd = " + std::to_string(L.gd) + ", gi = " + std::to_string(L.gi) + ";\n";
   s += table("int", "frame", n, L.frame.data(), fi) + table("int", "par", n, L.par.data(), fi) +
        table("int", "box", n, L.box.data(), fi) + table("int", "der", n, L.der.data(), fi);
@@ -207,6 +216,7 @@ std::string spec_text(const HostScene& hs, int n_samplers) {
   s += std::string("#define ODW_SPEC_LEAN ") + (hs.lean ? "true" : "false") + "\n";
   // stochastic surfaces: the kernel variant with scatter() (the sampler tables themselves are run-time data)
   s += std::string("#define ODW_SPEC_STOCH ") + (n_samplers > 0 ? "true" : "false") + "\n";
+  if (disp_kind) s += "#define ODW_SPEC_CHROMA true\n";
   return s;
 }
 
@@ -362,14 +372,24 @@ void spec_wait_at_exit() {
 // variant kSpecBatch: the kernel's BATCH variant (scenes of one structure side by side, odw_trace_batch) -> ctx->spec_batch_fn;
 // it is bound on the first batch launch, while the single-scene kernel of the same structure is bound (its mode decides).
 // variant kSpecPower: the POWER variant (launches that fill the detector's power plane) -> ctx->spec_power_fn, likewise.
-enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2 };
+// variants kSpecChroma / kSpecChromaPower: the kernel of spectral launches (a wavelength per lane; the context's dispersion
+// is part of its header) without / with the power plane -> ctx->spec_chroma_fn[0 / 1]; bound on the first such launch
+// while the single-scene kernel is bound, under ODW_COMPILE_STRUCTURE only (under ODW_COMPILE_AUTO spectral launches stay
+// on the binary tree).
+enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2, kSpecChroma = 3, kSpecChromaPower = 4 };
 int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   const bool batch = variant != kSpecSingle;      // (a variant rides on the single-scene kernel's bookkeeping)
+  const bool chroma = variant == kSpecChroma || variant == kSpecChromaPower;
   if (variant == kSpecBatch) {
     ctx->spec_batch_fn = nullptr;
   } else if (variant == kSpecPower) {
     ctx->spec_power_fn = nullptr;
+  } else if (chroma) {
+    ctx->spec_chroma_fn[variant == kSpecChromaPower] = nullptr;
+    if (ctx->compile_mode != ODW_COMPILE_STRUCTURE) return ODW_OK;
   } else {
+    ctx->spec_chroma_fn[0] = ctx->spec_chroma_fn[1] = nullptr;
+    ctx->spec_chroma_failed = false;
     ctx->spec_power_fn = nullptr;
     ctx->spec_power_failed = false;
     ctx->spec_power_wait = nullptr;
@@ -391,8 +411,11 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   HIPCHK(ctx, hipGetDeviceProperties(&prop, ctx->device));
   const std::string arch = prop.gcnArchName;
   // (the BATCH variant takes its rays from the batch's buffer, odw_batch_rays_kernel: never compiled against a source)
-  const std::string text = spec_text(ctx->hs, ctx->n_samplers) + (variant == kSpecBatch ? "" : spec_source_text(ctx->spec_source_key)) +
-                           (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n" : variant == kSpecPower ? "#define ODW_SPEC_POWER true\n" : "");
+  if (chroma) ctx->spec_chroma_layout = spec_image_layout(ctx->hs, ctx->disp_kind);
+  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr) +
+                           (variant == kSpecBatch ? "" : spec_source_text(ctx->spec_source_key)) +
+                           (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n"
+                                                  : (variant == kSpecPower || variant == kSpecChromaPower) ? "#define ODW_SPEC_POWER true\n" : "");
   const char* xo = getenv("ODW_SPEC_OPTS");
   const std::string jkey = arch + "|" + (xo ? xo : "") + "|" + text;
   const std::string key = std::to_string(ctx->device) + "|" + jkey;
@@ -473,6 +496,10 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   } else {
     ctx->spec_cache_hit = 1;
   }
+  if (chroma) {
+    ctx->spec_chroma_fn[variant == kSpecChromaPower] = it->second.fn;
+    return ODW_OK;
+  }
   if (batch) {
     (variant == kSpecBatch ? ctx->spec_batch_fn : ctx->spec_power_fn) = it->second.fn;
     return ODW_OK;
@@ -502,14 +529,16 @@ void spec_note_launch(odw_ctx* ctx, uint64_t n_rays) {
 // the host tables and limits in force at this very launch: whatever changed values under the bound structure --
 // another scene of a sweep, other limits -- is in it.  An image too large for the arguments goes to device memory when
 // it differs from the one there; a batch's images lie in its blocks (odw_upload_scene_batch), one per scene.
-int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch) {
-  const SpecLayout& L = ctx->spec_layout;
+// chroma (the variant of spectral launches): the longer image with the groups' dispersion coefficients, and the
+// wavelength tables as a third argument behind the tail.
+int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const DeviceChroma* chroma = nullptr) {
+  const SpecLayout& L = chroma ? ctx->spec_chroma_layout : ctx->spec_layout;
   if (L.n != ctx->hs.n_prims || L.size < kSpecImageLimits) return fail(ctx, ODW_ERR_DEVICE, "compiled kernel without its value image");
   constexpr size_t tail = (sizeof(TraceParams) + 7) & ~(size_t)7;
-  const bool resident = !batch && L.fits(sizeof(TraceParams));
+  const bool resident = !batch && L.fits(sizeof(TraceParams) + (chroma ? sizeof(DeviceChroma) : 0));
   std::vector<double>& img = ctx->spec_image_now;
   img.resize((size_t)L.size);
-  spec_image_build(ctx->hs, ctx->P.lim, L, img.data());
+  spec_image_build(ctx->hs, ctx->P.lim, L, img.data(), chroma ? ctx->disp_coef : nullptr);
   const double* dev = nullptr;
   if (batch) {
     if (!ctx->batch_img_off) return fail(ctx, ODW_ERR_DEVICE, "batch without value images");
@@ -526,10 +555,13 @@ int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch) {
   }
   const size_t nv = resident ? (size_t)L.size : (size_t)kSpecImageLimits;
   std::vector<char>& args = ctx->spec_args;
-  args.assign(tail + sizeof(double*) + nv * sizeof(double), 0);
+  static_assert(sizeof(DeviceChroma) % 8 == 0 && alignof(DeviceChroma) == 8, "DeviceChroma follows the tail without padding");
+  const size_t tail_end = tail + sizeof(double*) + nv * sizeof(double);
+  args.assign(tail_end + (chroma ? sizeof(DeviceChroma) : 0), 0);
   std::memcpy(args.data(), &ctx->P, sizeof(TraceParams));
   std::memcpy(args.data() + tail, &dev, sizeof dev);
   std::memcpy(args.data() + tail + sizeof dev, img.data(), nv * sizeof(double));
+  if (chroma) std::memcpy(args.data() + tail_end, chroma, sizeof(DeviceChroma));
   size_t size = args.size();
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   HIPCHK(ctx, hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, ctx->stream, nullptr, config));

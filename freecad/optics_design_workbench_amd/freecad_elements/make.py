@@ -16,7 +16,17 @@ _GROUP_DEFAULTS = dict(
     PowerThetaDomain='-pi/2, pi/2', PowerPhiDomain='0, 2*pi', RayModificationProbabilityDensity='',
     ModifyThetaDomain='-pi/2, pi/2', ModifyPhiDomain='0, 2*pi', Reflectivity=1.0,
     AbsorptionLength='inf', GratingType='Reflection', GratingLinesPerMillimeter=1000.0,
-    GratingLinesOrientation=np.array([0.0, 0.0, 1.0]), GratingDiffractionOrder=1)
+    GratingLinesOrientation=np.array([0.0, 0.0, 1.0]), GratingDiffractionOrder=1,
+    # dispersive glasses (not in the reference): '' -- RefractiveIndex as it is --, 'Sellmeier' (B1, B2, B3, C1, C2, C3:
+    # n^2 = 1 + sum B_i l^2 / (l^2 - C_i), l in um, C_i in um^2 as catalogues print them) or 'Cauchy' (A, B, C:
+    # n = A + B / l^2 + C / l^4)
+    Dispersion='', DispersionCoefficients=[])
+
+# Fraunhofer lines the Abbe number is defined on (nm)
+LINE_F, LINE_d, LINE_C = 486.1327, 587.5618, 656.2725
+# Schott N-BK7 (Sellmeier; catalogue values)
+N_BK7 = dict(Dispersion='Sellmeier',
+             DispersionCoefficients=[1.03961212, 0.231792344, 1.01046945, 0.00600069867, 0.0200179144, 103.560653])
 
 _RECORD_DEFAULT = dict(Mirror=False, Lens=False, Grating=False, Absorber=True, Vacuum=True)
 
@@ -25,7 +35,10 @@ _SOURCE_DEFAULTS = dict(
     ThetaDomain='0, pi/4', PhiDomain='0, 2*pi', RadiusDomain='0, 10', RandomNumberGeneratorMode='?',
     ThetaResolutionNumericMode='1e5', RadiusResolutionNumericMode='1e5', PhiResolutionNumericMode='1e2',
     Fans=2, FanPhi0='0', RaysPerFan=20, FanModePowerSpan=0.9, RecordRays=False,
-    IgnoredOpticalElements=[], RaysPerIterationScale=1.0, MaxIntersectionsScale=1.0, MaxRayLengthScale=1.0)
+    IgnoredOpticalElements=[], RaysPerIterationScale=1.0, MaxIntersectionsScale=1.0, MaxRayLengthScale=1.0,
+    # polychromatic sources (not in the reference; true-random mode only): spectral lines as (wavelength_nm, weight)
+    # pairs, or a density in `wavelength` (nm) over SpectrumDomain 'lo, hi'; exactly one of the two, neither: Wavelength
+    Spectrum=[], SpectralDensity='', SpectrumDomain='', SpectrumResolution='1e4')
 
 _SETTINGS_DEFAULTS = dict(
     Active=True, EnableStoreSingleShotData=False, EndAfterIterations='inf', EndAfterRays='1e4',
@@ -244,6 +257,21 @@ def makeAsphericLens(doc, name='AsphericLens', front=None, back=None, thickness=
   b = makeAsphere(doc, f'{name}Back', curvature=c2, conicConstant=k2, coefficients=co2, semiDiameter=a2, height=h2,
                   base=(0.0, 0.0, t), quat=(1.0, 0.0, 0.0, 0.0))
   return makeCommon(doc, [f, b], name=name, **pl)
+
+
+def glassFromAbbe(nd, vd):
+  """the group properties (`makeLens(doc, [...], **glassFromAbbe(1.5168, 64.17))`) of the two-term Cauchy glass
+  n = A + B / l^2 (l in um) that has the index nd at the d line (587.5618 nm) and the Abbe number
+  vd = (nd - 1) / (nF - nC), F and C at 486.1327 and 656.2725 nm.  A conversion on the host: the device knows the
+  Cauchy formula it already has.  RefractiveIndex is nd (what a group without dispersion support would use)."""
+  nd, vd = float(nd), float(vd)
+  if not (nd >= 1.0 and vd > 0 and np.isfinite(nd) and np.isfinite(vd)):
+    raise ValueError(f'glassFromAbbe: nd = {nd} must be >= 1 and vd = {vd} positive')
+  lF, ld, lC = LINE_F / 1000.0, LINE_d / 1000.0, LINE_C / 1000.0
+  # nF - nC = B (1 / lF^2 - 1 / lC^2) = (nd - 1) / vd;  A = nd - B / ld^2
+  B = (nd - 1.0) / vd / (1.0 / (lF * lF) - 1.0 / (lC * lC))
+  A = nd - B / (ld * ld)
+  return dict(RefractiveIndex=nd, Dispersion='Cauchy', DispersionCoefficients=[A, B, 0.0])
 
 
 def makeOpticalGroup(doc, opticalType, elements, name=None, placement=None, **props):

@@ -93,6 +93,66 @@ class BakedSource:
   name: str = ''
   label: str = ''
   rays_per_iteration_scale: float = 1.0
+  spectrum: 'BakedSpectrum' = None     # None: every ray has `wavelength`
+
+
+@dataclass
+class BakedSpectrum:
+  """the spectrum of a point source as the device samples it (include/odw_trace.h: odw_set_spectrum).
+  mode 'lines': wavelengths ascending, cdf[j] = (w_0 + .. + w_j) / sum w -- a ray takes line
+  numpy.searchsorted(cdf, u, side='right'); mode 'density': the (edges, cdf) of ScalarRandomVariable.tables() --
+  a ray's wavelength is numpy.interp(u, cdf, wavelengths)"""
+  mode: str
+  wavelengths: np.ndarray
+  cdf: np.ndarray
+
+  def wavelengthOf(self, u):
+    """host evaluation of the device's draw for uniforms u (the same arithmetic)"""
+    u = np.asarray(u, dtype=np.float64)
+    if self.mode == 'lines':
+      return self.wavelengths[np.searchsorted(self.cdf, u, side='right')]
+    return np.interp(u, self.cdf, self.wavelengths)
+
+
+def bakeSpectrum(obj):
+  """BakedSpectrum from a source's `Spectrum` (list of (wavelength_nm, weight) pairs: spectral lines) or
+  `SpectralDensity` (an expression in `wavelength` (nm) over `SpectrumDomain` 'lo, hi', `SpectrumResolution` knots,
+  default 1e4); None when neither is set (`Wavelength` applies).  ValueError naming the property when both are set,
+  when the lines are not strictly ascending or not positive, when the weights are negative or sum to 0."""
+  p = obj._props
+  lines = p.get('Spectrum')
+  density = str(p.get('SpectralDensity') or '').strip()
+  has_lines = lines is not None and len(lines) > 0
+  if has_lines and density:
+    raise ValueError(f'{obj.Name}: Spectrum and SpectralDensity are both set: exactly one of the two may be')
+  if has_lines:
+    a = np.asarray(lines, dtype=np.float64)
+    if a.ndim == 1 and len(a) % 2 == 0:       # (a document's float list: wavelength, weight, wavelength, weight, ...)
+      a = a.reshape(-1, 2)
+    if a.ndim != 2 or a.shape[1] != 2:
+      raise ValueError(f'{obj.Name}: Spectrum: a list of (wavelength_nm, weight) pairs')
+    wl, w = a[:, 0], a[:, 1]
+    if not np.all(np.isfinite(a)) or not np.all(wl > 0):
+      raise ValueError(f'{obj.Name}: Spectrum: wavelengths must be finite and > 0')
+    if np.any(np.diff(wl) <= 0):
+      raise ValueError(f'{obj.Name}: Spectrum: wavelengths must be strictly ascending')
+    if np.any(w < 0) or not w.sum() > 0:
+      raise ValueError(f'{obj.Name}: Spectrum: weights must be >= 0 and sum to more than 0')
+    cdf = np.cumsum(w) / w.sum()
+    cdf[-1] = 1.0
+    return BakedSpectrum('lines', np.ascontiguousarray(wl), np.minimum(cdf, 1.0))
+  if density:
+    dom = str(p.get('SpectrumDomain') or '').strip()
+    if not dom:
+      raise ValueError(f'{obj.Name}: SpectralDensity needs SpectrumDomain \'lo, hi\' (nm)')
+    lo, hi = parsedDomain(dom, default='nan, nan')
+    if not (np.isfinite(lo) and np.isfinite(hi) and 0 < lo < hi):
+      raise ValueError(f'{obj.Name}: SpectrumDomain {dom!r}: two wavelengths 0 < lo < hi (nm)')
+    res = float(p.get('SpectrumResolution') or 1e4)
+    srv = distributions.ScalarRandomVariable(density, (lo, hi), variable='wavelength', numericalResolution=res)
+    edges, cdf = srv.tables()
+    return BakedSpectrum('density', np.ascontiguousarray(edges, dtype=np.float64), np.ascontiguousarray(cdf, dtype=np.float64))
+  return None
 
 
 _VRV_CACHE = {}
@@ -124,7 +184,8 @@ def bakeSource(doc, obj):
                      wavelength=float(obj._props.get('Wavelength', 500)), power=1.0,
                      tables=getVrv(obj).tables(), name=obj.Name,
                      label=obj._props.get('Label', obj.Name),
-                     rays_per_iteration_scale=float(obj._props.get('RaysPerIterationScale', 1)))
+                     rays_per_iteration_scale=float(obj._props.get('RaysPerIterationScale', 1)),
+                     spectrum=bakeSpectrum(obj))
 
 
 def makeRay(baked, thetaOrRadius, phi):

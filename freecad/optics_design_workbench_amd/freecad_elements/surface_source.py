@@ -164,6 +164,9 @@ def bakeSurfaceSource(doc, obj):
                 faces.append((fp, f))
   if not faces and not facets:
     raise ValueError(f'surface source {obj.Name} has no ActiveSurfaces selected for emission')
+  for key in ('Spectrum', 'SpectralDensity'):
+    if obj._props.get(key):
+      raise ValueError(f'surface source {obj.Name}: {key}: spectra are for point sources (surface sources carry one Wavelength)')
   cond_off, cond_prim, cond_inside = geometry.condTables(prims)
   srv = distributions.ScalarRandomVariable(
       **point_source.rvArgs(obj, obj.PowerDensity, variableDomain=point_source.parsedDomain(

@@ -206,6 +206,8 @@ class BakedScene:
   tri_normals: np.ndarray = None                         # (n_prims, 9) vertex normals of TRIANGLE primitives, or None
   tri_edges: np.ndarray = None                           # (n_prims,) bits: which facet edges are edges of the face
   prim_coef: np.ndarray = None                           # (n_prims, 8) polynomial coefficients of ASPHERE primitives, or None: no asphere
+  group_disp_kind: np.ndarray = None                     # (G,) int32 dispersion of each group: 0 constant (group_ior), 1 Sellmeier, 2 Cauchy
+  group_disp: np.ndarray = None                          # (G, 6) float64 its coefficients (Sellmeier B1 B2 B3 C1 C2 C3 / Cauchy A B C 0 0 0)
 
   @property
   def n_prims(self):
@@ -266,6 +268,37 @@ def faceEdgeBits(tri, vertices=None):
   _, inv, cnt = np.unique(key, axis=0, return_inverse=True, return_counts=True)
   single = (cnt[inv.ravel()] == 1).reshape(-1, 3)
   return (single[:, 0] * 1 + single[:, 1] * 2 + single[:, 2] * 4).astype(np.int32)
+
+
+DISPERSION_KINDS = {'': 0, 'Sellmeier': 1, 'Cauchy': 2}      # ODW_DISP_*
+DISPERSION_COEFS = {1: 6, 2: 3}                                # numbers each formula takes
+
+
+def groupDispersion(groups, types, gratingTypes):
+  """(group_disp_kind int32 [G], group_disp float64 [G, 6]) from the groups' `Dispersion` ('' / 'Sellmeier' / 'Cauchy') and
+  `DispersionCoefficients` (Sellmeier: B1, B2, B3, C1, C2, C3 with lambda in um and C in um^2; Cauchy: A, B, C).
+  ValueError naming the property: an unknown formula (tabulated n(lambda), temperature or pressure terms and more than
+  three Sellmeier terms are out of scope), a wrong number of coefficients, non-finite ones, a group that is neither a
+  lens nor a transmission grating."""
+  kind = np.zeros(len(groups), dtype=np.int32)
+  coef = np.zeros((len(groups), 6), dtype=np.float64)
+  for gi, g in enumerate(groups):
+    name = g._props.get('Dispersion', '') or ''
+    if name not in DISPERSION_KINDS:
+      raise ValueError(f"{g.Name}: Dispersion {name!r}: '' (constant RefractiveIndex), 'Sellmeier' or 'Cauchy'")
+    k = DISPERSION_KINDS[name]
+    if k == 0:
+      continue
+    c = np.asarray(g._props.get('DispersionCoefficients') or [], dtype=np.float64).reshape(-1)
+    if len(c) != DISPERSION_COEFS[k]:
+      raise ValueError(f'{g.Name}: DispersionCoefficients: {name} takes {DISPERSION_COEFS[k]} numbers, not {len(c)}')
+    if not np.all(np.isfinite(c)):
+      raise ValueError(f'{g.Name}: DispersionCoefficients: non-finite coefficient')
+    if not (types[gi] == OPTICAL_TYPES.index('Lens') or (types[gi] == OPTICAL_TYPES.index('Grating') and gratingTypes[gi] == 1)):
+      raise ValueError(f'{g.Name}: Dispersion on a group that is neither a lens nor a transmission grating')
+    kind[gi] = k
+    coef[gi, :len(c)] = c
+  return kind, coef
 
 
 def bakeScene(doc, source=None, surfaceFamily=None):
@@ -374,8 +407,10 @@ def bakeScene(doc, source=None, surfaceFamily=None):
       if p.kind == geometry.ASPHERE:
         prim_coef[k] = p.params[4:4 + geometry.ASPHERE_COEFS]
 
+  disp_kind, disp = groupDispersion(groups, types, gt)
+
   return BakedScene(
-      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef,
+      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef, group_disp_kind=disp_kind, group_disp=disp,
       prim_type=np.concatenate([np.array([p.kind for p in prims], dtype=np.int32),
                                 np.full(n_tri, geometry.TRIANGLE, dtype=np.int32)]),
       prim_group=np.concatenate([np.array(prim_group, dtype=np.int32), tri_group]),

@@ -105,6 +105,15 @@ def _parse_property(prop, zf):
     return child.attrib['value']
   if tag == 'Path':
     return child.attrib.get('value', '')
+  if tag == 'FloatList':
+    # App::PropertyFloatList (DispersionCoefficients of a group; Spectrum of a point source as wavelength, weight,
+    # wavelength, weight, ...): a member of the zip, a uint32 count and that many float64
+    fname = child.attrib.get('file')
+    if not fname or zf is None or fname not in zf.namelist():
+      return []
+    data = zf.read(fname)
+    (count,) = struct.unpack_from('<I', data, 0)
+    return [float(v) for v in np.frombuffer(data, dtype='<f8', count=count, offset=4)]
   if tag == 'PropertyPlacement':
     a = child.attrib
     return Placement(base=(float(a['Px']), float(a['Py']), float(a['Pz'])),
@@ -191,12 +200,12 @@ _PROXY_PROPERTIES = {
       'OpticalType RefractiveIndex ReflectedProbabilityDensity RefractedProbabilityDensity PowerThetaDomain '
       'PowerPhiDomain RayModificationProbabilityDensity ModifyThetaDomain ModifyPhiDomain Reflectivity '
       'AbsorptionLength GratingType GratingLinesPerMillimeter GratingLinesOrientation GratingDiffractionOrder '
-      'RecordHits').split(),
+      'RecordHits Dispersion DispersionCoefficients').split(),
   ('freecad.optics_design_workbench.freecad_elements.point_source', 'PointSourceProxy'): (
       'PowerDensity Wavelength FocalLength Divergence ThetaDomain PhiDomain RadiusDomain RandomNumberGeneratorMode '
       'ThetaResolutionNumericMode RadiusResolutionNumericMode PhiResolutionNumericMode Fans FanPhi0 RaysPerFan '
       'FanModePowerSpan RecordRays IgnoredOpticalElements RaysPerIterationScale MaxIntersectionsScale '
-      'MaxRayLengthScale').split(),
+      'MaxRayLengthScale Spectrum SpectralDensity SpectrumDomain SpectrumResolution').split(),
   ('freecad.optics_design_workbench.freecad_elements.surface_source', 'SurfaceSourceProxy'): (
       'ActiveSurfaces PowerDensity UVSamplingInitialResolution UVSamplingMaxRelAreaElementChange FanModeRayCount '
       'Wavelength ThetaDomain RandomNumberGeneratorMode ThetaResolutionNumericMode RadiusResolutionNumericMode '
@@ -214,6 +223,12 @@ _PROXY_PROPERTIES = {
 }
 
 
+# properties this project adds to the reference's tables (dispersive glasses, polychromatic sources): documents written
+# by the reference's workbench do not carry them, so they count neither for nor against a proxy in repairProxies --
+# which documents get their proxy back is what it was
+_OPTIONAL_PROPERTIES = frozenset('Dispersion DispersionCoefficients Spectrum SpectralDensity SpectrumDomain SpectrumResolution'.split())
+
+
 def repairProxies(doc):
   """documents saved without proxy information (`Proxy` = null) still carry
   the workbench properties; like the reference's repairAllProxies
@@ -224,6 +239,7 @@ def repairProxies(doc):
     if not obj.Name.startswith('Optical') or obj.ProxyClass:
       continue
     for (module, cls), names in _PROXY_PROPERTIES.items():
+      names = [n for n in names if n not in _OPTIONAL_PROPERTIES]
       present = sum(1 for n in names if n in obj._props)
       if present > 5 and present > len(names) - 3:
         obj._props['Proxy'] = {'module': module, 'class': cls, 'state': {}, 'repaired': True}

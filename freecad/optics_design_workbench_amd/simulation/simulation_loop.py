@@ -154,6 +154,9 @@ def runSimulation(doc, action='true', *, seed=DEFAULT_SEED, device=0, resultsPat
         rpl = min(raysPerLaunch, _RECORD_RAYS_PER_LAUNCH) if record_rays else raysPerLaunch
         # -- what this launch traces: device-generated rays or explicit initial conditions ----
         explicit = None          # (origins, directions, powers or None, wavelengths or None)
+        if getattr(bsrc, 'spectrum', None) is not None and (action in ('fans', 'singlefans') or pseudo):
+          raise ValueError(f'{src.Name}: Spectrum / SpectralDensity: spectra are for the true-random mode of point sources '
+                           f'(fan mode and pseudo-random mode carry one Wavelength)')
         if isinstance(bsrc, replay_source.BakedReplay):
           # replay_source.py:116-166: no fans; true and pseudo modes alike take the next
           # RaysPerIteration rays of the stock; an exhausted stock ends the simulation
@@ -490,9 +493,16 @@ class _DeviceInitialConditions:
   def __contains__(self, key):
     if key in ('initPoint', 'initDirection', 'initPower', 'initWavelength'):
       return True
+    # (a polychromatic source: a row's wavelength is a function of its ray's number in the Philox stream, so
+    #  StoreHitRayIndex stores that number -- Tracer.rayWavelengths(rayIndex, seed) gives the wavelength back; rays of
+    #  every other Monte-Carlo source carry no ray index, as in the reference, where it is fan metadata)
+    if key == 'rayIndex':
+      return getattr(self._src, 'spectrum', None) is not None
     return key in ('initPhi', 'initTheta') and isinstance(self._src, point_source.BakedSource)
 
   def __getitem__(self, key):
+    if key == 'rayIndex' and key in self:
+      return self._first + np.arange(self._n, dtype=np.int64)
     if key in ('initPoint', 'initDirection'):
       if 'rays' not in self._cache:
         self._cache['rays'] = self._tr.generateRays(self._first, self._n, self._seed)
@@ -507,7 +517,12 @@ class _DeviceInitialConditions:
     if key == 'initPower':
       return np.full(self._n, self._src.power)
     if key == 'initWavelength':
-      return np.full(self._n, self._src.wavelength)
+      if getattr(self._src, 'spectrum', None) is None:
+        return np.full(self._n, self._src.wavelength)
+      # a polychromatic source: the wavelength the device drew for each ray (a function of seed and ray index)
+      if 'wavelengths' not in self._cache:
+        self._cache['wavelengths'] = self._tr.rayWavelengths(self._first + np.arange(self._n, dtype=np.uint64), self._seed)
+      return self._cache['wavelengths']
     raise KeyError(key)
 
 

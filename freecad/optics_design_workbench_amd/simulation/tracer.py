@@ -183,6 +183,58 @@ class Tracer:
     arr, n, keep = _native.surface_sampler_descs(getattr(scene, 'surface_samplers', None))
     self._chk(self._lib.odw_upload_surface_samplers(self._ctx, arr, C.c_int32(n)), 'odw_upload_surface_samplers')
     self.scene = scene
+    # (odw_upload_scene has cleared the previous scene's dispersion: what this one carries, if anything)
+    kind = getattr(scene, 'group_disp_kind', None)
+    if kind is not None and np.any(np.asarray(kind) != 0):
+      self.setDispersion(kind, scene.group_disp)
+
+  def setDispersion(self, kind, coef=None):
+    """Dispersion of the uploaded scene's groups (`odw_set_dispersion`): kind [G] (0 constant, 1 Sellmeier, 2 Cauchy),
+    coef [G, 6] (Sellmeier B1 B2 B3 C1 C2 C3 with C in um^2; Cauchy A B C).  None or an empty kind clears it.
+    Monochromatic launches trace the glasses at the launch wavelength (folded into the tables on the host: every
+    kernel, today's speed); spectral launches (setSpectrum, traceRays(wavelengths=)) evaluate them per interaction."""
+    pi = C.POINTER(C.c_int32)
+    pd = C.POINTER(C.c_double)
+    if kind is None or len(kind) == 0:
+      self._chk(self._lib.odw_set_dispersion(self._ctx, C.c_int32(0), None, None), 'odw_set_dispersion')
+      return
+    k = np.ascontiguousarray(kind, dtype=np.int32)
+    c = np.ascontiguousarray(coef, dtype=np.float64).reshape(len(k), _native.DISP_COEFS)
+    self._chk(self._lib.odw_set_dispersion(self._ctx, C.c_int32(len(k)), k.ctypes.data_as(pi), c.ctypes.data_as(pd)),
+              'odw_set_dispersion')
+
+  def setSpectrum(self, spectrum):
+    """Spectrum of the uploaded point source (`odw_set_spectrum`): a `freecad_elements.point_source.BakedSpectrum`
+    (mode 'lines' / 'density', wavelengths, cdf) or None (clears it).  With one bound, trace() is a spectral launch."""
+    pd = C.POINTER(C.c_double)
+    if spectrum is None:
+      self._chk(self._lib.odw_set_spectrum(self._ctx, C.c_int32(0), C.c_int32(0), None, None), 'odw_set_spectrum')
+      return
+    w = np.ascontiguousarray(spectrum.wavelengths, dtype=np.float64)
+    c = np.ascontiguousarray(spectrum.cdf, dtype=np.float64)
+    if w.shape != c.shape or w.ndim != 1:
+      raise ValueError('Spectrum: wavelengths and cdf differ in shape')
+    self._chk(self._lib.odw_set_spectrum(self._ctx, C.c_int32(_native.SPECTRUM_MODES[spectrum.mode]), C.c_int32(len(w)),
+                                         w.ctypes.data_as(pd), c.ctypes.data_as(pd)), 'odw_set_spectrum')
+
+  def rayWavelengths(self, rays, seed):
+    """the wavelengths (nm) the bound spectrum gives the ray indices `rays` under `seed` (`odw_ray_wavelengths`)"""
+    r = np.ascontiguousarray(rays, dtype=np.uint64).reshape(-1)
+    out = np.empty(len(r), np.float64)
+    self._chk(self._lib.odw_ray_wavelengths(self._ctx, C.c_uint64(len(r)), r.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                            C.c_uint64(int(seed)), out.ctypes.data_as(C.POINTER(C.c_double))), 'odw_ray_wavelengths')
+    return out
+
+  def refractiveIndex(self, group, wavelengths, device=False):
+    """index of group `group` of the uploaded scene at `wavelengths` (nm) under the dispersion set
+    (`odw_dispersion_index`); device=True: evaluated by the kernel-side function"""
+    w = np.ascontiguousarray(wavelengths, dtype=np.float64).reshape(-1)
+    out = np.empty(len(w), np.float64)
+    pd = C.POINTER(C.c_double)
+    self._chk(self._lib.odw_dispersion_index(self._ctx, C.c_int32(int(group)), C.c_int32(0), None, C.c_uint64(len(w)),
+                                             w.ctypes.data_as(pd), out.ctypes.data_as(pd), C.c_int32(1 if device else 0)),
+              'odw_dispersion_index')
+    return out
 
   def compileScene(self, mode='structure'):
     """Scene-compiled kernels (odw_compile_scene): 'structure' -- the ray loop compiled against the
@@ -220,7 +272,12 @@ class Tracer:
     f = self._lib.odw_compiled_source_info
     f.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     self._chk(f(self._ctx, C.byref(key)), 'odw_compiled_source_info')
-    return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value), source=int(key.value))
+    # chroma: the same as `mode` for spectral launches -- they run a variant of the compiled kernel of their own, bound by
+    # the first such launch under 'structure' (`odw_compiled_chroma_info`); 0: they walk the binary tree
+    ch = C.c_int32(0)
+    self._chk(self._lib.odw_compiled_chroma_info(self._ctx, C.byref(ch)), 'odw_compiled_chroma_info')
+    return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value), source=int(key.value),
+                chroma=int(ch.value))
 
   def setSurfaceSeed(self, seed):
     """Philox key of the stochastic-surface draws in traceRays launches"""
@@ -239,6 +296,11 @@ class Tracer:
       d, keep = _native.source_desc(source)
       self._chk(self._lib.odw_upload_source(self._ctx, C.byref(d)), 'odw_upload_source')
     self.source = source
+    # (the upload has cleared the previous source's spectrum: what this one carries, if anything)
+    if getattr(source, 'spectrum', None) is not None:
+      if hasattr(source, 'face_prim'):
+        raise ValueError('Spectrum / SpectralDensity: surface sources carry no spectrum')
+      self.setSpectrum(source.spectrum)
 
   def generateRays(self, first, n, seed):
     """initial conditions only (returnInitialConditions, generic_source.py:57): origins, directions"""
@@ -299,13 +361,23 @@ class Tracer:
               'odw_trace')
 
   def traceRays(self, origins, directions, powers=None, first=0, record_hits=True, histogram=True,
-                record_segments=False):
+                record_segments=False, wavelengths=None):
+    """wavelengths: one per ray (nm) -- a spectral launch (`odw_trace_rays_spectral`); None: the launch wavelength"""
     o = np.ascontiguousarray(origins, dtype=np.float64).reshape(-1, 3)
     d = np.ascontiguousarray(directions, dtype=np.float64).reshape(-1, 3)
     if o.shape != d.shape:
       raise ValueError('origins and directions differ in shape')
     p = np.ascontiguousarray(powers, dtype=np.float64) if powers is not None else None
     pd = C.POINTER(C.c_double)
+    if wavelengths is not None:
+      w = np.ascontiguousarray(wavelengths, dtype=np.float64).reshape(-1)
+      if len(w) != len(o):
+        raise ValueError('wavelengths: one per ray')
+      self._chk(self._lib.odw_trace_rays_spectral(
+          self._ctx, C.c_uint64(int(first)), C.c_uint64(len(o)), o.ctypes.data_as(pd), d.ctypes.data_as(pd),
+          p.ctypes.data_as(pd) if p is not None else None, w.ctypes.data_as(pd),
+          C.c_uint32(self._flags(record_hits, histogram, record_segments))), 'odw_trace_rays_spectral')
+      return
     self._chk(self._lib.odw_trace_rays(
         self._ctx, C.c_uint64(int(first)), C.c_uint64(len(o)), o.ctypes.data_as(pd), d.ctypes.data_as(pd),
         p.ctypes.data_as(pd) if p is not None else None,

@@ -459,6 +459,78 @@ int odw_set_surface_seed(odw_ctx* ctx, uint64_t seed);
  * ReplaySourceProxy._generateRays (replay_source.py:155); odw_upload_source
  * resets it to the source's own                                              */
 int odw_set_wavelength(odw_ctx* ctx, double wavelength_nm);
+/* ---- dispersive glasses and polychromatic sources (entry points more, no descriptor changed: still v12) ----
+ * Replaces nothing of the reference, which traces one colour through glasses of one number.
+ * Index of a group as a function of the wavelength; lambda in micrometres (= wavelength_nm / 1000):
+ *   ODW_DISP_SELLMEIER  coef = B1, B2, B3, C1, C2, C3 (C in um^2, as glass catalogues print them):
+ *                       n^2 = 1 + sum B_i lambda^2 / (lambda^2 - C_i)
+ *   ODW_DISP_CAUCHY     coef = A, B, C, 0, 0, 0:  n = A + B / lambda^2 + C / lambda^4
+ *   ODW_DISP_NONE       the constant group_ior
+ * The order of IEEE operations is fixed (csrc/odw_build.h: disp_index); host and device perform the same sequence
+ * without contraction.  Out of scope and refused rather than approximated: temperature and pressure terms, more
+ * than three Sellmeier terms, tabulated n(lambda), wavelength-dependent Reflectivity / AbsorptionLength.          */
+enum { ODW_DISP_NONE = 0, ODW_DISP_SELLMEIER = 1, ODW_DISP_CAUCHY = 2 };
+#define ODW_DISP_COEFS 6
+/* kind [n_groups], coef [n_groups * ODW_DISP_COEFS] for the uploaded scene's groups (n_groups = the scene's).
+ * n_groups = 0 clears it, and so does odw_upload_scene.  ODW_ERR_INVALID: an unknown kind, non-finite
+ * coefficients, a dispersive group that is neither a lens nor a transmission grating.
+ * A MONOCHROMATIC launch (no spectrum bound, no wavelength per ray -- every launch of before) folds
+ * disp_index(kind, coef, the launch wavelength) into the group's index on the host, before the launch, again
+ * whenever wavelength, dispersion or scene have changed: every kernel traces dispersive glass at one wavelength
+ * unchanged.  Batches refuse a dispersion (ODW_ERR_UNSUPPORTED): per-scene dispersion is out of scope.
+ * Before any launch the library checks that every dispersive group's index is finite and >= 1 over the
+ * wavelengths in force (the spectrum's ends, min and max of the explicit array, or the launch wavelength; judged
+ * at 33 evenly spaced wavelengths, the ends included; a Cauchy glass also at the one extremum of its formula,
+ * 1 / lambda^2 = -B / (2 C), which makes the check exact for it) and that no Sellmeier pole sqrt(C_i) lies inside that
+ * range: ODW_ERR_INVALID naming the group.                                                                  */
+int odw_set_dispersion(odw_ctx* ctx, int32_t n_groups, const int32_t* kind, const double* coef);
+/* The spectrum of the uploaded point source.  mode ODW_SPECTRUM_LINES: n_knots spectral lines, wavelength_nm
+ * strictly ascending, cdf[j] = (w_0 + .. + w_j) / sum w, non-decreasing, cdf[n_knots - 1] = 1 (the cdf runs
+ * from an implied 0 before the first line to 1); a ray takes line j = the number of entries cdf[.] <= u.
+ * mode ODW_SPECTRUM_DENSITY: n_knots >= 2 knots of an inverse-CDF table as the library's other tables, cdf from
+ * 0 to 1 non-decreasing; a ray's wavelength is numpy.interp(u, cdf, wavelength_nm) to the bit.
+ * u = u53(c0, c1) of Philox4x32-10 at counter (ray_lo, ray_hi, 0, 6) under the launch's seed: a stream no
+ * other draw uses, the geometric draws of a ray do not move, and a wavelength depends on (seed, ray index) only.
+ * n_knots = 0 clears it; odw_upload_source and odw_upload_surface_source clear it.  ODW_ERR_INVALID:
+ * wavelengths <= 0 or not ascending, a cdf that does not run to 1 monotonically.
+ * With a spectrum bound odw_trace is a SPECTRAL launch (below).  Surface sources, fan and pseudo-random modes
+ * have no spectrum.                                                                                          */
+enum { ODW_SPECTRUM_LINES = 1, ODW_SPECTRUM_DENSITY = 2 };
+int odw_set_spectrum(odw_ctx* ctx, int32_t mode, int32_t n_knots, const double* wavelength_nm, const double* cdf);
+/* odw_trace_rays with one wavelength (nm, > 0) per ray: a SPECTRAL launch.  Spectral launches carry the
+ * wavelength per ray; the index of every dispersive group is evaluated per interaction on the device, both
+ * gratings diffract by the ray's wavelength.  They run the compiled kernel's CHROMA variant where one is bound
+ * (odw_compiled_chroma_info), else instantiations of their own of the binary-tree kernel (a flat scene gets a
+ * tree built for them); they never take the flat, grid or mesh kernel.  Same rows on both routes, bit for bit.
+ * ODW_ERR_UNSUPPORTED: scenes with stochastic surfaces, batches, surface sources.                            */
+int odw_trace_rays_spectral(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, const double* origins,
+                            const double* directions, const double* powers, const double* wavelengths,
+                            uint32_t flags);
+/* the wavelengths the bound spectrum gives the ray indices rays[0 .. n) under `seed`: a small kernel that calls
+ * the device function the ray loop calls                                                                    */
+int odw_ray_wavelengths(odw_ctx* ctx, uint64_t n, const uint64_t* rays, uint64_t seed, double* out);
+/* out[i] = index at wavelength_nm[i].  ctx != NULL: of group `group` of the context's dispersion (a group of
+ * kind 0: its constant), kind / coef ignored.  ctx == NULL (on_device must be 0): of the glass (kind, coef) --
+ * no device, no context.  on_device != 0: evaluated by a one-line kernel.                                     */
+int odw_dispersion_index(odw_ctx* ctx, int32_t group, int32_t kind, const double* coef, uint64_t n,
+                         const double* wavelength_nm, double* out, int32_t on_device);
+/* bound = the compile mode if the next spectral launch without segment rows runs the compiled kernel's CHROMA
+ * variant (its header carries Spec::chroma(), a constexpr Spec::disp(G) per group and the place Spec::dc(G) of
+ * the group's six coefficients in the value image, so the dispersion's kinds are part of the cache key; bound by
+ * the first spectral launch under ODW_COMPILE_STRUCTURE, with / without the power plane), 0 if it walks the
+ * binary tree (ODW_COMPILE_OFF / AUTO, segment rows, a scene outside the compiled kernels' domain).           */
+int odw_compiled_chroma_info(odw_ctx* ctx, int32_t* bound);
+/* test support, no device needed: odw_compile_check_source for the CHROMA variant under the dispersion kinds
+ * disp_kind [n_groups]                                                                                       */
+int odw_compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limits, const char* arch,
+                             const odw_source_desc* source, const int32_t* disp_kind, char* header_out,
+                             uint64_t header_capacity, uint64_t* code_bytes);
+/* test support, no device needed (they exist so that the CPU suite reaches the validators; not for production
+ * callers): the two validity checks as a launch runs them (odw_set_dispersion's on kind / coef -- the
+ * group types are the context's business --, then the range check over [lo_nm, hi_nm])                       */
+int odw_dispersion_check(int32_t n_groups, const int32_t* kind, const double* coef, double lo_nm, double hi_nm);
+/* no device needed: odw_set_spectrum's validation of a table                                                 */
+int odw_spectrum_check(int32_t mode, int32_t n_knots, const double* wavelength_nm, const double* cdf);
 int odw_set_limits(odw_ctx* ctx, const odw_limits* limits);
 int odw_set_detector(odw_ctx* ctx, const odw_detector_desc* det);
 /* capacity of the device hit list in rows (0 frees it)                     */
