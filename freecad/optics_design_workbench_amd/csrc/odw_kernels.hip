@@ -1276,20 +1276,44 @@ __device__ __forceinline__ bool ray_box(P bx, d3 oi, d3 inv, double tmax) {
   return hi >= fmax(lo, 0.0) && lo < tmax;
 }
 
-// The same screen on a box of the value image (compiled kernels): bx = centre xyz, half extent xyz, the half extent
+// The same screen on a box of the value image (compiled kernels): b = centre xyz, half extent xyz, the half extent
 // rounded outward by the host (odw_build.h: spec_image_build).  With a = c inv - o inv the planes of an axis lie at
 // a -+ h |inv|, nearer first whatever the sign of inv: three fma per axis, no min / max to order the pair (the
 // absolute value and the negation are source modifiers).  A zero direction component: inv is NaN, so is every
 // distance of that axis, and it drops out of fmin / fmax as above.
-template <class P>
-__device__ __forceinline__ bool ray_box_centred(P bx, d3 oi, d3 inv, double tmax) {
-  double a = fma(bx[0], inv.x, -oi.x), w = fabs(inv.x);
-  double lo = fma(-bx[3], w, a), hi = fma(bx[3], w, a);
-  a = fma(bx[1], inv.y, -oi.y); w = fabs(inv.y);
-  lo = fmax(lo, fma(-bx[4], w, a)); hi = fmin(hi, fma(bx[4], w, a));
-  a = fma(bx[2], inv.z, -oi.z); w = fabs(inv.z);
-  lo = fmax(lo, fma(-bx[5], w, a)); hi = fmin(hi, fma(bx[5], w, a));
+// The six words travel BY VALUE (SpecBox): a compiled kernel asks for a primitive's block one primitive ahead of the
+// screen that reads it (spec_prim), so that the scalar load's latency runs under the previous primitive's code.
+struct SpecBox { double cx, cy, cz, hx, hy, hz; };
+__device__ __forceinline__ bool ray_box_centred(SpecBox b, d3 oi, d3 inv, double tmax) {
+  double a = fma(b.cx, inv.x, -oi.x), w = fabs(inv.x);
+  double lo = fma(-b.hx, w, a), hi = fma(b.hx, w, a);
+  a = fma(b.cy, inv.y, -oi.y); w = fabs(inv.y);
+  lo = fmax(lo, fma(-b.hy, w, a)); hi = fmin(hi, fma(b.hy, w, a));
+  a = fma(b.cz, inv.z, -oi.z); w = fabs(inv.z);
+  lo = fmax(lo, fma(-b.hz, w, a)); hi = fmin(hi, fma(b.hz, w, a));
   return hi >= fmax(lo, 0.0) && lo < tmax;
+}
+// does primitive PI of a compiled scene leave code at all (spec_prim), and does that code screen a box of its own
+template <class SPEC>
+constexpr bool spec_live(int pi) { return !SPEC::dead(pi) && (SPEC::seq() || ((SPEC::umask() >> SPEC::group(pi)) & 1) != 0); }
+template <class SPEC>
+constexpr bool spec_own_box(int pi) { return spec_live<SPEC>(pi) && SPEC::box_of(pi) == pi; }
+// the first primitive from `from` on whose code screens a box of its own (-1: none)
+template <class SPEC>
+constexpr int spec_next_box(int from) {
+  for (int p = from; p < SPEC::N; ++p)
+    if (spec_own_box<SPEC>(p)) return p;
+  return -1;
+}
+// the box block of primitive PI.  The offset is checked here, once for every block a kernel asks for: Spec::box() is
+// -1 for a primitive without a box of its own, and the image may lie in device memory, where a read past its end is
+// a read past an allocation.
+template <class SPEC, int PI>
+__device__ __forceinline__ SpecBox spec_box(const SceneView& sv) {
+  static_assert(PI >= 0 && PI < SPEC::N, "box block of a primitive the scene does not have");
+  static_assert(SPEC::box(PI) >= 0 && SPEC::box(PI) <= SPEC::IMG - 6, "box block outside the value image");
+  cf64 bx = sv.img + SPEC::box(PI);
+  return SpecBox{bx[0], bx[1], bx[2], bx[3], bx[4], bx[5]};
 }
 
 // findNearestIntersection (ray.py:290-452).  Returns prim (<0: none).
@@ -1305,11 +1329,19 @@ __device__ __forceinline__ bool ray_box_centred(P bx, d3 oi, d3 inv, double tmax
 // with a cut at least as wide: conservative).
 template <class SPEC, int PI>
 __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid, int only_solid,
-                                          uint64_t mask, bool* boxhit) {
+                                          uint64_t mask, bool* boxhit, SpecBox& pending) {
   constexpr int flags = SPEC::flags(PI);
   // relevant groups: a constant without sequential mode (ignored groups' primitives leave no code),
   // the ray's own mask with it
-  if constexpr (!SPEC::dead(PI) && (SPEC::seq() || ((SPEC::umask() >> SPEC::group(PI)) & 1) != 0)) {
+  if constexpr (spec_live<SPEC>(PI)) {
+    // `pending` holds the block of the next primitive that screens a box of its own: this one's, if it has one.  It
+    // takes the block and asks for the one after it here, in the block that dominates its screen and its exact test,
+    // ahead of both: the load waits behind this primitive's code, not in front of the next one's screen.  A primitive
+    // that shares an earlier one's box passes the pending block on.  (The exact test's own operands stay where they
+    // are read, inside its branch: asked for ahead of the screen they have to be waited for before its verdict, on
+    // every segment, and that cost more than it hid -- profiles/r08/README.md.)
+    [[maybe_unused]] const SpecBox own = pending;
+    if constexpr (SPEC::box_of(PI) == PI && spec_next_box<SPEC>(PI + 1) >= 0) pending = spec_box<SPEC, spec_next_box<SPEC>(PI + 1)>(sv);
     // (only_solid: the isolated solid the ray has just entered, ODW_FLAG_ISOLATED -- a scene without such solids
     //  never sets it, and the test folds away)
     if ((!SPEC::seq() || ((mask >> SPEC::group(PI)) & 1)) && (flags >> ODW_SOLID_SHIFT) != skip_solid &&
@@ -1319,9 +1351,9 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
         in_box = boxhit[SPEC::box_of(PI)];
       } else {
         const double cut = q.cut;
-        in_box = ray_box_centred(sv.img + SPEC::box(PI), oi, inv, cut);
+        in_box = ray_box_centred(own, oi, inv, cut);
 #if ODW_DOUBLE == 1
-        in_box = in_box & ray_box_centred(sv.img + SPEC::box(PI), mk(opq(oi.x), oi.y, oi.z), inv, cut);
+        in_box = in_box & ray_box_centred(own, mk(opq(oi.x), oi.y, oi.z), inv, cut);
 #endif
       }
       boxhit[PI] = in_box;
@@ -1339,7 +1371,7 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
     } else if constexpr (SPEC::box_of(PI) == PI) {
       // (skipped for this lane -- not relevant, or the convex solid just left --, but a later primitive may
       //  ask for this box: its own test then)
-      boxhit[PI] = SPEC::box_shared(PI) ? ray_box_centred(sv.img + SPEC::box(PI), oi, inv, q.cut) : false;
+      boxhit[PI] = SPEC::box_shared(PI) ? ray_box_centred(own, oi, inv, q.cut) : false;
     }
   }
 }
@@ -1348,7 +1380,11 @@ template <class SPEC, int... PI>
 __device__ __forceinline__ void spec_prims(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid, int only_solid,
                                            uint64_t mask, IndexList<int, PI...>) {
   bool boxhit[sizeof...(PI)] = {};
-  (spec_prim<SPEC, PI>(sv, q, oi, inv, skip_solid, only_solid, mask, boxhit), ...);
+  // the first block; every spec_prim that uses one asks for the next (from sv.img as it stands at this segment: a
+  // batch's image moves with the hand-out unit's scene)
+  SpecBox pending = {};
+  if constexpr (spec_next_box<SPEC>(0) >= 0) pending = spec_box<SPEC, spec_next_box<SPEC>(0)>(sv);
+  (spec_prim<SPEC, PI>(sv, q, oi, inv, skip_solid, only_solid, mask, boxhit, pending), ...);
 }
 
 template <bool BVH, class SPEC = NoSpec, bool ASPH = false>
