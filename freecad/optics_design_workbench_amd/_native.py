@@ -51,7 +51,8 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_batch_reserve', 'odw_batch_hits_begin', 'odw_batch_hits_sampled', 'odw_batch_hits_measure', 'odw_batch_hits_measured',
            'odw_enable_power_histogram', 'odw_fetch_power_histogram', 'odw_device_power_histogram', 'odw_hits_bin_power', 'odw_compiled_power_info',
            'odw_set_dispersion', 'odw_set_spectrum', 'odw_trace_rays_spectral', 'odw_ray_wavelengths', 'odw_dispersion_index',
-           'odw_dispersion_check', 'odw_spectrum_check', 'odw_compiled_chroma_info', 'odw_compile_check_chroma']
+           'odw_dispersion_check', 'odw_spectrum_check', 'odw_compiled_chroma_info', 'odw_compile_check_chroma',
+           'odw_set_fresnel', 'odw_compiled_fresnel_info', 'odw_fresnel_reflectance', 'odw_compile_check_fresnel', 'odw_fresnel_check']
 
 # dispersion of a group (ODW_DISP_*) and spectrum of a point source (ODW_SPECTRUM_*)
 DISP_NONE, DISP_SELLMEIER, DISP_CAUCHY = 0, 1, 2
@@ -59,6 +60,10 @@ DISP_KINDS = {'': 0, None: 0, 'Sellmeier': 1, 'Cauchy': 2}
 DISP_COEFS = 6                            # ODW_DISP_COEFS
 SPECTRUM_MODES = {'lines': 1, 'density': 2}
 STREAM_WAVELENGTH = 6                     # ODW_STREAM_WAVELENGTH: word 3 of the Philox counter of the wavelength draw
+# Fresnel mode of a lens group (ODW_FRESNEL_*)
+FRESNEL_NONE, FRESNEL_LOSS, FRESNEL_SPLIT = 0, 1, 2
+FRESNEL_MODES = {'': 0, None: 0, 'Loss': 1, 'Split': 2}
+STREAM_FRESNEL = 7                        # ODW_STREAM_FRESNEL: word 3 of the Philox counter of the reflect-or-transmit draw
 
 _pd = C.POINTER(C.c_double)
 _pi = C.POINTER(C.c_int32)
@@ -295,6 +300,48 @@ def compile_check_chroma(scene, limits, arch=None, source=None):
          kinds.ctypes.data_as(_pi), buf, len(buf), C.byref(size))
   check(None, rc, 'odw_compile_check_chroma')
   return buf.value.decode(), int(size.value)
+
+
+def compile_check_fresnel(scene, limits, arch=None, source=None, modes=None):
+  """Host only (no GPU): header and code size of the compiled kernel's FRESNEL variant for `scene` under `modes`
+  (default: its group_fresnel) (`odw_compile_check_fresnel`); all modes 0: the plain header"""
+  d, keep = scene_desc(scene)
+  lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
+                   float(limits.power_tol))
+  m = _arr(scene.group_fresnel if modes is None else modes, np.int32).reshape(-1)
+  if len(m) != scene.n_groups:          # (the entry point reads one mode per group of the scene)
+    raise ValueError(f'compile_check_fresnel: {len(m)} modes for a scene of {scene.n_groups} groups')
+  buf = C.create_string_buffer(1 << 20)
+  size = C.c_uint64(0)
+  f = lib().odw_compile_check_fresnel
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), C.c_char_p, C.POINTER(SourceDesc), _pi, C.c_char_p, C.c_uint64,
+                C.POINTER(C.c_uint64)]
+  sd, keep_source = source_desc(source) if source is not None else (None, None)
+  rc = f(C.byref(d), C.byref(lim), arch.encode() if arch else None, C.byref(sd) if sd is not None else None,
+         m.ctypes.data_as(_pi), buf, len(buf), C.byref(size))
+  check(None, rc, 'odw_compile_check_fresnel')
+  return buf.value.decode(), int(size.value)
+
+
+def fresnel_reflectance(n1, n2, cos_i):
+  """Host only (no GPU): the unpolarised reflectance of a surface from index n1 to n2 at the cosines of incidence
+  `cos_i` -- the library's fresnel_reflectance (`odw_fresnel_reflectance` without a context); 1 beyond the critical angle"""
+  c = _arr(cos_i, np.float64).reshape(-1)
+  out = np.empty(len(c), np.float64)
+  f = lib().odw_fresnel_reflectance
+  f.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint64, _pd, _pd, C.c_int32]
+  check(None, f(None, float(n1), float(n2), len(c), c.ctypes.data_as(_pd), out.ctypes.data_as(_pd), 0), 'odw_fresnel_reflectance')
+  return out
+
+
+def fresnel_check(modes, group_types=None):
+  """Host only (no GPU): `odw_set_fresnel`'s validation of `modes` (with the groups' ODW_OPT_* types where given);
+  raises NativeError naming the group"""
+  m = _arr(modes, np.int32).reshape(-1)
+  t = _arr(group_types, np.int32).reshape(-1) if group_types is not None else None
+  f = lib().odw_fresnel_check
+  f.argtypes = [C.c_int32, _pi, _pi]
+  check(None, f(len(m), m.ctypes.data_as(_pi), t.ctypes.data_as(_pi) if t is not None else None), 'odw_fresnel_check')
 
 
 def compile_check(scene, limits, mode='structure', arch=None, source=None):

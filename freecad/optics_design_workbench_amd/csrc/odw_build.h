@@ -244,6 +244,44 @@ inline void spectrum_table(int n, const double* wl, const double* cdf, std::vect
   append_slopes(tab, 1, (size_t)n);
 }
 
+// ---- Fresnel reflection at lens surfaces ---------------------------------------------------------
+// The unpolarised reflectance of a surface between the indices n1 (the side the ray comes from) and n2, cos_i the cosine
+// of the angle of incidence and cos_t that of the refracted ray (snells_law: sqrt(root)).  The device twin
+// (odw_kernels.hip: fresnel_reflectance_dev) writes the same expressions.
+inline double fresnel_reflectance(double n1, double n2, double cos_i, double cos_t) {
+  const double a = n1 * cos_i, b = n2 * cos_t, c = n2 * cos_i, e = n1 * cos_t;
+  const double rs = (a - b) / (a + b), rp = (c - e) / (c + e);
+  return 0.5 * (rs * rs + rp * rp);
+}
+// ... from the incidence alone, with mu and root as snells_law writes them; 1 under total internal reflection
+inline double fresnel_reflectance(double n1, double n2, double cos_i) {
+  const double mu = n1 / n2;
+  const double root = 1.0 - mu * mu * (1.0 - cos_i * cos_i);
+  if (root < 0) return 1.0;
+  return fresnel_reflectance(n1, n2, cos_i, std::sqrt(root));
+}
+
+// odw_set_fresnel's check of the modes; group_i32 (may be null: no scene at hand) adds the groups' types
+inline int fresnel_validate(int n_groups, const int32_t* mode, const int32_t* group_i32, std::string& err) {
+  if (n_groups < 0 || n_groups > ODW_MAX_GROUPS || (n_groups && !mode))
+    return refuse(err, ODW_ERR_INVALID, "odw_set_fresnel: bad argument");
+  for (int g = 0; g < n_groups; ++g) {
+    if (mode[g] == ODW_FRESNEL_NONE) continue;
+    char buf[160];
+    if (mode[g] != ODW_FRESNEL_LOSS && mode[g] != ODW_FRESNEL_SPLIT) {
+      std::snprintf(buf, sizeof buf, "odw_set_fresnel: group %d: unknown Fresnel mode %d", g, (int)mode[g]);
+      err = buf;
+      return ODW_ERR_INVALID;
+    }
+    if (group_i32 && group_i32[4 * g] != ODW_OPT_LENS) {
+      std::snprintf(buf, sizeof buf, "odw_set_fresnel: group %d: a Fresnel mode on a group that is not a lens", g);
+      err = buf;
+      return ODW_ERR_INVALID;
+    }
+  }
+  return ODW_OK;
+}
+
 // host half of odw_upload_scene: validation and the host copies of every table.  hs is complete only where the
 // answer is ODW_OK
 int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) {

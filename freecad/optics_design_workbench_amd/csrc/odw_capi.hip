@@ -210,6 +210,12 @@ struct odw_ctx {
   SpecLayout spec_chroma_layout;           // ... and their value image (the plain one + the dispersion coefficients)
   DevBuf chroma_nodes, chroma_prims;       // the binary tree spectral launches walk in a scene that has none of its own
   int chroma_n_nodes = 0;                  // 0: to be built
+  // Fresnel modes of the scene's groups (odw_set_fresnel); launches with one set walk the same tree where the scene has none
+  bool fresnel_on = false, fresnel_split = false;
+  int32_t fresnel_mode[ODW_MAX_GROUPS] = {};
+  DevBuf d_fresnel_mode, fr_in, fr_out;
+  hipFunction_t spec_fresnel_fn[2] = {nullptr, nullptr};  // the compiled kernel's variants for such launches: without / with the power plane
+  bool spec_fresnel_failed = false;        // ... could not be built for this binding: they walk the tree
 
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -509,8 +515,9 @@ int upload_dispersion(odw_ctx* ctx) {
   return upload(ctx, ctx->d_disp_coef, ctx->disp_coef, sizeof ctx->disp_coef);
 }
 
-// Spectral launches walk the binary tree.  A scene the flat loop takes has none: one is built for them, kept beside the
-// scene's own structures (which stay what they are: the monochromatic launches of the same scene keep their kernel).
+// Spectral launches, and launches with a Fresnel mode set, walk the binary tree.  A scene the flat loop takes has none: one
+// is built for them (one tree for both), kept beside the scene's own structures (which stay what they are: the plain
+// launches of the same scene keep their kernel).
 int chroma_tree(odw_ctx* ctx) {
   if (ctx->chroma_n_nodes) return ODW_OK;
   std::vector<Box> boxes;
@@ -565,6 +572,13 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   } else {
     const int rc = fold_dispersion(ctx);
     if (rc) return rc;
+  }
+  const bool fresnel = ctx->fresnel_on;
+  if (fresnel) {
+    if (ctx->batch_launch) return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: a batch with a Fresnel mode set (per-scene Fresnel modes are out of scope)");
+    if (ctx->n_samplers > 0) return fail(ctx, ODW_ERR_UNSUPPORTED, "Fresnel launch: scenes with stochastic surfaces are not supported");
+    if (ctx->fresnel_split && ctx->hs.seq_enabled)
+      return fail(ctx, ODW_ERR_UNSUPPORTED, "Fresnel launch: 'Split' in a scene with a tracing sequence is not supported (a ghost has no place in the sequence)");
   }
   ctx->ph_valid = false;           // the hit list is about to change
   if (!ctx->batch_launch) {
@@ -675,7 +689,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // while the single-scene kernel is bound, ODW_COMPILE_STRUCTURE only; one attempt per binding, and a variant that cannot
   // be built does not become the error of a launch that succeeds on the tree
   const bool segments = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0;
-  if (spectral && !segments && ctx->spec_fn && !ctx->spec_chroma_fn[pw] && !ctx->spec_chroma_failed) {
+  if (spectral && !fresnel && !segments && ctx->spec_fn && !ctx->spec_chroma_fn[pw] && !ctx->spec_chroma_failed) {
     const std::string keep_err = ctx->err;
     if (spec_bind(ctx, pw ? kSpecChromaPower : kSpecChroma) != ODW_OK) {
       ctx->spec_chroma_fn[pw] = nullptr;
@@ -683,13 +697,34 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       ctx->err = keep_err;
     }
   }
+  // The compiled kernel's FRESNEL variant (its header carries the context's modes): likewise, on the first monochromatic
+  // launch with a mode set
+  if (fresnel && !spectral && !segments && ctx->spec_fn && !ctx->spec_fresnel_fn[pw] && !ctx->spec_fresnel_failed) {
+    const std::string keep_err = ctx->err;
+    if (spec_bind(ctx, pw ? kSpecFresnelPower : kSpecFresnel) != ODW_OK) {
+      ctx->spec_fresnel_fn[pw] = nullptr;
+      ctx->spec_fresnel_failed = true;
+      ctx->err = keep_err;
+    }
+  }
   // (after the bindings above: they decide `compiled`.)  A spectral launch goes to the compiled kernel when its CHROMA
   // variant is bound for the scene as it is, else to the binary tree -- never to the flat, grid or mesh kernel, which know
   // no wavelength per ray
-  const bool chroma_compiled = spectral && !segments && ctx->spec_fn && ctx->spec_chroma_fn[pw] && ctx->spec_lean == ctx->hs.lean;
-  const TraceKernel kernel = spectral ? (chroma_compiled ? TraceKernel::compiled : TraceKernel::tree) : choose_kernel(ctx, flags, batch);
+  const bool chroma_compiled = spectral && !fresnel && !segments && ctx->spec_fn && ctx->spec_chroma_fn[pw] && ctx->spec_lean == ctx->hs.lean;
+  // A launch with a Fresnel mode set: the compiled kernel's FRESNEL variant where it is bound for the scene as it is and the
+  // launch is monochromatic, else the binary tree (spectral + Fresnel: always) -- never the flat, grid or mesh kernel
+  const bool fresnel_compiled = fresnel && !spectral && !segments && ctx->spec_fn && ctx->spec_fresnel_fn[pw] && ctx->spec_lean == ctx->hs.lean;
+  const TraceKernel kernel = fresnel ? (fresnel_compiled ? TraceKernel::compiled : TraceKernel::tree)
+                             : spectral ? (chroma_compiled ? TraceKernel::compiled : TraceKernel::tree) : choose_kernel(ctx, flags, batch);
   DeviceChroma chroma;
   std::memset(&chroma, 0, sizeof chroma);
+  DeviceFresnel fresnel_arg;
+  fresnel_arg.mode = (const int32_t*)ctx->d_fresnel_mode.p;
+  if (fresnel && !fresnel_compiled) {
+    int rc;
+    if (!fresnel_arg.mode) return fail(ctx, ODW_ERR_DEVICE, "Fresnel launch without its mode table");
+    if (!P.scene.n_nodes && (rc = chroma_tree(ctx))) return rc;
+  }
   TraceParams Pc;                          // the spectral launch's arguments: P, with the tree built for it where the scene has none
   if (spectral) {
     int rc;
@@ -790,7 +825,25 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     int rc = presort_rays(ctx, first, n, seed);       // (inside the timed window: part of the launch's cost)
     if (rc) return rc;
   }
-  if (chroma_compiled) {
+  if (fresnel_compiled) {
+    int rc = spec_launch(ctx, grid, ctx->spec_fresnel_fn[pw], false);
+    if (rc) return rc;
+  } else if (fresnel) {
+    Pc = P;
+    if (!P.scene.n_nodes) {
+      Pc.scene.bvh_nodes = (const float*)ctx->chroma_nodes.p;
+      Pc.scene.bvh_prims = (const int32_t*)ctx->chroma_prims.p;
+      Pc.scene.n_nodes = ctx->chroma_n_nodes;
+    }
+#define ODW_FRESNEL_LAUNCH(S, W, A, C) hipLaunchKernelGGL((odw_trace_fresnel_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, fresnel_arg)
+#define ODW_FRESNEL_LAUNCH_C(S, W, A) do { if (spectral) ODW_FRESNEL_LAUNCH(S, W, A, true); else ODW_FRESNEL_LAUNCH(S, W, A, false); } while (0)
+#define ODW_FRESNEL_LAUNCH_A(S, W) do { if (asph) ODW_FRESNEL_LAUNCH_C(S, W, true); else ODW_FRESNEL_LAUNCH_C(S, W, false); } while (0)
+    if (segments) { if (pw) ODW_FRESNEL_LAUNCH_A(true, true); else ODW_FRESNEL_LAUNCH_A(true, false); }
+    else { if (pw) ODW_FRESNEL_LAUNCH_A(false, true); else ODW_FRESNEL_LAUNCH_A(false, false); }
+#undef ODW_FRESNEL_LAUNCH_A
+#undef ODW_FRESNEL_LAUNCH_C
+#undef ODW_FRESNEL_LAUNCH
+  } else if (chroma_compiled) {
     int rc = spec_launch(ctx, grid, ctx->spec_chroma_fn[pw], false, &chroma);
     if (rc) return rc;
   } else if (spectral) {
@@ -1022,7 +1075,7 @@ void odw_destroy(odw_ctx* ctx) {
                     &ctx->em_t_tab, &ctx->em_t_guide, &ctx->em_o, &ctx->em_d, &ctx->em_tri_nrm, &ctx->tri_nrm, &ctx->phi_guide, &ctx->asph})
     release(*b);
   for (DevBuf* b : {&ctx->d_disp_kind, &ctx->d_disp_coef, &ctx->spec_tab, &ctx->ray_wl, &ctx->wl_rays, &ctx->wl_out, &ctx->chroma_nodes,
-                    &ctx->chroma_prims})
+                    &ctx->chroma_prims, &ctx->d_fresnel_mode, &ctx->fr_in, &ctx->fr_out})
     release(*b);
   for (auto& sb : ctx->surf_bufs) { release(sb.phi_tab); release(sb.t_tab); release(sb.t_guide); }
   release(ctx->d_samplers);
@@ -1114,6 +1167,101 @@ int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* s) {
     std::memset(ctx->disp_coef, 0, sizeof ctx->disp_coef);
     if (ctx->d_disp_kind.p && (rc = upload_dispersion(ctx))) return rc;
   }
+  // ... and Fresnel modes
+  ctx->fresnel_on = ctx->fresnel_split = false;
+  std::memset(ctx->fresnel_mode, 0, sizeof ctx->fresnel_mode);
+  return ODW_OK;
+}
+
+int odw_set_fresnel(odw_ctx* ctx, int32_t n_groups, const int32_t* mode) {
+  if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_fresnel: null ctx");
+  if (n_groups == 0) {
+    if (!ctx->fresnel_on) return ODW_OK;
+  } else {
+    if (!ctx->have_scene) return fail(ctx, ODW_ERR_NO_SCENE, "odw_set_fresnel before odw_upload_scene");
+    if (n_groups != ctx->hs.n_groups) return fail(ctx, ODW_ERR_INVALID, "odw_set_fresnel: n_groups is not the scene's");
+    std::string err;
+    const int rc = fresnel_validate(n_groups, mode, ctx->hs.group_i32.data(), err);
+    if (rc) return fail(ctx, rc, err);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::memset(ctx->fresnel_mode, 0, sizeof ctx->fresnel_mode);
+  ctx->fresnel_on = ctx->fresnel_split = false;
+  for (int g = 0; g < n_groups; ++g) {
+    ctx->fresnel_mode[g] = mode[g];
+    ctx->fresnel_on |= mode[g] != ODW_FRESNEL_NONE;
+    ctx->fresnel_split |= mode[g] == ODW_FRESNEL_SPLIT;
+  }
+  // (the modes are part of the compiled FRESNEL variant's header: bound again by the next launch that needs it)
+  ctx->spec_fresnel_fn[0] = ctx->spec_fresnel_fn[1] = nullptr;
+  ctx->spec_fresnel_failed = false;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // a running launch may still read the old table
+  return upload(ctx, ctx->d_fresnel_mode, ctx->fresnel_mode, sizeof ctx->fresnel_mode);
+}
+
+int odw_compiled_fresnel_info(odw_ctx* ctx, int32_t* bound) {
+  if (!ctx || !bound) return fail(ctx, ODW_ERR_INVALID, "odw_compiled_fresnel_info: bad argument");
+  *bound = (ctx->fresnel_on && ctx->spec_fn && (ctx->spec_fresnel_fn[0] || ctx->spec_fresnel_fn[1]) && !ctx->spec_dirty && !ctx->bvh_dirty)
+               ? ctx->compile_mode : 0;
+  return ODW_OK;
+}
+
+int odw_fresnel_check(int32_t n_groups, const int32_t* mode, const int32_t* group_type) {
+  std::string err;
+  std::vector<int32_t> gi;
+  if (group_type && n_groups > 0 && n_groups <= ODW_MAX_GROUPS) {
+    gi.assign((size_t)n_groups * 4, 0);
+    for (int g = 0; g < n_groups; ++g) gi[4 * (size_t)g] = group_type[g];
+  }
+  const int rc = fresnel_validate(n_groups, mode, gi.empty() ? nullptr : gi.data(), err);
+  return rc ? fail(nullptr, rc, err) : ODW_OK;
+}
+
+int odw_fresnel_reflectance(odw_ctx* ctx, double n1, double n2, uint64_t n, const double* cos_i, double* R, int32_t device) {
+  if ((n && (!cos_i || !R)) || (!ctx && device) || !(n1 > 0) || !(n2 > 0) || !std::isfinite(n1) || !std::isfinite(n2))
+    return fail(ctx, ODW_ERR_INVALID, "odw_fresnel_reflectance: bad argument");
+  if (!device) {
+    for (uint64_t i = 0; i < n; ++i) R[i] = fresnel_reflectance(n1, n2, cos_i[i]);
+    return ODW_OK;
+  }
+  if (n == 0) return ODW_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  int rc;
+  if ((rc = ensure(ctx, ctx->fr_in, n * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, ctx->fr_out, n * sizeof(double)))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->fr_in.p, cos_i, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->n_cu * 16));
+  hipLaunchKernelGGL(odw_fresnel_kernel, dim3(grid), dim3(256), 0, ctx->stream, n1, n2, (const double*)ctx->fr_in.p, n, (double*)ctx->fr_out.p);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(R, ctx->fr_out.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return ODW_OK;
+}
+
+int odw_compile_check_fresnel(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                              const int32_t* mode, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
+  if (!scene || !limits || !mode) return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check_fresnel: bad argument");
+  HostScene tmp;
+  std::string refusal;
+  int rc = scene_host_tables(scene, tmp, refusal);
+  if (rc) return fail(nullptr, rc, refusal);
+  if ((rc = fresnel_validate(tmp.n_groups, mode, tmp.group_i32.data(), refusal))) return fail(nullptr, rc, refusal);
+  std::vector<Box> boxes;
+  compute_boxes(tmp, limits->dist_tol, boxes);
+  const std::string why = spec_ineligible(tmp);
+  if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_compile_check_fresnel: " + why);
+  const std::string text = spec_text(tmp, 0, nullptr, mode) +
+      (source ? spec_source_text(spec_source_key(source->xform, source->n_t_rows, true, std::isfinite(source->focal_length))) : "");
+  if (header_out && header_capacity) {
+    const size_t k = std::min<size_t>(text.size(), (size_t)header_capacity - 1);
+    std::memcpy(header_out, text.data(), k);
+    header_out[k] = 0;
+  }
+  std::vector<char> code;
+  std::string err;
+  if (!spec_compile(text, arch && *arch ? arch : "gfx950", code, err)) return fail(nullptr, ODW_ERR_DEVICE, err);
+  if (code_bytes) *code_bytes = code.size();
   return ODW_OK;
 }
 
@@ -1910,6 +2058,9 @@ bool same_structure(const HostScene& a, const HostScene& b, std::string& why) {
 int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n_scenes) {
   if (!ctx || !scenes || n_scenes < 1) return fail(ctx, ODW_ERR_INVALID, "odw_upload_scene_batch: bad argument");
   if (!ctx->have_limits) return fail(ctx, ODW_ERR_NO_SCENE, "odw_upload_scene_batch before odw_set_limits (the boxes carry the tolerance)");
+  if (ctx->fresnel_on)
+    return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_upload_scene_batch: a batch with a Fresnel mode set (per-scene Fresnel modes are out of scope; "
+                                          "odw_set_fresnel with n_groups = 0 clears it)");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   ctx->batch_n = 0;
   ctx->batch_traced = 0;

@@ -241,7 +241,10 @@ struct TraceParams {
 // face / acceptance and face coordinates, 5 its angles (odw_emit_kernel).  The wavelength of a ray under a spectrum:
 // u = u53(c0, c1) of counter (ray_lo, ray_hi, 0, ODW_STREAM_WAVELENGTH) under the launch's seed -- a stream of its own,
 // so the geometric draws of a ray are the same with and without a spectrum.
+// 7: the reflect-or-transmit decision of a lens hit under Fresnel 'Split': u = u53(c0, c1) of counter (ray_lo, ray_hi,
+// nint, ODW_STREAM_FRESNEL), nint the ordinal scatter() gets -- a ghost depends on (seed, ray number, ordinal) only.
 #define ODW_STREAM_WAVELENGTH 6u
+#define ODW_STREAM_FRESNEL 7u
 
 // Second kernel argument of the CHROMA instantiations (spectral launches: one wavelength per ray).  The other
 // instantiations never see it: TraceParams is what it was.
@@ -251,6 +254,12 @@ struct DeviceChroma {
   int32_t spec_n, spec_mode;    // knots; ODW_SPECTRUM_LINES / ODW_SPECTRUM_DENSITY
   const int32_t* disp_kind;     // [ODW_MAX_GROUPS] ODW_DISP_* (0: the constant of group_f64)
   const double* disp_coef;      // [ODW_MAX_GROUPS * ODW_DISP_COEFS]
+};
+
+// Kernel argument of the FRESNEL instantiations of the binary tree (launches with a Fresnel mode on some lens group),
+// behind DeviceChroma.  A kernel compiled against the scene carries the modes in its header instead (Spec::fresnel(G)).
+struct DeviceFresnel {
+  const int32_t* mode;          // [ODW_MAX_GROUPS] ODW_FRESNEL_* of every group
 };
 
 }  // namespace odw

@@ -1570,6 +1570,34 @@ __device__ __forceinline__ d3 snells_law(d3 r, double n1, double n2, d3 n, bool&
   return perp * mu + n * fsqrt(root);
 }
 
+// ------------------------------------------- Fresnel reflection (FRESNEL)
+// snells_law for the instantiations that need the reflectance too: the same operations in the same order, and the
+// cosines of incidence (d) and refraction (cos_t; 0 under total reflection) it has computed anyway
+__device__ __forceinline__ d3 snells_law(d3 r, double n1, double n2, d3 n, bool& tir, double& d, double& cos_t) {
+  d = dot(n, r);
+  const double mu = n1 * frcp(n2);
+  const double root = 1.0 - mu * mu * (1.0 - d * d);
+  if (root < 0) { tir = true; cos_t = 0.0; return r - n * (2.0 * d); }
+  tir = false;
+  const d3 perp = r - n * d;
+  cos_t = fsqrt(root);
+  return perp * mu + n * cos_t;
+}
+
+// The unpolarised reflectance: the device twin of fresnel_reflectance (odw_build.h), the same expressions
+__device__ __forceinline__ double fresnel_reflectance_dev(double n1, double n2, double cos_i, double cos_t) {
+  const double a = n1 * cos_i, b = n2 * cos_t, c = n2 * cos_i, e = n1 * cos_t;
+  const double rs = (a - b) / (a + b), rp = (c - e) / (c + e);
+  return 0.5 * (rs * rs + rp * rp);
+}
+
+// the uniform that decides reflect-or-transmit at interaction `ordinal` of ray `ray` under 'Split'
+__device__ __forceinline__ double fresnel_uniform(uint64_t ray, uint64_t seed, uint32_t ordinal) {
+  uint32_t c0 = (uint32_t)ray, c1 = (uint32_t)(ray >> 32), c2 = ordinal, c3 = ODW_STREAM_FRESNEL;
+  philox4x32_10(c0, c1, c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32));
+  return u53(c0, c1);
+}
+
 __device__ __forceinline__ d3 line_grating(d3 ray, double n1, double n2, d3 normal, double wavelength_nm,
                                         int order, double lpm, d3 gdir, bool transmission) {
   const double wl = wavelength_nm / 1000;
@@ -2037,11 +2065,15 @@ __device__ __forceinline__ double group_index(cf64 group_f64, int g, const Devic
 // n: surface normal along the travel direction; cnt: the thread's column of event counters.
 // CHROMA (spectral launches): the ray carries its wavelength wl; the index of the current medium and of the group
 // entered come from the group's formula where it has one (chroma_index), and the gratings diffract by wl.
-template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec, bool CHROMA = false>
+// FRESNEL (launches with a Fresnel mode on some lens group): fmode is the hit group's ODW_FRESNEL_* -- a constant where the
+// scene is compiled in, so a group without a mode keeps the code it has; 'Loss' takes 1 - R off the power, 'Split' reflects
+// the ray with probability R (fresnel_uniform) and leaves medium and sequence as they were.
+template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec, bool CHROMA = false, bool FRESNEL = false>
 __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, ci32 group_i32, cf64 group_gdir, int g,
                                          int gtype, bool record, d3 n, bool entering, uint64_t ray, int nint,
                                          uint32_t* cnt, uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power,
-                                         int& medium, int& seq, bool& alive, const DeviceChroma* C = nullptr, double wl = 0.0) {
+                                         int& medium, int& seq, bool& alive, const DeviceChroma* C = nullptr, double wl = 0.0,
+                                         int fmode = ODW_FRESNEL_NONE) {
   if (record) {
     cnt[ODW_CNT_RECORDED_HITS * 256] += 1u;
     // (block reservations and the histogram window only in the flat kernels: in the BVH kernels
@@ -2065,8 +2097,30 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
   } else if (gtype == ODW_OPT_LENS) {
     const double n1 = (medium >= 0) ? medium_index<SPEC, CHROMA>(group_f64, medium, C, wl) : 1.0;
     double n2 = 1.0;
+    [[maybe_unused]] const int medium_before = medium;
     if (entering) { medium = g; n2 = group_index<SPEC, CHROMA>(group_f64, g, C, wl); }
     bool tir;
+    if constexpr (FRESNEL) {
+      static_assert(!STOCH, "Fresnel launches: deterministic surfaces");
+      // (the ODW_DOUBLE == 7 diagnostic of the plain branch below -- the refraction evaluated a second time behind an
+      //  optimisation barrier -- is not carried over: that build measures the plain kernels, and its figures say nothing
+      //  about a launch with a Fresnel mode set)
+      double d, cos_t;
+      const d3 ideal = snells_law(dir, n1, n2, n, tir, d, cos_t);
+      bool reflected = false;
+      if (fmode != ODW_FRESNEL_NONE && !tir) {
+        const double R = fresnel_reflectance_dev(n1, n2, d, cos_t);
+        if (fmode == ODW_FRESNEL_LOSS) power *= 1.0 - R;      // (the hit is recorded: its row holds the power before the surface)
+        else reflected = fresnel_uniform(ray, P.seed, (uint32_t)nint) < R;
+      }
+      if (reflected) {
+        dir = dir - n * (2.0 * d);         // mirror(dir, n) with the dot product at hand
+        medium = medium_before;            // the ghost stays where the ray was; the sequence does not advance
+      } else {
+        dir = ideal;
+        if (!entering && !tir && medium == g) { medium = -1; ++seq; }
+      }
+    } else {
 #if ODW_DOUBLE == 7
     d3 ideal = snells_law(dir, n1, n2, n, tir);
     { bool tir2; const d3 again = snells_law(mk(opq(dir.x), dir.y, dir.z), n1, n2, n, tir2); ideal = again.x == ideal.x ? ideal : again; tir = tir & tir2; }
@@ -2077,6 +2131,7 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
                              dir, ideal, n, tir ? -1.0 : n1 / n2);
     else dir = ideal;
     if (!entering && !tir && medium == g) { medium = -1; ++seq; }
+    }
   } else if (gtype == ODW_OPT_ABSORBER) {
     power = 0;
     ++seq;
@@ -2110,9 +2165,16 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
   }
 }
 
+// the Fresnel mode of group g in the header of a scene compiled for such launches (Spec::fresnel(G)); none elsewhere
+template <class SPEC, bool FRESNEL>
+constexpr int spec_fresnel(int g) {
+  if constexpr (FRESNEL && SPEC::enabled) return SPEC::fresnel(g);
+  else return ODW_FRESNEL_NONE;
+}
+
 // the hit is on primitive PI of a compiled scene: its type, frame pattern, flags, group and the group's
 // optical type / recording switch are constants
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, int PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, int PI>
 __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                          cf64 group_gdir, int face, uint64_t ray, int nint, uint32_t* cnt,
                                          uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
@@ -2133,8 +2195,10 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
 #endif
   const bool entering = dot(dir, n) < 0;
   if (entering) n = n * -1.0;
-  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
-                               nint, cnt, hit_state, win, point, dir, power, medium, seq, alive, C, wl);
+  // (FRESNEL: the group's mode from the header -- a group without one folds to the code of before)
+  constexpr int fmode = spec_fresnel<SPEC, FRESNEL>(g);
+  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
+                               nint, cnt, hit_state, win, point, dir, power, medium, seq, alive, C, wl, fmode);
   // n points along the incoming travel direction: out of the solid when leaving it, into it when entering
   const double out = entering ? -dot(dir, n) : dot(dir, n);
   if constexpr ((flags & ODW_FLAG_CONVEX) != 0) skip = out > 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
@@ -2142,12 +2206,12 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   if constexpr ((flags & ODW_FLAG_ISOLATED) != 0) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else only = -1;
 }
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, int... PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, int... PI>
 __device__ __forceinline__ void spec_hits(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                           cf64 group_gdir, int prim, int face, uint64_t ray, int nint, uint32_t* cnt,
                                           uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
                                           int& skip, int& only, bool& alive, const DeviceChroma* C, double wl, IndexList<int, PI...>) {
-  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
+  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
                                                   point, dir, power, medium, seq, skip, only, alive, C, wl), true)
                      : false) || ...);
 }
@@ -2212,11 +2276,14 @@ template <> struct HitBlockState<false> {
 // ASPH (binary tree): the instantiations scenes with an asphere are launched with
 // CHROMA (binary tree): spectral launches -- a wavelength per lane, set at every (re)generation of the lane from the
 //   explicit array or the spectrum draw (DeviceChroma), handed to interact()
+// FRESNEL (binary tree, or a kernel compiled for it): launches with a Fresnel mode on some lens group -- the hit group's mode
+//   from DeviceFresnel (tree) or the header (compiled), handed to interact()
 template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false,
-          class SRC = NoSource, bool ASPH = false, bool CHROMA = false>
-__device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChroma* C = nullptr) {
+          class SRC = NoSource, bool ASPH = false, bool CHROMA = false, bool FRESNEL = false>
+__device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChroma* C = nullptr, const DeviceFresnel* F = nullptr) {
   static_assert(!ASPH || BVH, "aspheres: the binary tree (or a compiled kernel, which knows its scene from Spec::rare())");
   static_assert(!CHROMA || ((BVH || SPEC::enabled) && !STOCH && !BATCH), "spectral launches: the binary tree or a kernel compiled for them, no stochastic surfaces, no batches");
+  static_assert(!FRESNEL || ((BVH || SPEC::enabled) && !STOCH && !BATCH), "Fresnel launches: the binary tree or a kernel compiled for them, no stochastic surfaces, no batches");
   static_assert(!BATCH || (!BVH && !SEG), "batch launches: flat kernels, no segment rows");
   extern __shared__ int bvh_stack[];  // ODW_BVH_STACK x 256 ints (BVH variant only)
   // per-thread event counters live in LDS (one column per thread, ds_add_u32
@@ -2427,7 +2494,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
       uint32_t* cnt = cnt_lds + threadIdx.x;
       uint32_t* hit_state = hit_lds + (threadIdx.x >> 6) * 4;
       if constexpr (SPEC::enabled) {
-        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
+        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
                               hist_win, point, dir, power, medium, seq, skip, only, alive, C, wl, __make_integer_seq<IndexList, int, SPEC::N>{});
       } else {
       cf64 pf = sv.prim_f64 + (size_t)prim * 16;
@@ -2447,8 +2514,10 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
       const bool entering = dot(dir, n) < 0;
       if (entering) n = n * -1.0;
       const int g = pi[1];
-      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
-                                 entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive, C, wl);
+      int fmode = ODW_FRESNEL_NONE;
+      if constexpr (FRESNEL) fmode = F->mode[g];
+      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA, FRESNEL>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
+                                 entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive, C, wl, fmode);
       // outward normal of the solid = n against the travel direction when entering; for a facet of a convex
       // tessellated solid the FACET's own normal decides (the interpolated one of smooth shading can point out of
       // the solid where the ray still runs into it)
@@ -2520,6 +2589,28 @@ __global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_chroma_
   trace_body<true, false, SEG, false, NoSpec, false, POWER, NoSource, ASPH, true>(P, &C);
 }
 
+// Launches with a Fresnel mode on some lens group: the binary tree, deterministic surfaces; SEG x POWER x ASPH x CHROMA
+// (spectral launches with Fresnel: the wavelength per lane too).  The modes arrive in an argument of their own behind
+// DeviceChroma (all zero where the launch is monochromatic): TraceParams stays what it is.
+template <bool SEG, bool POWER, bool ASPH, bool CHROMA>
+__global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_fresnel_kernel(const TraceParams P, const DeviceChroma C,
+                                                                                        const DeviceFresnel F) {
+  trace_body<true, false, SEG, false, NoSpec, false, POWER, NoSource, ASPH, CHROMA, true>(P, &C, &F);
+}
+
+// R of a surface n1 -> n2 at n cosines of incidence (odw_fresnel_reflectance, device): the ray loop's own evaluation,
+// mu, root and cos_t as snells_law has them
+__global__ __launch_bounds__(256) void odw_fresnel_kernel(double n1, double n2, const double* __restrict__ cos_i, uint64_t n,
+                                                          double* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const double d = cos_i[i];
+    const double mu = n1 * frcp(n2);
+    const double root = 1.0 - mu * mu * (1.0 - d * d);
+    out[i] = root < 0 ? 1.0 : fresnel_reflectance_dev(n1, n2, d, fsqrt(root));
+  }
+}
+
 // the wavelengths a spectrum gives the rays rays[0 .. n) (odw_ray_wavelengths): the ray loop's own draw
 __global__ __launch_bounds__(256) void odw_ray_wavelengths_kernel(const double* __restrict__ tab, int n_knots, int mode,
                                                                   const uint64_t* __restrict__ rays, uint64_t n, uint64_t seed,
@@ -2573,6 +2664,13 @@ extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kerne
   (void)T;
   static_assert(Spec::chroma(), "ODW_SPEC_CHROMA with a header that is not a spectral one");
   trace_body<false, false, false, ODW_SPEC_LEAN, Spec, false, ODW_SPEC_POWER, ODW_SPEC_SOURCE, false, true>(P, &C);
+}
+#elif defined(ODW_SPEC_FRESNEL)
+// the variant for launches with a Fresnel mode set (the header's Spec has fresnel(G)): the arguments of the plain kernel
+extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(
+    const TraceParams P, const SpecTail<Spec::img_fits ? Spec::IMG : 4> T) {
+  (void)T;
+  trace_body<false, false, false, ODW_SPEC_LEAN, Spec, false, ODW_SPEC_POWER, ODW_SPEC_SOURCE, false, false, true>(P);
 }
 #else
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(

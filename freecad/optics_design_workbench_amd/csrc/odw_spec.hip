@@ -152,7 +152,9 @@ std::string spec_source_text(uint64_t key) {
 // disp_kind: the header of the variant for spectral launches -- Spec::chroma(), every group's formula as a constexpr
 // Spec::disp(G), where its coefficients lie in the (longer) value image as Spec::dc(G), and ODW_SPEC_CHROMA; part of the
 // text, so part of the cache key.  Null: the text of before, byte for byte.
-std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_kind = nullptr) {
+// fresnel: the header of the variant for launches with a Fresnel mode set -- every group's mode as a constexpr
+// Spec::fresnel(G) and ODW_SPEC_FRESNEL; part of the text likewise.  Null, or every mode 0: the text of before, byte for byte.
+std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_kind = nullptr, const int32_t* fresnel = nullptr) {
   const int n = hs.n_prims, ng = hs.n_groups;
   std::vector<int> type(n), group(n), flags(n), condw(n), dead(n);
   std::vector<unsigned long long> xf(n);
@@ -205,6 +207,13 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
     s += "  static constexpr bool chroma() { return true; }\n";
     s += table("int", "disp", ng, kinds.data(), fi) + table("int", "dc", ng, L.dc.data(), fi);
   }
+  bool any_fresnel = false;
+  for (int g = 0; fresnel && g < ng; ++g) any_fresnel |= fresnel[g] != 0;
+  if (any_fresnel) {
+    std::vector<int> modes(std::max(1, ng), 0);
+    for (int g = 0; g < ng; ++g) modes[g] = fresnel[g];
+    s += table("int", "fresnel", ng, modes.data(), fi);
+  }
   s += "  static constexpr int gf = " + std::to_string(L.gf) + ", gd = " + std::to_string(L.gd) + ", gi = " + std::to_string(L.gi) + ";\n";
   s += table("int", "frame", n, L.frame.data(), fi) + table("int", "par", n, L.par.data(), fi) +
        table("int", "box", n, L.box.data(), fi) + table("int", "der", n, L.der.data(), fi);
@@ -217,6 +226,7 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
   // stochastic surfaces: the kernel variant with scatter() (the sampler tables themselves are run-time data)
   s += std::string("#define ODW_SPEC_STOCH ") + (n_samplers > 0 ? "true" : "false") + "\n";
   if (disp_kind) s += "#define ODW_SPEC_CHROMA true\n";
+  if (any_fresnel) s += "#define ODW_SPEC_FRESNEL true\n";
   return s;
 }
 
@@ -376,10 +386,13 @@ void spec_wait_at_exit() {
 // is part of its header) without / with the power plane -> ctx->spec_chroma_fn[0 / 1]; bound on the first such launch
 // while the single-scene kernel is bound, under ODW_COMPILE_STRUCTURE only (under ODW_COMPILE_AUTO spectral launches stay
 // on the binary tree).
-enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2, kSpecChroma = 3, kSpecChromaPower = 4 };
+// variants kSpecFresnel / kSpecFresnelPower: the kernel of launches with a Fresnel mode set (the context's modes are part of
+// its header; arguments and value image are the plain kernel's) -> ctx->spec_fresnel_fn[0 / 1]; bound like the CHROMA ones.
+enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2, kSpecChroma = 3, kSpecChromaPower = 4, kSpecFresnel = 5, kSpecFresnelPower = 6 };
 int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   const bool batch = variant != kSpecSingle;      // (a variant rides on the single-scene kernel's bookkeeping)
   const bool chroma = variant == kSpecChroma || variant == kSpecChromaPower;
+  const bool fresnel = variant == kSpecFresnel || variant == kSpecFresnelPower;
   if (variant == kSpecBatch) {
     ctx->spec_batch_fn = nullptr;
   } else if (variant == kSpecPower) {
@@ -387,7 +400,12 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   } else if (chroma) {
     ctx->spec_chroma_fn[variant == kSpecChromaPower] = nullptr;
     if (ctx->compile_mode != ODW_COMPILE_STRUCTURE) return ODW_OK;
+  } else if (fresnel) {
+    ctx->spec_fresnel_fn[variant == kSpecFresnelPower] = nullptr;
+    if (ctx->compile_mode != ODW_COMPILE_STRUCTURE) return ODW_OK;
   } else {
+    ctx->spec_fresnel_fn[0] = ctx->spec_fresnel_fn[1] = nullptr;
+    ctx->spec_fresnel_failed = false;
     ctx->spec_chroma_fn[0] = ctx->spec_chroma_fn[1] = nullptr;
     ctx->spec_chroma_failed = false;
     ctx->spec_power_fn = nullptr;
@@ -412,10 +430,10 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   const std::string arch = prop.gcnArchName;
   // (the BATCH variant takes its rays from the batch's buffer, odw_batch_rays_kernel: never compiled against a source)
   if (chroma) ctx->spec_chroma_layout = spec_image_layout(ctx->hs, ctx->disp_kind);
-  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr) +
+  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr, fresnel ? ctx->fresnel_mode : nullptr) +
                            (variant == kSpecBatch ? "" : spec_source_text(ctx->spec_source_key)) +
                            (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n"
-                                                  : (variant == kSpecPower || variant == kSpecChromaPower) ? "#define ODW_SPEC_POWER true\n" : "");
+                                                  : (variant == kSpecPower || variant == kSpecChromaPower || variant == kSpecFresnelPower) ? "#define ODW_SPEC_POWER true\n" : "");
   const char* xo = getenv("ODW_SPEC_OPTS");
   const std::string jkey = arch + "|" + (xo ? xo : "") + "|" + text;
   const std::string key = std::to_string(ctx->device) + "|" + jkey;
@@ -498,6 +516,10 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   }
   if (chroma) {
     ctx->spec_chroma_fn[variant == kSpecChromaPower] = it->second.fn;
+    return ODW_OK;
+  }
+  if (fresnel) {
+    ctx->spec_fresnel_fn[variant == kSpecFresnelPower] = it->second.fn;
     return ODW_OK;
   }
   if (batch) {

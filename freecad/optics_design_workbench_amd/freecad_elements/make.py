@@ -20,7 +20,10 @@ _GROUP_DEFAULTS = dict(
     # dispersive glasses (not in the reference): '' -- RefractiveIndex as it is --, 'Sellmeier' (B1, B2, B3, C1, C2, C3:
     # n^2 = 1 + sum B_i l^2 / (l^2 - C_i), l in um, C_i in um^2 as catalogues print them) or 'Cauchy' (A, B, C:
     # n = A + B / l^2 + C / l^4)
-    Dispersion='', DispersionCoefficients=[])
+    Dispersion='', DispersionCoefficients=[],
+    # Fresnel reflection at a lens group's surfaces (not in the reference): '' -- the surface only bends the ray --,
+    # 'Loss' (power *= 1 - R at every crossing) or 'Split' (reflected with probability R: ghost rays)
+    Fresnel='')
 
 # Fraunhofer lines the Abbe number is defined on (nm)
 LINE_F, LINE_d, LINE_C = 486.1327, 587.5618, 656.2725

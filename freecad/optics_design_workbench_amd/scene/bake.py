@@ -208,6 +208,7 @@ class BakedScene:
   prim_coef: np.ndarray = None                           # (n_prims, 8) polynomial coefficients of ASPHERE primitives, or None: no asphere
   group_disp_kind: np.ndarray = None                     # (G,) int32 dispersion of each group: 0 constant (group_ior), 1 Sellmeier, 2 Cauchy
   group_disp: np.ndarray = None                          # (G, 6) float64 its coefficients (Sellmeier B1 B2 B3 C1 C2 C3 / Cauchy A B C 0 0 0)
+  group_fresnel: np.ndarray = None                       # (G,) int32 Fresnel mode of each group: 0 none, 1 'Loss', 2 'Split' (lenses only)
 
   @property
   def n_prims(self):
@@ -299,6 +300,24 @@ def groupDispersion(groups, types, gratingTypes):
     kind[gi] = k
     coef[gi, :len(c)] = c
   return kind, coef
+
+
+FRESNEL_MODES = {'': 0, 'Loss': 1, 'Split': 2}               # ODW_FRESNEL_*
+
+
+def groupFresnel(groups, types):
+  """group_fresnel int32 [G] from the groups' `Fresnel` ('' / 'Loss' / 'Split').  ValueError naming the group: an unknown
+  mode, a mode on a group that is not a lens (mirrors have Reflectivity; absorbers, vacuum groups and both gratings
+  reflect nothing here), 'Split' beside a tracing sequence is refused at the launch."""
+  mode = np.zeros(len(groups), dtype=np.int32)
+  for gi, g in enumerate(groups):
+    name = g._props.get('Fresnel', '') or ''
+    if name not in FRESNEL_MODES:
+      raise ValueError(f"{g.Name}: Fresnel {name!r}: '' (none), 'Loss' or 'Split'")
+    if FRESNEL_MODES[name] and types[gi] != OPTICAL_TYPES.index('Lens'):
+      raise ValueError(f'{g.Name}: Fresnel on a group that is not a lens')
+    mode[gi] = FRESNEL_MODES[name]
+  return mode
 
 
 def bakeScene(doc, source=None, surfaceFamily=None):
@@ -408,9 +427,10 @@ def bakeScene(doc, source=None, surfaceFamily=None):
         prim_coef[k] = p.params[4:4 + geometry.ASPHERE_COEFS]
 
   disp_kind, disp = groupDispersion(groups, types, gt)
+  fresnel = groupFresnel(groups, types)
 
   return BakedScene(
-      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef, group_disp_kind=disp_kind, group_disp=disp,
+      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef, group_disp_kind=disp_kind, group_disp=disp, group_fresnel=fresnel,
       prim_type=np.concatenate([np.array([p.kind for p in prims], dtype=np.int32),
                                 np.full(n_tri, geometry.TRIANGLE, dtype=np.int32)]),
       prim_group=np.concatenate([np.array(prim_group, dtype=np.int32), tri_group]),

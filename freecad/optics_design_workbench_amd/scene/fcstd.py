@@ -200,7 +200,7 @@ _PROXY_PROPERTIES = {
       'OpticalType RefractiveIndex ReflectedProbabilityDensity RefractedProbabilityDensity PowerThetaDomain '
       'PowerPhiDomain RayModificationProbabilityDensity ModifyThetaDomain ModifyPhiDomain Reflectivity '
       'AbsorptionLength GratingType GratingLinesPerMillimeter GratingLinesOrientation GratingDiffractionOrder '
-      'RecordHits Dispersion DispersionCoefficients').split(),
+      'RecordHits Dispersion DispersionCoefficients Fresnel').split(),
   ('freecad.optics_design_workbench.freecad_elements.point_source', 'PointSourceProxy'): (
       'PowerDensity Wavelength FocalLength Divergence ThetaDomain PhiDomain RadiusDomain RandomNumberGeneratorMode '
       'ThetaResolutionNumericMode RadiusResolutionNumericMode PhiResolutionNumericMode Fans FanPhi0 RaysPerFan '
@@ -223,10 +223,10 @@ _PROXY_PROPERTIES = {
 }
 
 
-# properties this project adds to the reference's tables (dispersive glasses, polychromatic sources): documents written
+# properties this project adds to the reference's tables (dispersive glasses, polychromatic sources, Fresnel modes): documents written
 # by the reference's workbench do not carry them, so they count neither for nor against a proxy in repairProxies --
 # which documents get their proxy back is what it was
-_OPTIONAL_PROPERTIES = frozenset('Dispersion DispersionCoefficients Spectrum SpectralDensity SpectrumDomain SpectrumResolution'.split())
+_OPTIONAL_PROPERTIES = frozenset('Dispersion DispersionCoefficients Fresnel Spectrum SpectralDensity SpectrumDomain SpectrumResolution'.split())
 
 
 def repairProxies(doc):

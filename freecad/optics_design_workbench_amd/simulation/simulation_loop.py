@@ -157,6 +157,9 @@ def runSimulation(doc, action='true', *, seed=DEFAULT_SEED, device=0, resultsPat
         if getattr(bsrc, 'spectrum', None) is not None and (action in ('fans', 'singlefans') or pseudo):
           raise ValueError(f'{src.Name}: Spectrum / SpectralDensity: spectra are for the true-random mode of point sources '
                            f'(fan mode and pseudo-random mode carry one Wavelength)')
+        if action in ('fans', 'singlefans') and np.any(np.asarray(getattr(scene, 'group_fresnel', 0)) == _bake.FRESNEL_MODES['Split']):
+          raise ValueError(f"{src.Name}: Fresnel 'Split' is for the Monte-Carlo modes (a fan ray is one deterministic path; "
+                           f"'Loss' is allowed in fan mode)")
         if isinstance(bsrc, replay_source.BakedReplay):
           # replay_source.py:116-166: no fans; true and pseudo modes alike take the next
           # RaysPerIteration rays of the stock; an exhausted stock ends the simulation

@@ -187,6 +187,34 @@ class Tracer:
     kind = getattr(scene, 'group_disp_kind', None)
     if kind is not None and np.any(np.asarray(kind) != 0):
       self.setDispersion(kind, scene.group_disp)
+    # (... and its Fresnel modes)
+    mode = getattr(scene, 'group_fresnel', None)
+    if mode is not None and np.any(np.asarray(mode) != 0):
+      self.setFresnel(mode)
+
+  def setFresnel(self, mode):
+    """Fresnel modes of the uploaded scene's groups (`odw_set_fresnel`): mode [G] of 0 / '' (none), 1 / 'Loss'
+    (power *= 1 - R at every crossing of the group's surfaces), 2 / 'Split' (reflected with probability R, decided on a
+    Philox stream of its own).  Lens groups only.  None or an empty mode clears it.  Launches with a mode set run the
+    compiled kernel's FRESNEL variant under compileScene('structure') (compiledInfo()['fresnel']), else the binary tree."""
+    pi = C.POINTER(C.c_int32)
+    if mode is None or len(mode) == 0:
+      self._chk(self._lib.odw_set_fresnel(self._ctx, C.c_int32(0), None), 'odw_set_fresnel')
+      return
+    m = np.ascontiguousarray([_native.FRESNEL_MODES[v] if (v is None or isinstance(v, str)) else int(v) for v in mode], dtype=np.int32)
+    self._chk(self._lib.odw_set_fresnel(self._ctx, C.c_int32(len(m)), m.ctypes.data_as(pi)), 'odw_set_fresnel')
+
+  def fresnelReflectance(self, n1, n2, cos_i, device=False):
+    """unpolarised reflectance of a surface from index n1 to n2 at the cosines of incidence cos_i
+    (`odw_fresnel_reflectance`); device=True: evaluated by the kernel-side function"""
+    c = np.ascontiguousarray(cos_i, dtype=np.float64).reshape(-1)
+    out = np.empty(len(c), np.float64)
+    pd = C.POINTER(C.c_double)
+    f = self._lib.odw_fresnel_reflectance
+    f.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_uint64, pd, pd, C.c_int32]
+    self._chk(f(self._ctx, float(n1), float(n2), len(c), c.ctypes.data_as(pd), out.ctypes.data_as(pd), 1 if device else 0),
+              'odw_fresnel_reflectance')
+    return out
 
   def setDispersion(self, kind, coef=None):
     """Dispersion of the uploaded scene's groups (`odw_set_dispersion`): kind [G] (0 constant, 1 Sellmeier, 2 Cauchy),
@@ -276,8 +304,11 @@ class Tracer:
     # the first such launch under 'structure' (`odw_compiled_chroma_info`); 0: they walk the binary tree
     ch = C.c_int32(0)
     self._chk(self._lib.odw_compiled_chroma_info(self._ctx, C.byref(ch)), 'odw_compiled_chroma_info')
+    # fresnel: likewise for launches with a Fresnel mode set (`odw_compiled_fresnel_info`); 0 also when no mode is set
+    fr = C.c_int32(0)
+    self._chk(self._lib.odw_compiled_fresnel_info(self._ctx, C.byref(fr)), 'odw_compiled_fresnel_info')
     return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value), source=int(key.value),
-                chroma=int(ch.value))
+                chroma=int(ch.value), fresnel=int(fr.value))
 
   def setSurfaceSeed(self, seed):
     """Philox key of the stochastic-surface draws in traceRays launches"""
@@ -402,6 +433,8 @@ class Tracer:
         sc = stripped
       if getattr(sc, 'surface_samplers', None):
         raise _native.NativeError('setSceneBatch: unsupported: scenes with stochastic surfaces are traced one by one')
+      if getattr(sc, 'group_fresnel', None) is not None and np.any(np.asarray(sc.group_fresnel) != 0):
+        raise _native.NativeError('setSceneBatch: unsupported: scenes with a Fresnel mode are traced one by one')
       d, keep = _native.scene_desc(sc)
       descs.append(d)
       keeps.append(keep)

@@ -531,6 +531,48 @@ int odw_compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limi
 int odw_dispersion_check(int32_t n_groups, const int32_t* kind, const double* coef, double lo_nm, double hi_nm);
 /* no device needed: odw_set_spectrum's validation of a table                                                 */
 int odw_spectrum_check(int32_t mode, int32_t n_knots, const double* wavelength_nm, const double* cdf);
+/* ---- Fresnel reflection at lens surfaces (entry points more, no descriptor changed: still v12) ----
+ * Replaces nothing of the reference, whose lenses only bend a ray.  With n the normal along the travel direction,
+ * cos_i = n . dir, mu = n1 / n2, root = 1 - mu^2 (1 - cos_i^2), cos_t = sqrt(root) (all as the refraction has
+ * them), the unpolarised reflectance is
+ *   a = n1 cos_i, b = n2 cos_t, c = n2 cos_i, e = n1 cos_t, rs = (a - b) / (a + b), rp = (c - e) / (c + e),
+ *   R = (rs^2 + rp^2) / 2;        R = 1 under total internal reflection, where nothing changes.
+ * n1, n2 are what the launch uses: table words, n(launch wavelength) folded into them, or n(ray's wavelength).
+ *   ODW_FRESNEL_LOSS   the ray refracts as without; power *= 1 - R after the hit is recorded (the row holds the
+ *                      power before the surface, as at a mirror).  Deterministic.
+ *   ODW_FRESNEL_SPLIT  u = u53(c0, c1) of Philox4x32-10 at counter (ray_lo, ray_hi, ordinal, 7) under the launch's
+ *                      seed, ordinal = the interaction's number along the ray (what a surface draw gets).  u < R:
+ *                      the ray is reflected (mirror), stays in the medium it was in, and the sequence does not
+ *                      advance; else it transmits as without.  Power unchanged.  A ray trapped inside glass ends
+ *                      at max_intersections (ODW_CNT_CAPPED).
+ * In a medium of finite AbsorptionLength the power is ASSIGNED exp(-t / L) per segment, which overwrites factors
+ * gathered before (Reflectivity as much as 1 - R): kept as it is.
+ * mode [n_groups] for the uploaded scene's groups; n_groups = 0 clears it, and so does odw_upload_scene.
+ * ODW_ERR_INVALID naming the group: an unknown mode, a mode on a group that is not a lens.
+ * A launch with a mode set runs the compiled kernel's FRESNEL variant where one is bound
+ * (odw_compiled_fresnel_info), else instantiations of their own of the binary-tree kernel (a flat scene gets the tree
+ * spectral launches get); never the flat, grid or mesh kernel.  Same rows on both routes, bit for bit.
+ * ODW_ERR_UNSUPPORTED at the launch: scenes with stochastic surfaces, batches, ODW_FRESNEL_SPLIT in a scene with a
+ * tracing sequence.                                                                                            */
+enum { ODW_FRESNEL_NONE = 0, ODW_FRESNEL_LOSS = 1, ODW_FRESNEL_SPLIT = 2 };
+int odw_set_fresnel(odw_ctx* ctx, int32_t n_groups, const int32_t* mode);
+/* bound = the compile mode if the next launch with a Fresnel mode set, monochromatic and without segment rows, runs
+ * the compiled kernel's FRESNEL variant (its header carries a constexpr Spec::fresnel(G) per group: the modes are
+ * part of the cache key; bound by the first such launch under ODW_COMPILE_STRUCTURE, with / without the power
+ * plane), 0 if it walks the binary tree (ODW_COMPILE_OFF / AUTO, segment rows, spectral launches, a scene outside
+ * the compiled kernels' domain) or if no mode is set.                                                          */
+int odw_compiled_fresnel_info(odw_ctx* ctx, int32_t* bound);
+/* R[i] of a surface from index n1 to n2 at cos_i[i] (1 beyond the critical angle).  device = 0: on the host, no
+ * context needed (ctx may be NULL); device = 1: a small kernel that calls the device function the ray loop calls. */
+int odw_fresnel_reflectance(odw_ctx* ctx, double n1, double n2, uint64_t n, const double* cos_i, double* R,
+                            int32_t device);
+/* test support, no device needed: odw_compile_check_source for the FRESNEL variant under the modes
+ * mode [n_groups] (all 0: the plain header); ODW_ERR_INVALID as odw_set_fresnel                                */
+int odw_compile_check_fresnel(const odw_scene_desc* scene, const odw_limits* limits, const char* arch,
+                              const odw_source_desc* source, const int32_t* mode, char* header_out,
+                              uint64_t header_capacity, uint64_t* code_bytes);
+/* test support, no device needed: odw_set_fresnel's validation (group_type [n_groups] ODW_OPT_*, or NULL)      */
+int odw_fresnel_check(int32_t n_groups, const int32_t* mode, const int32_t* group_type);
 int odw_set_limits(odw_ctx* ctx, const odw_limits* limits);
 int odw_set_detector(odw_ctx* ctx, const odw_detector_desc* det);
 /* capacity of the device hit list in rows (0 frees it)                     */
