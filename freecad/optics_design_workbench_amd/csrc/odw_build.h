@@ -1255,6 +1255,10 @@ void compute_boxes(HostScene& hs, double dist_tol, std::vector<Box>& boxes) {
 //   per primitive: the frame entries that are neither 0 nor +-1 (xf_pattern), in index order | its 4 parameters |
 //                  with a box of its own (box_of[p] == p, some face): centre xyz, half extent xyz |
 //                  with a face: the constants intersect_prim derives from parameters and tolerance (spec_image_build)
+//   behind the doubles, one word of 64 bits that is not one: bit s = solid s is isolated (compute_boxes:
+//            ODW_FLAG_ISOLATED).  Isolation depends on the boxes' values, so it is a value like them: the header never
+//            holds it, and in a batch every scene's image carries its own (which is why the word lies in the per-scene
+//            part and not in the limits section, read from the kernel arguments for every scene of a batch)
 // The layout depends on the structure only, the values on the scene's numbers and the limits.
 
 // zero / +-1 pattern of a frame's 12 entries (odw_kernels.hip: xf_comb): bits 0-11 entry != 0, 12-23 entry == +1,
@@ -1317,10 +1321,12 @@ constexpr size_t kSpecArgBytes = 4096 - 512;
 struct SpecLayout {
   int n = 0, ng = 0, size = 0;
   int gf = 0, gd = 0, gi = 0;                       // group_f64, group_gdir, group_i32 rows
+  int iso = 0;                                      // the mask of isolated solids (one word), behind the plain layout's last double
   std::vector<int> frame, par, box, der;            // per primitive (box, der: -1 = none)
   std::vector<int> box_of, box_shared;
   std::vector<int> dc;                              // spectral variant: per group, its six dispersion coefficients (-1: none); else empty
-  bool fits(size_t params_bytes) const { return ((params_bytes + 7) & ~(size_t)7) + 8 + (size_t)size * 8 <= kSpecArgBytes; }
+  int words() const { return std::max(size, iso + 1); }     // the image as a kernel reads it: the doubles and the mask word
+  bool fits(size_t params_bytes) const { return ((params_bytes + 7) & ~(size_t)7) + 8 + (size_t)words() * 8 <= kSpecArgBytes; }
 };
 
 inline int spec_derived_count(int type) {
@@ -1352,7 +1358,11 @@ inline SpecLayout spec_image_layout(const HostScene& hs, const int32_t* disp_kin
     const int nd = faces ? spec_derived_count(hs.prim_i32[4 * p]) : 0;
     if (nd) { L.der[p] = at; at += nd; }
   }
+  // (the doubles of the plain layout end here, and `size` with them; the mask word stands behind them, in front of a
+  //  spectral variant's coefficients, whose layout holds it inside its size: words() in every case)
+  L.iso = at;
   if (disp_kind) {
+    at += 1;
     L.dc.assign(std::max(1, ng), -1);
     for (int g = 0; g < ng; ++g)
       if (disp_kind[g]) { L.dc[g] = at; at += ODW_DISP_COEFS; }
@@ -1372,15 +1382,29 @@ inline void box_centre_half(double lo, double hi, double& c, double& h) {
   while (c - h > lo || c + h < hi) h = std::nextafter(h, INFINITY);
 }
 
-// The image of hs (boxes built: compute_boxes) for the limits lim, img[0 .. L.size).  Every derived constant is the
+// The isolated solids of hs as the compiled kernels read them: bit s = the primitives of solid s carry
+// ODW_FLAG_ISOLATED (compute_boxes sets it on every primitive of a solid that has a box, or on none).  Solid ids of 64
+// and more -- 0x7fff, the id of solids that did not fit the flag word, among them -- have no bit: never isolated here.
+inline uint64_t spec_isolated_mask(const HostScene& hs) {
+  uint64_t mask = 0;
+  for (int p = 0; p < hs.n_prims; ++p) {
+    const int32_t w = hs.prim_i32[4 * (size_t)p + 2];
+    const int sid = w >> ODW_SOLID_SHIFT;
+    if ((w & ODW_FLAG_ISOLATED) && sid >= 0 && sid < 64) mask |= 1ull << sid;
+  }
+  return mask;
+}
+
+// The image of hs (boxes built: compute_boxes) for the limits lim: its doubles, img[0 .. L.size), or -- whole, what a
+// launch hands its kernel -- img[0 .. L.words()) with the mask of isolated solids at L.iso.  Every derived constant is the
 // sequence of IEEE operations intersect_prim performs on the device for it (odw_kernels.hip, compiled with
 // -ffp-contract=on): std::fma where a product and a sum of ONE expression fuse there, plain operations elsewhere --
 // and nothing else fuses here.
 inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const SpecLayout& L, double* img,
-                             const double* disp_coef = nullptr) {
+                             const double* disp_coef = nullptr, bool whole = false) {
 #pragma clang fp contract(off)
   const double tol = lim.dist_tol;
-  std::fill(img, img + L.size, 0.0);
+  std::fill(img, img + (whole ? L.words() : L.size), 0.0);
   if (disp_coef)
     for (int g = 0; g < (int)L.dc.size() && g < L.ng; ++g)
       if (L.dc[g] >= 0) std::memcpy(&img[L.dc[g]], disp_coef + ODW_DISP_COEFS * g, ODW_DISP_COEFS * sizeof(double));
@@ -1391,6 +1415,10 @@ inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const
     for (int k = 0; k < 4; ++k) img[L.gf + 4 * g + k] = hs.group_f64[4 * (size_t)g + k];
     for (int k = 0; k < 3; ++k) img[L.gd + 3 * g + k] = hs.group_gdir[3 * (size_t)g + k];
     std::memcpy(&img[L.gi + 2 * g], &hs.group_i32[4 * (size_t)g], 4 * sizeof(int32_t));
+  }
+  if (whole) {
+    const uint64_t iso = spec_isolated_mask(hs);
+    std::memcpy(&img[L.iso], &iso, sizeof iso);
   }
   for (int p = 0; p < L.n; ++p) {
     const double* pf = &hs.prim_f64[16 * (size_t)p];

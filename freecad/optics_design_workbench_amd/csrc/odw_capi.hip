@@ -1506,6 +1506,7 @@ int odw_spec_image(const odw_scene_desc* scene, const odw_limits* limits, double
   const std::string why = spec_ineligible(tmp);
   if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_spec_image: " + why);
   const SpecLayout L = spec_image_layout(tmp);
+  // (the doubles: the mask of isolated solids, the one word behind them, is no double and not counted)
   if (image_size) *image_size = (uint64_t)L.size;
   if (in_arguments) *in_arguments = L.fits(sizeof(TraceParams)) ? 1 : 0;
   if (image) {
@@ -1515,7 +1516,10 @@ int odw_spec_image(const odw_scene_desc* scene, const odw_limits* limits, double
     lim.dist_tol = limits->dist_tol;
     lim.power_tol = limits->power_tol;
     lim.max_intersections = limits->max_intersections;
-    spec_image_build(tmp, lim, L, image);
+    std::vector<double> whole((size_t)L.words());
+    spec_image_build(tmp, lim, L, whole.data(), nullptr, true);
+    // (a caller with room for one word more gets the mask too, as the kernel finds it: 64 bits in image[*image_size])
+    std::memcpy(image, whole.data(), (size_t)std::min<uint64_t>(image_capacity, (uint64_t)L.words()) * sizeof(double));
   }
   if (boxes)
     for (int p = 0; p < L.n; ++p) std::memcpy(boxes + 6 * (size_t)p, &tmp.prim_hdr[8 * (size_t)p], 6 * sizeof(double));
@@ -2088,7 +2092,7 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
   // one block of doubles per scene: prim_f64 (16 n) | prim_hdr (8 n) | group_f64 (4 x 64) | group_gdir (3 x 64) |
   // the value image of the compiled kernel's BATCH variant (odw_build.h: spec_image_build)
   const size_t o_hdr = 16 * n, o_gf = o_hdr + 8 * n, o_gd = o_gf + ODW_MAX_GROUPS * 4, o_img = o_gd + ODW_MAX_GROUPS * 3,
-               stride = o_img + (size_t)L0.size;
+               stride = o_img + (size_t)(eligible ? L0.words() : 0);
   std::vector<double> blocks(stride * (size_t)n_scenes, 0.0);
   for (int k = 0; k < n_scenes; ++k) {
     HostScene tmp;
@@ -2105,7 +2109,7 @@ int odw_upload_scene_batch(odw_ctx* ctx, const odw_scene_desc* scenes, int32_t n
       images = false;                                  // (generic kernels only for this batch)
     }
     double* b = blocks.data() + stride * (size_t)k;
-    if (images) spec_image_build(tmp, ctx->P.lim, L0, b + o_img);
+    if (images) spec_image_build(tmp, ctx->P.lim, L0, b + o_img, nullptr, true);
     std::memcpy(b, tmp.prim_f64.data(), 16 * n * sizeof(double));
     std::memcpy(b + o_hdr, tmp.prim_hdr.data(), 8 * n * sizeof(double));
     // (the isolated-solid shortcut depends on the boxes' values; it never changes a result: left out of batches)

@@ -217,7 +217,6 @@ struct NoSpec {
   static constexpr int type(int) { return 0; }
   static constexpr int gtype(int) { return 0; }
   static constexpr int cond(int) { return 0; }
-  static constexpr bool isolated() { return true; }
 };
 // The STRUCTURE of the point source a kernel is compiled against (odw_spec.h: struct SpecSource, written when the
 // launch that binds the kernel generates its rays from a table source): one theta table or one per phi cell,
@@ -1328,7 +1327,7 @@ __device__ __forceinline__ SpecBox spec_box(const SceneView& sv) {
 // (SPEC::box_of = the first primitive with that set).  The later ones reuse the first one's outcome (taken
 // with a cut at least as wide: conservative).
 template <class SPEC, int PI>
-__device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid, int only_solid,
+__device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid,
                                           uint64_t mask, bool* boxhit, SpecBox& pending) {
   constexpr int flags = SPEC::flags(PI);
   // relevant groups: a constant without sequential mode (ignored groups' primitives leave no code),
@@ -1342,10 +1341,9 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
     // every segment, and that cost more than it hid -- profiles/r08/README.md.)
     [[maybe_unused]] const SpecBox own = pending;
     if constexpr (SPEC::box_of(PI) == PI && spec_next_box<SPEC>(PI + 1) >= 0) pending = spec_box<SPEC, spec_next_box<SPEC>(PI + 1)>(sv);
-    // (only_solid: the isolated solid the ray has just entered, ODW_FLAG_ISOLATED -- a scene without such solids
-    //  never sets it, and the test folds away)
-    if ((!SPEC::seq() || ((mask >> SPEC::group(PI)) & 1)) && (flags >> ODW_SOLID_SHIFT) != skip_solid &&
-        (!SPEC::isolated() || only_solid < 0 || (flags >> ODW_SOLID_SHIFT) == only_solid)) {
+    // (the isolated solid a ray has just entered is no predicate here: a wave whose lanes all stand in one takes
+    //  spec_uniform instead of this loop, every other wave searches everything)
+    if ((!SPEC::seq() || ((mask >> SPEC::group(PI)) & 1)) && (flags >> ODW_SOLID_SHIFT) != skip_solid) {
       bool in_box;
       if constexpr (SPEC::box_of(PI) != PI) {
         in_box = boxhit[SPEC::box_of(PI)];
@@ -1377,21 +1375,112 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
 }
 template <class T, T... I> struct IndexList {};      // (std::integer_sequence without <utility>: runtime compilation has no libstdc++)
 template <class SPEC, int... PI>
-__device__ __forceinline__ void spec_prims(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid, int only_solid,
+__device__ __forceinline__ void spec_prims(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid,
                                            uint64_t mask, IndexList<int, PI...>) {
   bool boxhit[sizeof...(PI)] = {};
   // the first block; every spec_prim that uses one asks for the next (from sv.img as it stands at this segment: a
   // batch's image moves with the hand-out unit's scene)
   SpecBox pending = {};
   if constexpr (spec_next_box<SPEC>(0) >= 0) pending = spec_box<SPEC, spec_next_box<SPEC>(0)>(sv);
-  (spec_prim<SPEC, PI>(sv, q, oi, inv, skip_solid, only_solid, mask, boxhit, pending), ...);
+  (spec_prim<SPEC, PI>(sv, q, oi, inv, skip_solid, mask, boxhit, pending), ...);
 }
 
-template <bool BVH, class SPEC = NoSpec, bool ASPH = false>
+// ---- a wave inside one isolated solid (compiled kernels) ----
+// A ray that has just entered an isolated solid (odw_build.h: compute_boxes -- its box keeps 4 distTol clear of every
+// other solid's) meets that solid before anything else: its own primitives are all the segment has to search.  The
+// lanes of a wave are refilled together and, in a beam, stand on the same segment of the same path, so "every live
+// lane has just entered solid S" is a fact about the WAVE: one scalar branch acts on it, and the search it opens has
+// no reciprocal of the direction, no box block or screen, no skip / mask predicate -- every lane is inside S (so not
+// leaving a convex solid), and the box of S holds every point the tolerance rules accept on it.  The exact tests, the
+// trims, consider_spec and the closing rule of nearest() are the general loop's.
+// Which solids qualify is STRUCTURE: a solid of ONE group that can be a medium -- a lens; nothing is entered through a
+// mirror or an absorber -- with an id the mask word has a bit for, in a scene without sequential mode (whose per-lane
+// group masks the path does not carry).  WHETHER such a solid is isolated is a value: bit S of the image's word
+// Spec::iso, read by the one wave that asks.
+constexpr bool can_be_medium(int gtype) {     // interact(): the groups whose branch sets `medium`
+  return gtype != ODW_OPT_MIRROR && gtype != ODW_OPT_ABSORBER && gtype != ODW_OPT_VACUUM;
+}
+template <class SPEC>
+constexpr int spec_solid(int pi) { return SPEC::flags(pi) >> ODW_SOLID_SHIFT; }
+// the first primitive of solid s that leaves code (-1: none)
+template <class SPEC>
+constexpr int spec_solid_first(int s) {
+  for (int p = 0; p < SPEC::N; ++p)
+    if (spec_live<SPEC>(p) && spec_solid<SPEC>(p) == s) return p;
+  return -1;
+}
+template <class SPEC>
+constexpr bool spec_cand_solid(int s) {
+  if (SPEC::seq() || s < 0 || s >= 64) return false;
+  const int f = spec_solid_first<SPEC>(s);
+  if (f < 0 || !can_be_medium(SPEC::gtype(SPEC::group(f)))) return false;
+  for (int p = f; p < SPEC::N; ++p)
+    if (spec_live<SPEC>(p) && spec_solid<SPEC>(p) == s && SPEC::group(p) != SPEC::group(f)) return false;
+  return true;
+}
+// how many solids a wave can take the path for (0: the kernel carries none of its code)
+template <class SPEC>
+constexpr int spec_cand_count() {
+  int k = 0;
+  for (int p = 0; p < SPEC::N; ++p)
+    if (spec_live<SPEC>(p) && spec_solid_first<SPEC>(spec_solid<SPEC>(p)) == p && spec_cand_solid<SPEC>(spec_solid<SPEC>(p))) ++k;
+  return k;
+}
+template <class SPEC, int S, int PI>
+__device__ __forceinline__ void spec_solid_prim(const SceneView& sv, Query& q) {
+  if constexpr (spec_live<SPEC>(PI) && spec_solid<SPEC>(PI) == S)
+    intersect_prim<SPEC::rare(), SPEC, PI>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), SPEC::flags(PI), SPEC::cond_word(PI));
+}
+// PF opens a candidate solid S: if the wave's first live lane stands in S, S is isolated in this scene, and every
+// live lane stands in S with S's group as its medium, the primitives of S in index order -- true; else nothing
+template <class SPEC, int PF, int... PI>
+__device__ __forceinline__ bool spec_uniform_solid(const SceneView& sv, Query& q, int first_only, int only_solid,
+                                                   IndexList<int, PI...>) {
+  constexpr int S = spec_solid<SPEC>(PF);
+  if constexpr (spec_cand_solid<SPEC>(S) && spec_solid_first<SPEC>(S) == PF) {
+    if (first_only == S) {
+      static_assert(SPEC::iso >= 4 && SPEC::iso < SPEC::IMG, "the mask of isolated solids outside the value image");
+      const uint64_t iso = *(cu64)(sv.img + SPEC::iso);
+      const uint64_t others = __ballot(only_solid != S || q.medium != SPEC::group(PF));
+      if (((iso >> S) & 1ull) != 0ull && others == 0ull) {
+        (spec_solid_prim<SPEC, S, PI>(sv, q), ...);
+        return true;
+      }
+    }
+  }
+  return false;
+}
+template <class SPEC, int... PI>
+__device__ __forceinline__ bool spec_uniform(const SceneView& sv, Query& q, int only_solid, IndexList<int, PI...> all) {
+  // (called by the live lanes of the wave: the first of them names the solid, the vote is theirs)
+  const int first_only = __builtin_amdgcn_readfirstlane(only_solid);
+  if (first_only < 0) return false;
+  return (spec_uniform_solid<SPEC, PI>(sv, q, first_only, only_solid, all) || ...);
+}
+
+// reciprocal of the direction and origin x reciprocal, as the box screens take them
+__device__ __forceinline__ void ray_reciprocals(d3 start, d3 dn, d3& inv, d3& oi) {
+  inv = mk(frcp1(dn.x), frcp1(dn.y), frcp1(dn.z));
+  oi = mk(start.x * inv.x, start.y * inv.y, start.z * inv.z);
+#if ODW_DOUBLE == 9
+  {
+    const d3 dn2 = mk(opq(dn.x), opq(dn.y), opq(dn.z));
+    const d3 inv2 = mk(frcp1(dn2.x), frcp1(dn2.y), frcp1(dn2.z));
+    const d3 oi2 = mk(start.x * inv2.x, start.y * inv2.y, start.z * inv2.z);
+    inv = inv2.x == inv.x ? inv : inv2;
+    oi = oi2.y == oi.y ? oi : oi2;
+  }
+#endif
+}
+
+// UNIFORM (compiled kernels): the instantiation carries spec_uniform.  Not the BATCH variant's: the sweep's launches
+// (a wide source, rays that miss the lens beside rays that cross it: mixed waves) ran 1 - 2 % slower with it
+// (profiles/r09/README.md), so a batch keeps the general loop alone and its code is what it was.
+template <bool BVH, class SPEC = NoSpec, bool ASPH = false, bool UNIFORM = true>
 __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& sv,
                                        const DeviceLimits& lim, d3 start, d3 dn, int medium,
                                        uint64_t mask, double& t_hit, int& face,
-                                       int* __restrict__ stack, int skip_solid, int only_solid = -1) {
+                                       int* __restrict__ stack, int skip_solid, int& only_solid) {
   Query q;
   q.start = start; q.dn = dn;
   if constexpr (SPEC::enabled) { q.tol = sv.lim[0]; q.tmax = sv.lim[1]; }
@@ -1401,23 +1490,20 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
   q.cut = q.tmax;
   q.any.t = INFINITY; q.any.prim = 0x7fffffff; q.any.face = 0x7fffffff;
   q.oth = q.any;
-#if ODW_DOUBLE == 9
-  d3 inv = mk(frcp1(dn.x), frcp1(dn.y), frcp1(dn.z));
-  d3 oi = mk(start.x * inv.x, start.y * inv.y, start.z * inv.z);
-  {
-    const d3 dn2 = mk(opq(dn.x), opq(dn.y), opq(dn.z));
-    const d3 inv2 = mk(frcp1(dn2.x), frcp1(dn2.y), frcp1(dn2.z));
-    const d3 oi2 = mk(start.x * inv2.x, start.y * inv2.y, start.z * inv2.z);
-    inv = inv2.x == inv.x ? inv : inv2;
-    oi = oi2.y == oi.y ? oi : oi2;
-  }
-#else
-  const d3 inv = mk(frcp1(dn.x), frcp1(dn.y), frcp1(dn.z));
-  const d3 oi = mk(start.x * inv.x, start.y * inv.y, start.z * inv.z);
-#endif
+  d3 inv, oi;
   if constexpr (SPEC::enabled) {
-    spec_prims<SPEC>(sv, q, oi, inv, skip_solid, only_solid, mask, __make_integer_seq<IndexList, int, SPEC::N>{});
+    // a wave whose live lanes have all just entered one isolated lens searches that lens alone (spec_uniform); every
+    // other wave runs the general loop over every primitive, which takes no notice of `only_solid` -- and says so to
+    // the caller, whose retry of a segment that found nothing is for the short search alone
+    bool uniform = false;
+    if constexpr (UNIFORM && spec_cand_count<SPEC>() > 0) uniform = spec_uniform<SPEC>(sv, q, only_solid, __make_integer_seq<IndexList, int, SPEC::N>{});
+    if (!uniform) {
+      ray_reciprocals(start, dn, inv, oi);
+      spec_prims<SPEC>(sv, q, oi, inv, skip_solid, mask, __make_integer_seq<IndexList, int, SPEC::N>{});
+      only_solid = -1;
+    }
   } else if (!BVH) {
+    ray_reciprocals(start, dn, inv, oi);
     // without sequential mode the set of relevant groups is the same for
     // every ray: the test is scalar and skips a primitive for the whole wave
     const bool per_lane_mask = sc.seq_enabled != 0;
@@ -1442,6 +1528,7 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
       intersect_prim<0>(sv, q, p, type, g, flags, cond_word);
     }
   } else {
+    ray_reciprocals(start, dn, inv, oi);
     // BVH traversal in float32 (culling only: leaves are intersected in
     // float64).  One 64-byte node fetch carries the boxes of both children.
     // "while-while": every lane walks inner nodes (cheap, same code for all
@@ -2005,9 +2092,7 @@ __device__ __noinline__ RayInit generate_ray_spec_call(csource src, uint64_t ray
 // generic kernels gather it per lane.  A compiled scene knows which groups can be a medium at all -- lenses, and
 // transmission gratings -- and there are a handful at most: a select over them, every operand a scalar load at a
 // constant offset, no vector load to wait for.  (More than eight such groups: the gather.)
-constexpr bool can_be_medium(int gtype) {     // interact(): the groups whose branch sets `medium`
-  return gtype != ODW_OPT_MIRROR && gtype != ODW_OPT_ABSORBER && gtype != ODW_OPT_VACUUM;
-}
+// (can_be_medium: above, beside spec_cand_solid)
 template <class SPEC, int G = 0>
 constexpr int spec_media() {
   if constexpr (G >= SPEC::NG) return 0;
@@ -2203,7 +2288,10 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   const double out = entering ? -dot(dir, n) : dot(dir, n);
   if constexpr ((flags & ODW_FLAG_CONVEX) != 0) skip = out > 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else skip = -1;
-  if constexpr ((flags & ODW_FLAG_ISOLATED) != 0) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
+  // (the solid the ray has just entered, where a wave could search it alone: spec_cand_solid -- structure; whether
+  //  it is isolated in this scene is asked by the wave that takes the path, nearest().  `out` is taken after
+  //  interact(): the direction a Fresnel ghost or a scattered ray leaves with decides, as in the generic kernel)
+  if constexpr (spec_cand_solid<SPEC>(flags >> ODW_SOLID_SHIFT)) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else only = -1;
 }
 template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, int... PI>
@@ -2466,8 +2554,11 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
       mask &= ~sc.ignore_mask;
       double t_hit;
       int face;
-      const int prim = nearest<BVH, SPEC, ASPH>(sc, sv, lim, point, dir, medium, mask, t_hit, face,
-                                          bvh_stack + threadIdx.x, skip, BVH ? -1 : only);
+      // (a compiled kernel clears `only` when its wave ran the general loop, which searches everything: nearest())
+      int only_now = BVH ? -1 : only;
+      const int prim = nearest<BVH, SPEC, ASPH, !BATCH>(sc, sv, lim, point, dir, medium, mask, t_hit, face,
+                                          bvh_stack + threadIdx.x, skip, only_now);
+      if constexpr (SPEC::enabled) only = only_now;
       // A ray that has entered an isolated solid within distTol beyond one of its edges can pass it by: then, and
       // only then, the solid's own primitives yield nothing -- the segment is done again with every primitive, in
       // the next trip of the loop (no second copy of the search, no state kept across one)

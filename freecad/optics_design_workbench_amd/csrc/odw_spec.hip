@@ -193,13 +193,18 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
   for (int p = 0; p < n; ++p) rare |= (type[p] == ODW_PRIM_PARABOLOID ? 1 : 0) | (type[p] == ODW_PRIM_ELLIPSOID ? 2 : 0) | (type[p] == ODW_PRIM_CONICOID ? 4 : 0) |
                                       (type[p] == ODW_PRIM_ASPHERE ? 8 : 0);
   s += "  static constexpr int rare() { return " + std::to_string(rare) + "; }\n";
-  // ODW_FLAG_ISOLATED (a ray that has entered an isolated solid tests that solid only) is left to the generic
-  // flat kernel, which gains 3 % on lensesAndMirrors from it: in a compiled kernel a skipped box test saves less
-  // than the extra predicate on every primitive costs (11.85 against 11.30 ms, 8 spilled SGPRs).  The rule
-  // never changes a result, so the two kernels still produce the same rows.
-  s += "  static constexpr bool isolated() { return false; }\n";
+  // ODW_FLAG_ISOLATED (a ray that has entered an isolated solid tests that solid only) is stripped from the flags
+  // above: whether a solid is isolated depends on the boxes' values, and one kernel serves a whole sweep.  The kernel
+  // reads it at run time from one word of the value image (Spec::iso: bit s = solid s is isolated, odw_build.h) and
+  // acts on it per WAVE, never per lane: when every live lane of a wave has just entered the same isolated solid that
+  // can be a medium -- a lens --, one scalar branch sends the wave through that solid's primitives alone, without
+  // reciprocals, box screens or predicates (odw_kernels.hip: spec_uniform); every other wave runs the general loop,
+  // which knows nothing of the rule.  (As a per-lane predicate on every unrolled primitive the rule cost more than it
+  // saved: 11.85 against 11.30 ms per 1e8 lensesAndMirrors rays, 8 more spilled SGPRs.)  The rule never changes a
+  // result, so the compiled and the generic kernels still produce the same rows.
+  s += "  static constexpr int iso = " + std::to_string(L.iso) + ";\n";
   // the value image: its size, whether it travels in the kernel arguments, and the offset of every piece
-  s += "  static constexpr int IMG = " + std::to_string(L.size) + ";\n";
+  s += "  static constexpr int IMG = " + std::to_string(L.words()) + ";\n";
   s += std::string("  static constexpr bool img_fits = ") + (L.fits(sizeof(TraceParams) + (disp_kind ? sizeof(DeviceChroma) : 0)) ? "true" : "false") + ";\n";
   if (disp_kind) {
     std::vector<int> kinds(std::max(1, ng), 0);
@@ -559,8 +564,8 @@ int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const
   constexpr size_t tail = (sizeof(TraceParams) + 7) & ~(size_t)7;
   const bool resident = !batch && L.fits(sizeof(TraceParams) + (chroma ? sizeof(DeviceChroma) : 0));
   std::vector<double>& img = ctx->spec_image_now;
-  img.resize((size_t)L.size);
-  spec_image_build(ctx->hs, ctx->P.lim, L, img.data(), chroma ? ctx->disp_coef : nullptr);
+  img.resize((size_t)L.words());
+  spec_image_build(ctx->hs, ctx->P.lim, L, img.data(), chroma ? ctx->disp_coef : nullptr, true);
   const double* dev = nullptr;
   if (batch) {
     if (!ctx->batch_img_off) return fail(ctx, ODW_ERR_DEVICE, "batch without value images");
@@ -575,7 +580,7 @@ int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const
     }
     dev = (const double*)ctx->spec_image.p;
   }
-  const size_t nv = resident ? (size_t)L.size : (size_t)kSpecImageLimits;
+  const size_t nv = resident ? (size_t)L.words() : (size_t)kSpecImageLimits;
   std::vector<char>& args = ctx->spec_args;
   static_assert(sizeof(DeviceChroma) % 8 == 0 && alignof(DeviceChroma) == 8, "DeviceChroma follows the tail without padding");
   const size_t tail_end = tail + sizeof(double*) + nv * sizeof(double);

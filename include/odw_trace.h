@@ -800,7 +800,10 @@ int odw_table_slopes(const double* cdf, const double* edges, int32_t n_tables, i
  * box (the half extent rounded outward: [c - h, c + h] holds the box the generic kernels screen with), and the
  * constants its intersection derives from parameters and tolerance: box S_i + tol (3); cylinder, cone,
  * paraboloid H + tol, R1 R1 (1 - 1e-9), (R1 + tol)^2, (R2 + tol)^2; torus bound, slab half height, inner
- * radius, its square.
+ * radius, its square.  Behind the doubles the kernel's image holds one word of 64 bits that is none -- bit s = solid s
+ * is isolated (its box keeps 4 distTol clear of every other solid's), what the compiled kernels' wave-uniform search
+ * of one solid asks for --: not counted in *image_size, written to image[*image_size] when image_capacity has room
+ * for it; its place is `Spec::iso` of the header odw_compile_check writes.
  * offsets [offsets_capacity >= 3 + 5 n_prims] (may be NULL): group_f64, group_gdir, group_i32 sections, then
  * per primitive: frame, parameters, box (-1: it shares another's or has no face), derived (-1: none), the
  * primitive whose box it is screened with.
