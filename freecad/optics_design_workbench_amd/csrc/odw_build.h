@@ -543,6 +543,8 @@ float round_up(double v) {
 
 constexpr int kBvhLeaf = 8;   // largest leaf the SAH may form (measured: 8 >= 4 > 2 > 1 on meshes; round 5, mesh kernel at 1e6 facets: 8 / 6 / 4 / 3 / 2 / 1 = 7.70 / 7.73 / 7.84 / 7.95 / 8.16 / 9.04 ms -- candidates per segment 18 -> 8, node visits 11.7 -> 14.7)
 constexpr int kBvhSweepMax = 256;        // nodes with more primitives use binned SAH
+// the walk's leaf word, -2 - (first | count << 24), holds 24 bits of `first`: the leaf order must stay below 1 << 24 entries
+inline bool bvh_order_fits(size_t entries) { return entries < ((size_t)1 << 24); }
 
 // Surface-area-heuristic build (full sweep on the three axes).  Measured on
 // hugeArray: 33 node visits and 3.0 primitive tests per segment against 57 /
@@ -613,7 +615,9 @@ struct BvhBuilder {
     // leaf if splitting does not pay (traversal step ~ 1 primitive test) and it is small
     const double leaf_cost = area(bb) * m;
     if (m <= kBvhLeaf && best_cost + area(bb) >= leaf_cost) return make_leaf();
-    if (best_axis < 0) return make_leaf();
+    // (no cost compares below infinity -- boxes whose area overflows --: median splits, never one leaf of up to
+    //  kBvhSweepMax primitives, which the 7-bit count of a leaf word could not hold)
+    if (best_axis < 0) return build_big(ids, depth, bb);
     std::vector<int> left(best_sorted.begin(), best_sorted.begin() + best_split);
     std::vector<int> right(best_sorted.begin() + best_split, best_sorted.end());
     return inner(left, right, depth, bb);
@@ -1513,6 +1517,10 @@ int build_accel(const HostScene& hs, std::vector<Box> boxes, double dist_tol, in
   for (int i = 0; i < n; ++i)
     if (!dead[i]) ids.push_back(i);
   if (ids.empty() && n > 0) ids.push_back(0);   // (a far-away box: the tree needs one leaf)
+  if (!bvh_order_fits(ids.size())) {
+    A = SceneAccel();
+    return refuse(error, ODW_ERR_UNSUPPORTED, "more than 16777215 (2^24 - 1) primitives in the tree: a leaf word holds 24 bits of its first primitive");
+  }
   b.nodes.reserve((size_t)n);
   const BvhBuilder::Ref root = b.build(ids, 0);
   if (root.count > 0) {   // everything in one leaf: wrap it into a root node
