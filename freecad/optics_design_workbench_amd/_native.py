@@ -52,7 +52,8 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_enable_power_histogram', 'odw_fetch_power_histogram', 'odw_device_power_histogram', 'odw_hits_bin_power', 'odw_compiled_power_info',
            'odw_set_dispersion', 'odw_set_spectrum', 'odw_trace_rays_spectral', 'odw_ray_wavelengths', 'odw_dispersion_index',
            'odw_dispersion_check', 'odw_spectrum_check', 'odw_compiled_chroma_info', 'odw_compile_check_chroma',
-           'odw_set_fresnel', 'odw_compiled_fresnel_info', 'odw_fresnel_reflectance', 'odw_compile_check_fresnel', 'odw_fresnel_check']
+           'odw_set_fresnel', 'odw_compiled_fresnel_info', 'odw_fresnel_reflectance', 'odw_compile_check_fresnel', 'odw_fresnel_check',
+           'odw_set_coating', 'odw_coating_check', 'odw_coated_reflectance', 'odw_compile_check_coating']
 
 # dispersion of a group (ODW_DISP_*) and spectrum of a point source (ODW_SPECTRUM_*)
 DISP_NONE, DISP_SELLMEIER, DISP_CAUCHY = 0, 1, 2
@@ -63,6 +64,7 @@ STREAM_WAVELENGTH = 6                     # ODW_STREAM_WAVELENGTH: word 3 of the
 # Fresnel mode of a lens group (ODW_FRESNEL_*)
 FRESNEL_NONE, FRESNEL_LOSS, FRESNEL_SPLIT = 0, 1, 2
 FRESNEL_MODES = {'': 0, None: 0, 'Loss': 1, 'Split': 2}
+COAT_LAYERS = 4                           # ODW_COAT_LAYERS: layers of a group's thin-film coating at most
 STREAM_FRESNEL = 7                        # ODW_STREAM_FRESNEL: word 3 of the Philox counter of the reflect-or-transmit draw
 
 _pd = C.POINTER(C.c_double)
@@ -321,6 +323,75 @@ def compile_check_fresnel(scene, limits, arch=None, source=None, modes=None):
          m.ctypes.data_as(_pi), buf, len(buf), C.byref(size))
   check(None, rc, 'odw_compile_check_fresnel')
   return buf.value.decode(), int(size.value)
+
+
+def coating_tables(coating, n_groups=None):
+  """(n_layers int32 [G], layers float64 [G, COAT_LAYERS, 2]) of `coating`: such a pair already, the bake's group_coating, or one list of
+  (index, thickness_nm) pairs per group (None or empty: no coating).  Counts beyond COAT_LAYERS are kept as they are -- the
+  library refuses them by name -- and the rows that fit are filled"""
+  if isinstance(coating, np.ndarray) and coating.dtype.names == ('n', 'layers'):        # (the bake's group_coating)
+    coating = (coating['n'], coating['layers'])
+  if isinstance(coating, tuple) and len(coating) == 2 and np.ndim(coating[0]) == 1 and np.ndim(coating[1]) == 3:
+    cnt = _arr(coating[0], np.int32).reshape(-1)
+    lay = _arr(coating[1], np.float64).reshape(len(cnt), COAT_LAYERS, 2)
+    return cnt, lay
+  stacks = [[] if st is None else list(st) for st in coating]
+  cnt = np.array([len(st) for st in stacks], dtype=np.int32)
+  lay = np.zeros((len(stacks), COAT_LAYERS, 2), dtype=np.float64)
+  for g, st in enumerate(stacks):
+    for j, (n, d) in enumerate(st[:COAT_LAYERS]):
+      lay[g, j] = float(n), float(d)
+  return cnt, lay
+
+
+def compile_check_coating(scene, limits, arch=None, source=None, modes=None, coating=None):
+  """Host only (no GPU): header and code size of the compiled kernel's FRESNEL variant for `scene` under `modes` (default:
+  its group_fresnel) and the stacks `coating` (default: its group_coating; see coating_tables)
+  (`odw_compile_check_coating`); no layer anywhere: compile_check_fresnel's header"""
+  d, keep = scene_desc(scene)
+  lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
+                   float(limits.power_tol))
+  m = _arr(scene.group_fresnel if modes is None else modes, np.int32).reshape(-1)
+  if coating is None:
+    coating = getattr(scene, 'group_coating', None)
+  cnt, lay = coating_tables(coating if coating is not None else [[]] * scene.n_groups)
+  if len(m) != scene.n_groups or len(cnt) != scene.n_groups:          # (the entry point reads one row per group of the scene)
+    raise ValueError(f'compile_check_coating: {len(m)} modes and {len(cnt)} stacks for a scene of {scene.n_groups} groups')
+  buf = C.create_string_buffer(1 << 20)
+  size = C.c_uint64(0)
+  f = lib().odw_compile_check_coating
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), C.c_char_p, C.POINTER(SourceDesc), _pi, _pi, _pd, C.c_char_p, C.c_uint64,
+                C.POINTER(C.c_uint64)]
+  sd, keep_source = source_desc(source) if source is not None else (None, None)
+  rc = f(C.byref(d), C.byref(lim), arch.encode() if arch else None, C.byref(sd) if sd is not None else None,
+         m.ctypes.data_as(_pi), cnt.ctypes.data_as(_pi), lay.ctypes.data_as(_pd), buf, len(buf), C.byref(size))
+  check(None, rc, 'odw_compile_check_coating')
+  return buf.value.decode(), int(size.value)
+
+
+def coated_reflectance(n1, n2, cos_i, layers, wavelength_nm, entering=True):
+  """Host only (no GPU): the unpolarised reflectance of a surface from index n1 to n2 that carries the stack `layers`
+  ((index, thickness_nm) pairs from the outside inwards; entering: the ray meets them in that order) at the cosines of
+  incidence `cos_i` -- the library's coated_reflectance (`odw_coated_reflectance` without a context)"""
+  c = _arr(cos_i, np.float64).reshape(-1)
+  lay = _arr(layers, np.float64).reshape(-1, 2) if len(layers) else np.zeros((0, 2))
+  out = np.empty(len(c), np.float64)
+  f = lib().odw_coated_reflectance
+  f.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, _pd, C.c_double, C.c_uint64, _pd, _pd, C.c_int32]
+  check(None, f(None, float(n1), float(n2), 1 if entering else 0, len(lay), lay.ctypes.data_as(_pd) if len(lay) else None,
+                float(wavelength_nm), len(c), c.ctypes.data_as(_pd), out.ctypes.data_as(_pd), 0), 'odw_coated_reflectance')
+  return out
+
+
+def coating_check(coating, modes=None):
+  """Host only (no GPU): `odw_set_coating`'s validation of the stacks `coating` (see coating_tables; with the groups'
+  Fresnel modes where given); raises NativeError naming the group"""
+  cnt, lay = coating_tables(coating)
+  m = _arr(modes, np.int32).reshape(-1) if modes is not None else None
+  f = lib().odw_coating_check
+  f.argtypes = [C.c_int32, _pi, _pd, _pi]
+  check(None, f(len(cnt), cnt.ctypes.data_as(_pi), lay.ctypes.data_as(_pd), m.ctypes.data_as(_pi) if m is not None else None),
+        'odw_coating_check')
 
 
 def fresnel_reflectance(n1, n2, cos_i):

@@ -282,6 +282,87 @@ inline int fresnel_validate(int n_groups, const int32_t* mode, const int32_t* gr
   return ODW_OK;
 }
 
+// ---- Thin-film coatings on lens groups -----------------------------------------------------------
+// The unpolarised reflectance of a surface between n1 and n2 that carries a stack of k non-absorbing layers
+// (layers: (index, thickness_nm) each, listed from the group's outside inwards; entering: the ray meets them in that
+// order, else in reverse), cos_i and cos_t as for fresnel_reflectance, at wavelength_nm.  Characteristic matrices: all
+// indices are real, so every layer matrix and every product is [[a, i b], [i c, d]] with real a, b, c, d -- four real
+// recurrences per polarisation; sin, cos of the phase and the cosine in the layer are shared by both.  The p admittances
+// of the two media (n / cos) enter R multiplied by cos_i cos_t: no division at grazing incidence.  A layer that would
+// hold an evanescent wave: the bare reflectance (frustrated total reflection is not built).  The device twin
+// (odw_kernels.hip: coated_reflectance_dev) writes the same expressions.
+inline double coated_reflectance(double n1, double n2, double cos_i, double cos_t, bool entering, int k, const double* layers,
+                                 double wavelength_nm) {
+  if (k <= 0) return fresnel_reflectance(n1, n2, cos_i, cos_t);      // (no stack: the bare surface, bit for bit)
+  const double s2 = n1 * n1 * (1.0 - cos_i * cos_i);
+  const double w = 6.283185307179586 / wavelength_nm;
+  double as = 1.0, bs = 0.0, cs = 0.0, ds = 1.0, ap = 1.0, bp = 0.0, cp = 0.0, dp = 1.0;
+  for (int i = 0; i < k; ++i) {
+    const int j = entering ? i : k - 1 - i;
+    const double nj = layers[2 * j], dj = layers[2 * j + 1];
+    const double q = 1.0 - s2 / (nj * nj);
+    if (!(q > 0)) return fresnel_reflectance(n1, n2, cos_i, cos_t);
+    const double cj = std::sqrt(q);
+    const double delta = w * nj * dj * cj;
+    const double sd = std::sin(delta), cd = std::cos(delta);
+    const double es = nj * cj, ep = nj / cj;
+    const double us = sd / es, vs = es * sd, up = sd / ep, vp = ep * sd;
+    const double as1 = as * cd - bs * vs, bs1 = as * us + bs * cd, cs1 = cs * cd + ds * vs, ds1 = ds * cd - cs * us;
+    const double ap1 = ap * cd - bp * vp, bp1 = ap * up + bp * cd, cp1 = cp * cd + dp * vp, dp1 = dp * cd - cp * up;
+    as = as1; bs = bs1; cs = cs1; ds = ds1;
+    ap = ap1; bp = bp1; cp = cp1; dp = dp1;
+  }
+  // s: eta = n cos.  p: eta = n / cos, both sides of the fraction times cos_i cos_t
+  const double e0 = n1 * cos_i, e1 = n2 * cos_t;
+  const double xs = e0 * as, ys = e1 * ds, zs = e0 * e1 * bs;
+  const double rs = ((xs - ys) * (xs - ys) + (zs - cs) * (zs - cs)) / ((xs + ys) * (xs + ys) + (zs + cs) * (zs + cs));
+  const double xp = n1 * cos_t * ap, yp = n2 * cos_i * dp, zp = n1 * n2 * bp, tp = cos_i * cos_t * cp;
+  const double rp = ((xp - yp) * (xp - yp) + (zp - tp) * (zp - tp)) / ((xp + yp) * (xp + yp) + (zp + tp) * (zp + tp));
+  return 0.5 * (rs + rp);
+}
+// ... from the incidence alone; 1 under total internal reflection
+inline double coated_reflectance(double n1, double n2, double cos_i, bool entering, int k, const double* layers, double wavelength_nm) {
+  const double mu = n1 / n2;
+  const double root = 1.0 - mu * mu * (1.0 - cos_i * cos_i);
+  if (root < 0) return 1.0;
+  return coated_reflectance(n1, n2, cos_i, std::sqrt(root), entering, k, layers, wavelength_nm);
+}
+
+// odw_set_coating's check of the stacks; mode (may be null: no modes at hand) adds the groups' Fresnel modes
+inline int coating_validate(int n_groups, const int32_t* n_layers, const double* layers, const int32_t* mode, std::string& err) {
+  if (n_groups < 0 || n_groups > ODW_MAX_GROUPS || (n_groups && !n_layers))
+    return refuse(err, ODW_ERR_INVALID, "odw_set_coating: bad argument");
+  for (int g = 0; g < n_groups; ++g) {
+    if (n_layers[g] == 0) continue;
+    char buf[200];
+    if (n_layers[g] < 0 || n_layers[g] > ODW_COAT_LAYERS) {
+      std::snprintf(buf, sizeof buf, "odw_set_coating: group %d: %d layers (a coating has at most %d)", g, (int)n_layers[g], ODW_COAT_LAYERS);
+      err = buf;
+      return ODW_ERR_INVALID;
+    }
+    if (!layers) return refuse(err, ODW_ERR_INVALID, "odw_set_coating: bad argument");
+    if (mode && mode[g] == ODW_FRESNEL_NONE) {
+      std::snprintf(buf, sizeof buf, "odw_set_coating: group %d: a coating on a group without a Fresnel mode", g);
+      err = buf;
+      return ODW_ERR_INVALID;
+    }
+    for (int j = 0; j < n_layers[g]; ++j) {
+      const double nj = layers[2 * (ODW_COAT_LAYERS * (size_t)g + j)], dj = layers[2 * (ODW_COAT_LAYERS * (size_t)g + j) + 1];
+      if (!std::isfinite(nj) || nj < 1.0) {
+        std::snprintf(buf, sizeof buf, "odw_set_coating: group %d: layer %d: index %g (finite and at least 1)", g, j, nj);
+        err = buf;
+        return ODW_ERR_INVALID;
+      }
+      if (!std::isfinite(dj) || dj < 0.0) {
+        std::snprintf(buf, sizeof buf, "odw_set_coating: group %d: layer %d: thickness %g nm (finite and not negative)", g, j, dj);
+        err = buf;
+        return ODW_ERR_INVALID;
+      }
+    }
+  }
+  return ODW_OK;
+}
+
 // host half of odw_upload_scene: validation and the host copies of every table.  hs is complete only where the
 // answer is ODW_OK
 int scene_host_tables(const odw_scene_desc* s, HostScene& hs, std::string& err) {
@@ -1329,6 +1410,7 @@ struct SpecLayout {
   std::vector<int> frame, par, box, der;            // per primitive (box, der: -1 = none)
   std::vector<int> box_of, box_shared;
   std::vector<int> dc;                              // spectral variant: per group, its six dispersion coefficients (-1: none); else empty
+  std::vector<int> cc, cn;                          // coated variant: per group, its (index, thickness) pairs (-1: none) and their number; else empty
   int words() const { return std::max(size, iso + 1); }     // the image as a kernel reads it: the doubles and the mask word
   bool fits(size_t params_bytes) const { return ((params_bytes + 7) & ~(size_t)7) + 8 + (size_t)words() * 8 <= kSpecArgBytes; }
 };
@@ -1344,7 +1426,9 @@ inline int spec_derived_count(int type) {
 
 // disp_kind (spectral variant of the compiled kernel): six coefficient words per dispersive group, behind everything
 // else -- the offsets of every other piece are those of the plain layout
-inline SpecLayout spec_image_layout(const HostScene& hs, const int32_t* disp_kind = nullptr) {
+// coat_n (coated variant of the FRESNEL kernel; never together with disp_kind): two words per layer of a coated group, in
+// the same place.  Null, or no layer anywhere: the plain layout
+inline SpecLayout spec_image_layout(const HostScene& hs, const int32_t* disp_kind = nullptr, const int32_t* coat_n = nullptr) {
   SpecLayout L;
   const int n = L.n = hs.n_prims, ng = L.ng = hs.n_groups;
   spec_box_sharing(hs, L.box_of, L.box_shared);
@@ -1370,6 +1454,15 @@ inline SpecLayout spec_image_layout(const HostScene& hs, const int32_t* disp_kin
     L.dc.assign(std::max(1, ng), -1);
     for (int g = 0; g < ng; ++g)
       if (disp_kind[g]) { L.dc[g] = at; at += ODW_DISP_COEFS; }
+  }
+  bool coated = false;
+  for (int g = 0; coat_n && !disp_kind && g < ng; ++g) coated |= coat_n[g] > 0;
+  if (coated) {
+    at += 1;
+    L.cc.assign(std::max(1, ng), -1);
+    L.cn.assign(std::max(1, ng), 0);
+    for (int g = 0; g < ng; ++g)
+      if (coat_n[g] > 0) { L.cc[g] = at; L.cn[g] = coat_n[g]; at += 2 * coat_n[g]; }
   }
   L.size = at;
   return L;
@@ -1404,14 +1497,18 @@ inline uint64_t spec_isolated_mask(const HostScene& hs) {
 // sequence of IEEE operations intersect_prim performs on the device for it (odw_kernels.hip, compiled with
 // -ffp-contract=on): std::fma where a product and a sum of ONE expression fuse there, plain operations elsewhere --
 // and nothing else fuses here.
+// coat: the context's table of layers, [group][ODW_COAT_LAYERS][2], for a layout with coated groups
 inline void spec_image_build(const HostScene& hs, const DeviceLimits& lim, const SpecLayout& L, double* img,
-                             const double* disp_coef = nullptr, bool whole = false) {
+                             const double* disp_coef = nullptr, bool whole = false, const double* coat = nullptr) {
 #pragma clang fp contract(off)
   const double tol = lim.dist_tol;
   std::fill(img, img + (whole ? L.words() : L.size), 0.0);
   if (disp_coef)
     for (int g = 0; g < (int)L.dc.size() && g < L.ng; ++g)
       if (L.dc[g] >= 0) std::memcpy(&img[L.dc[g]], disp_coef + ODW_DISP_COEFS * g, ODW_DISP_COEFS * sizeof(double));
+  if (coat)
+    for (int g = 0; g < (int)L.cc.size() && g < L.ng; ++g)
+      if (L.cc[g] >= 0) std::memcpy(&img[L.cc[g]], coat + 2 * ODW_COAT_LAYERS * (size_t)g, 2 * (size_t)L.cn[g] * sizeof(double));
   img[0] = tol;
   img[1] = lim.max_ray_length + tol;
   img[2] = 2.0 * tol;

@@ -216,6 +216,12 @@ struct odw_ctx {
   DevBuf d_fresnel_mode, fr_in, fr_out;
   hipFunction_t spec_fresnel_fn[2] = {nullptr, nullptr};  // the compiled kernel's variants for such launches: without / with the power plane
   bool spec_fresnel_failed = false;        // ... could not be built for this binding: they walk the tree
+  SpecLayout spec_fresnel_layout;          // ... and their value image (the plain one; with a coating set, + the layers)
+  // thin-film coatings of the groups (odw_set_coating): layers per group and their (index, thickness_nm) pairs
+  bool coat_on = false;
+  int32_t coat_n[ODW_MAX_GROUPS] = {};
+  double coat[ODW_MAX_GROUPS * ODW_COAT_LAYERS * 2] = {};
+  DevBuf d_coat_n, d_coat, coat_layers;
 
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -720,9 +726,15 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   std::memset(&chroma, 0, sizeof chroma);
   DeviceFresnel fresnel_arg;
   fresnel_arg.mode = (const int32_t*)ctx->d_fresnel_mode.p;
+  const bool coated = fresnel && ctx->coat_on;
+  DeviceCoat coat_arg;                     // the COAT kernels' argument: the modes and the stacks
+  coat_arg.mode = fresnel_arg.mode;
+  coat_arg.coat_n = coated ? (const int32_t*)ctx->d_coat_n.p : nullptr;
+  coat_arg.coat = coated ? (const double*)ctx->d_coat.p : nullptr;
   if (fresnel && !fresnel_compiled) {
     int rc;
     if (!fresnel_arg.mode) return fail(ctx, ODW_ERR_DEVICE, "Fresnel launch without its mode table");
+    if (coated && (!coat_arg.coat_n || !coat_arg.coat)) return fail(ctx, ODW_ERR_DEVICE, "coated launch without its layer tables");
     if (!P.scene.n_nodes && (rc = chroma_tree(ctx))) return rc;
   }
   TraceParams Pc;                          // the spectral launch's arguments: P, with the tree built for it where the scene has none
@@ -826,7 +838,7 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     if (rc) return rc;
   }
   if (fresnel_compiled) {
-    int rc = spec_launch(ctx, grid, ctx->spec_fresnel_fn[pw], false);
+    int rc = spec_launch(ctx, grid, ctx->spec_fresnel_fn[pw], false, nullptr, true);
     if (rc) return rc;
   } else if (fresnel) {
     Pc = P;
@@ -835,7 +847,10 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       Pc.scene.bvh_prims = (const int32_t*)ctx->chroma_prims.p;
       Pc.scene.n_nodes = ctx->chroma_n_nodes;
     }
-#define ODW_FRESNEL_LAUNCH(S, W, A, C) hipLaunchKernelGGL((odw_trace_fresnel_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, fresnel_arg)
+    // (a coating on some group: the COAT instantiations; without, the kernels of before)
+#define ODW_FRESNEL_LAUNCH(S, W, A, C) do { \
+      if (coated) hipLaunchKernelGGL((odw_trace_coat_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, coat_arg); \
+      else hipLaunchKernelGGL((odw_trace_fresnel_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, fresnel_arg); } while (0)
 #define ODW_FRESNEL_LAUNCH_C(S, W, A) do { if (spectral) ODW_FRESNEL_LAUNCH(S, W, A, true); else ODW_FRESNEL_LAUNCH(S, W, A, false); } while (0)
 #define ODW_FRESNEL_LAUNCH_A(S, W) do { if (asph) ODW_FRESNEL_LAUNCH_C(S, W, true); else ODW_FRESNEL_LAUNCH_C(S, W, false); } while (0)
     if (segments) { if (pw) ODW_FRESNEL_LAUNCH_A(true, true); else ODW_FRESNEL_LAUNCH_A(true, false); }
@@ -1075,7 +1090,7 @@ void odw_destroy(odw_ctx* ctx) {
                     &ctx->em_t_tab, &ctx->em_t_guide, &ctx->em_o, &ctx->em_d, &ctx->em_tri_nrm, &ctx->tri_nrm, &ctx->phi_guide, &ctx->asph})
     release(*b);
   for (DevBuf* b : {&ctx->d_disp_kind, &ctx->d_disp_coef, &ctx->spec_tab, &ctx->ray_wl, &ctx->wl_rays, &ctx->wl_out, &ctx->chroma_nodes,
-                    &ctx->chroma_prims, &ctx->d_fresnel_mode, &ctx->fr_in, &ctx->fr_out})
+                    &ctx->chroma_prims, &ctx->d_fresnel_mode, &ctx->fr_in, &ctx->fr_out, &ctx->d_coat_n, &ctx->d_coat, &ctx->coat_layers})
     release(*b);
   for (auto& sb : ctx->surf_bufs) { release(sb.phi_tab); release(sb.t_tab); release(sb.t_guide); }
   release(ctx->d_samplers);
@@ -1170,13 +1185,16 @@ int odw_upload_scene(odw_ctx* ctx, const odw_scene_desc* s) {
   // ... and Fresnel modes
   ctx->fresnel_on = ctx->fresnel_split = false;
   std::memset(ctx->fresnel_mode, 0, sizeof ctx->fresnel_mode);
+  // ... and coatings
+  ctx->coat_on = false;
+  std::memset(ctx->coat_n, 0, sizeof ctx->coat_n);
   return ODW_OK;
 }
 
 int odw_set_fresnel(odw_ctx* ctx, int32_t n_groups, const int32_t* mode) {
   if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_fresnel: null ctx");
   if (n_groups == 0) {
-    if (!ctx->fresnel_on) return ODW_OK;
+    if (!ctx->fresnel_on && !ctx->coat_on) return ODW_OK;
   } else {
     if (!ctx->have_scene) return fail(ctx, ODW_ERR_NO_SCENE, "odw_set_fresnel before odw_upload_scene");
     if (n_groups != ctx->hs.n_groups) return fail(ctx, ODW_ERR_INVALID, "odw_set_fresnel: n_groups is not the scene's");
@@ -1187,6 +1205,8 @@ int odw_set_fresnel(odw_ctx* ctx, int32_t n_groups, const int32_t* mode) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::memset(ctx->fresnel_mode, 0, sizeof ctx->fresnel_mode);
   ctx->fresnel_on = ctx->fresnel_split = false;
+  ctx->coat_on = false;                    // (a coating belongs to the modes it was set under: odw_set_coating follows)
+  std::memset(ctx->coat_n, 0, sizeof ctx->coat_n);
   for (int g = 0; g < n_groups; ++g) {
     ctx->fresnel_mode[g] = mode[g];
     ctx->fresnel_on |= mode[g] != ODW_FRESNEL_NONE;
@@ -1197,6 +1217,78 @@ int odw_set_fresnel(odw_ctx* ctx, int32_t n_groups, const int32_t* mode) {
   ctx->spec_fresnel_failed = false;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // a running launch may still read the old table
   return upload(ctx, ctx->d_fresnel_mode, ctx->fresnel_mode, sizeof ctx->fresnel_mode);
+}
+
+int odw_set_coating(odw_ctx* ctx, int32_t n_groups, const int32_t* n_layers, const double* layers) {
+  if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_coating: null ctx");
+  if (n_groups == 0) {
+    if (!ctx->coat_on) return ODW_OK;
+  } else {
+    if (!ctx->have_scene) return fail(ctx, ODW_ERR_NO_SCENE, "odw_set_coating before odw_upload_scene");
+    if (n_groups != ctx->hs.n_groups) return fail(ctx, ODW_ERR_INVALID, "odw_set_coating: n_groups is not the scene's");
+    std::string err;
+    const int rc = coating_validate(n_groups, n_layers, layers, ctx->fresnel_mode, err);
+    if (rc) return fail(ctx, rc, err);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::memset(ctx->coat_n, 0, sizeof ctx->coat_n);
+  std::memset(ctx->coat, 0, sizeof ctx->coat);
+  ctx->coat_on = false;
+  for (int g = 0; g < n_groups; ++g) {
+    ctx->coat_n[g] = n_layers[g];
+    ctx->coat_on |= n_layers[g] > 0;
+    for (int k = 0; k < 2 * n_layers[g]; ++k) ctx->coat[2 * ODW_COAT_LAYERS * (size_t)g + k] = layers[2 * ODW_COAT_LAYERS * (size_t)g + k];
+  }
+  // (the layer counts are part of the compiled FRESNEL variant's header, the layers of its image: bound again by the next
+  //  launch that needs it)
+  ctx->spec_fresnel_fn[0] = ctx->spec_fresnel_fn[1] = nullptr;
+  ctx->spec_fresnel_failed = false;
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));        // a running launch may still read the old tables
+  if (!ctx->coat_on) return ODW_OK;
+  const int rc = upload(ctx, ctx->d_coat_n, ctx->coat_n, sizeof ctx->coat_n);
+  return rc ? rc : upload(ctx, ctx->d_coat, ctx->coat, sizeof ctx->coat);
+}
+
+int odw_coating_check(int32_t n_groups, const int32_t* n_layers, const double* layers, const int32_t* mode) {
+  std::string err;
+  const int rc = coating_validate(n_groups, n_layers, layers, mode, err);
+  return rc ? fail(nullptr, rc, err) : ODW_OK;
+}
+
+int odw_coated_reflectance(odw_ctx* ctx, double n1, double n2, int32_t entering, int32_t n_layers, const double* layers,
+                           double wavelength_nm, uint64_t n, const double* cos_i, double* R, int32_t device) {
+  if ((n && (!cos_i || !R)) || (!ctx && device) || !(n1 > 0) || !(n2 > 0) || !std::isfinite(n1) || !std::isfinite(n2) ||
+      !(wavelength_nm > 0) || !std::isfinite(wavelength_nm))
+    return fail(ctx, ODW_ERR_INVALID, "odw_coated_reflectance: bad argument");
+  {
+    // (one group's stack: the mode is not asked about)
+    double row[2 * ODW_COAT_LAYERS] = {};
+    if (n_layers > 0 && n_layers <= ODW_COAT_LAYERS && layers) std::memcpy(row, layers, 2 * (size_t)n_layers * sizeof(double));
+    std::string err;
+    const int rc = coating_validate(1, &n_layers, n_layers > 0 && !layers ? nullptr : row, nullptr, err);
+    if (rc) return fail(ctx, rc, err);
+  }
+  if (!device) {
+    for (uint64_t i = 0; i < n; ++i) R[i] = coated_reflectance(n1, n2, cos_i[i], entering != 0, n_layers, layers, wavelength_nm);
+    return ODW_OK;
+  }
+  if (n == 0) return ODW_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  int rc;
+  if ((rc = ensure(ctx, ctx->fr_in, n * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, ctx->fr_out, n * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, ctx->coat_layers, 2 * ODW_COAT_LAYERS * sizeof(double)))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->fr_in.p, cos_i, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (n_layers > 0)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->coat_layers.p, layers, 2 * (size_t)n_layers * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, (uint64_t)ctx->n_cu * 16));
+  hipLaunchKernelGGL(odw_coating_kernel, dim3(grid), dim3(256), 0, ctx->stream, n1, n2, (int)(entering != 0), (int)n_layers,
+                     (const double*)ctx->coat_layers.p, wavelength_nm, (const double*)ctx->fr_in.p, n, (double*)ctx->fr_out.p);
+  HIPCHK(ctx, hipGetLastError());
+  HIPCHK(ctx, hipMemcpyAsync(R, ctx->fr_out.p, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return ODW_OK;
 }
 
 int odw_compiled_fresnel_info(odw_ctx* ctx, int32_t* bound) {
@@ -1239,19 +1331,23 @@ int odw_fresnel_reflectance(odw_ctx* ctx, double n1, double n2, uint64_t n, cons
   return ODW_OK;
 }
 
-int odw_compile_check_fresnel(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
-                              const int32_t* mode, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
-  if (!scene || !limits || !mode) return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check_fresnel: bad argument");
+namespace {
+// odw_compile_check_fresnel, and with n_layers odw_compile_check_coating
+int compile_check_fresnel(const char* who, const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                          const int32_t* mode, const int32_t* n_layers, const double* layers, char* header_out, uint64_t header_capacity,
+                          uint64_t* code_bytes) {
+  if (!scene || !limits || !mode) return fail(nullptr, ODW_ERR_INVALID, std::string(who) + ": bad argument");
   HostScene tmp;
   std::string refusal;
   int rc = scene_host_tables(scene, tmp, refusal);
   if (rc) return fail(nullptr, rc, refusal);
   if ((rc = fresnel_validate(tmp.n_groups, mode, tmp.group_i32.data(), refusal))) return fail(nullptr, rc, refusal);
+  if (n_layers && (rc = coating_validate(tmp.n_groups, n_layers, layers, mode, refusal))) return fail(nullptr, rc, refusal);
   std::vector<Box> boxes;
   compute_boxes(tmp, limits->dist_tol, boxes);
   const std::string why = spec_ineligible(tmp);
-  if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_compile_check_fresnel: " + why);
-  const std::string text = spec_text(tmp, 0, nullptr, mode) +
+  if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, std::string(who) + ": " + why);
+  const std::string text = spec_text(tmp, 0, nullptr, mode, n_layers) +
       (source ? spec_source_text(spec_source_key(source->xform, source->n_t_rows, true, std::isfinite(source->focal_length))) : "");
   if (header_out && header_capacity) {
     const size_t k = std::min<size_t>(text.size(), (size_t)header_capacity - 1);
@@ -1263,6 +1359,21 @@ int odw_compile_check_fresnel(const odw_scene_desc* scene, const odw_limits* lim
   if (!spec_compile(text, arch && *arch ? arch : "gfx950", code, err)) return fail(nullptr, ODW_ERR_DEVICE, err);
   if (code_bytes) *code_bytes = code.size();
   return ODW_OK;
+}
+}  // namespace
+
+int odw_compile_check_fresnel(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                              const int32_t* mode, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
+  return compile_check_fresnel("odw_compile_check_fresnel", scene, limits, arch, source, mode, nullptr, nullptr, header_out, header_capacity,
+                               code_bytes);
+}
+
+int odw_compile_check_coating(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                              const int32_t* mode, const int32_t* n_layers, const double* layers, char* header_out,
+                              uint64_t header_capacity, uint64_t* code_bytes) {
+  if (!n_layers) return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check_coating: bad argument");
+  return compile_check_fresnel("odw_compile_check_coating", scene, limits, arch, source, mode, n_layers, layers, header_out, header_capacity,
+                               code_bytes);
 }
 
 int odw_set_dispersion(odw_ctx* ctx, int32_t n_groups, const int32_t* kind, const double* coef) {

@@ -262,4 +262,12 @@ struct DeviceFresnel {
   const int32_t* mode;          // [ODW_MAX_GROUPS] ODW_FRESNEL_* of every group
 };
 
+// ... of the COAT instantiations (launches with a thin-film coating on some group, odw_set_coating): DeviceFresnel and the
+// groups' stacks.  The FRESNEL kernels without COAT keep the argument -- and with it the argument segment -- they had.  A
+// compiled kernel has the counts in its header (Spec::coat(G)) and the values in its image (Spec::cc(G)).
+struct DeviceCoat : DeviceFresnel {
+  const int32_t* coat_n;        // [ODW_MAX_GROUPS] layers of every group
+  const double* coat;           // [ODW_MAX_GROUPS * ODW_COAT_LAYERS * 2] (index, thickness_nm), from the outside inwards
+};
+
 }  // namespace odw

@@ -1678,6 +1678,41 @@ __device__ __forceinline__ double fresnel_reflectance_dev(double n1, double n2, 
   return 0.5 * (rs * rs + rp * rp);
 }
 
+// The unpolarised reflectance of a surface that carries a thin-film stack: the device twin of coated_reflectance
+// (odw_build.h), the same expressions -- k layers (index, thickness_nm) listed from the group's outside inwards, met in
+// that order when entering.  A layer that would hold an evanescent wave: the bare reflectance.  k is a constant where the
+// scene is compiled in (Spec::coat(G)): the loop unrolls and the reversal folds.
+__device__ __forceinline__ double coated_reflectance_dev(double n1, double n2, double cos_i, double cos_t, bool entering, int k,
+                                                         cf64 layers, double wavelength_nm) {
+  if (k <= 0) return fresnel_reflectance_dev(n1, n2, cos_i, cos_t);      // (no stack: the bare surface, bit for bit)
+  const double s2 = n1 * n1 * (1.0 - cos_i * cos_i);
+  const double w = 6.283185307179586 / wavelength_nm;
+  double as = 1.0, bs = 0.0, cs = 0.0, ds = 1.0, ap = 1.0, bp = 0.0, cp = 0.0, dp = 1.0;
+  for (int i = 0; i < k; ++i) {
+    const int j = entering ? i : k - 1 - i;
+    const double nj = layers[2 * j], dj = layers[2 * j + 1];
+    const double q = 1.0 - s2 / (nj * nj);
+    if (!(q > 0)) return fresnel_reflectance_dev(n1, n2, cos_i, cos_t);
+    const double cj = fsqrt(q);
+    const double delta = w * nj * dj * cj;
+    double sd, cd;
+    sincos(delta, &sd, &cd);
+    const double es = nj * cj, ep = nj / cj;
+    const double us = sd / es, vs = es * sd, up = sd / ep, vp = ep * sd;
+    const double as1 = as * cd - bs * vs, bs1 = as * us + bs * cd, cs1 = cs * cd + ds * vs, ds1 = ds * cd - cs * us;
+    const double ap1 = ap * cd - bp * vp, bp1 = ap * up + bp * cd, cp1 = cp * cd + dp * vp, dp1 = dp * cd - cp * up;
+    as = as1; bs = bs1; cs = cs1; ds = ds1;
+    ap = ap1; bp = bp1; cp = cp1; dp = dp1;
+  }
+  // s: eta = n cos.  p: eta = n / cos, both sides of the fraction times cos_i cos_t
+  const double e0 = n1 * cos_i, e1 = n2 * cos_t;
+  const double xs = e0 * as, ys = e1 * ds, zs = e0 * e1 * bs;
+  const double rs = ((xs - ys) * (xs - ys) + (zs - cs) * (zs - cs)) / ((xs + ys) * (xs + ys) + (zs + cs) * (zs + cs));
+  const double xp = n1 * cos_t * ap, yp = n2 * cos_i * dp, zp = n1 * n2 * bp, tp = cos_i * cos_t * cp;
+  const double rp = ((xp - yp) * (xp - yp) + (zp - tp) * (zp - tp)) / ((xp + yp) * (xp + yp) + (zp + tp) * (zp + tp));
+  return 0.5 * (rs + rp);
+}
+
 // the uniform that decides reflect-or-transmit at interaction `ordinal` of ray `ray` under 'Split'
 __device__ __forceinline__ double fresnel_uniform(uint64_t ray, uint64_t seed, uint32_t ordinal) {
   uint32_t c0 = (uint32_t)ray, c1 = (uint32_t)(ray >> 32), c2 = ordinal, c3 = ODW_STREAM_FRESNEL;
@@ -2153,12 +2188,17 @@ __device__ __forceinline__ double group_index(cf64 group_f64, int g, const Devic
 // FRESNEL (launches with a Fresnel mode on some lens group): fmode is the hit group's ODW_FRESNEL_* -- a constant where the
 // scene is compiled in, so a group without a mode keeps the code it has; 'Loss' takes 1 - R off the power, 'Split' reflects
 // the ray with probability R (fresnel_uniform) and leaves medium and sequence as they were.
-template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec, bool CHROMA = false, bool FRESNEL = false>
+// COAT (FRESNEL launches with a thin-film coating on some group): ncoat layers at coat for the hit group -- the count a
+// constant where the scene is compiled in; with layers, R is the stack's (coated_reflectance_dev) at the launch's wavelength
+// or the ray's; without, and in every instantiation without COAT, the bare one as before.
+template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec, bool CHROMA = false, bool FRESNEL = false,
+          bool COAT = false>
 __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, ci32 group_i32, cf64 group_gdir, int g,
                                          int gtype, bool record, d3 n, bool entering, uint64_t ray, int nint,
                                          uint32_t* cnt, uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power,
                                          int& medium, int& seq, bool& alive, const DeviceChroma* C = nullptr, double wl = 0.0,
-                                         int fmode = ODW_FRESNEL_NONE) {
+                                         int fmode = ODW_FRESNEL_NONE, int ncoat = 0, cf64 coat = nullptr) {
+  static_assert(!COAT || FRESNEL, "coatings: launches with a Fresnel mode");
   if (record) {
     cnt[ODW_CNT_RECORDED_HITS * 256] += 1u;
     // (block reservations and the histogram window only in the flat kernels: in the BVH kernels
@@ -2194,7 +2234,10 @@ __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, c
       const d3 ideal = snells_law(dir, n1, n2, n, tir, d, cos_t);
       bool reflected = false;
       if (fmode != ODW_FRESNEL_NONE && !tir) {
-        const double R = fresnel_reflectance_dev(n1, n2, d, cos_t);
+        double R;
+        if constexpr (COAT) R = ncoat > 0 ? coated_reflectance_dev(n1, n2, d, cos_t, entering, ncoat, coat, CHROMA ? wl : P.wavelength)
+                                          : fresnel_reflectance_dev(n1, n2, d, cos_t);
+        else R = fresnel_reflectance_dev(n1, n2, d, cos_t);
         if (fmode == ODW_FRESNEL_LOSS) power *= 1.0 - R;      // (the hit is recorded: its row holds the power before the surface)
         else reflected = fresnel_uniform(ray, P.seed, (uint32_t)nint) < R;
       }
@@ -2257,9 +2300,22 @@ constexpr int spec_fresnel(int g) {
   else return ODW_FRESNEL_NONE;
 }
 
+// the layers of group g's coating in the header of a scene compiled for such launches (Spec::coat(G)), and where the value
+// image holds them (Spec::cc(G)); none elsewhere
+template <class SPEC, bool COAT>
+constexpr int spec_coat(int g) {
+  if constexpr (COAT && SPEC::enabled) return SPEC::coat(g);
+  else return 0;
+}
+template <class SPEC, bool COAT>
+constexpr int spec_coat_at(int g) {
+  if constexpr (COAT && SPEC::enabled) return SPEC::coat(g) > 0 ? SPEC::cc(g) : 0;
+  else return 0;
+}
+
 // the hit is on primitive PI of a compiled scene: its type, frame pattern, flags, group and the group's
 // optical type / recording switch are constants
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, int PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, bool COAT, int PI>
 __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                          cf64 group_gdir, int face, uint64_t ray, int nint, uint32_t* cnt,
                                          uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
@@ -2282,8 +2338,11 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   if (entering) n = n * -1.0;
   // (FRESNEL: the group's mode from the header -- a group without one folds to the code of before)
   constexpr int fmode = spec_fresnel<SPEC, FRESNEL>(g);
-  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
-                               nint, cnt, hit_state, win, point, dir, power, medium, seq, alive, C, wl, fmode);
+  // (COAT: the group's layer count from the header, its layers from the image -- a group without layers folds likewise)
+  constexpr int ncoat = spec_coat<SPEC, COAT>(g);
+  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
+                               nint, cnt, hit_state, win, point, dir, power, medium, seq, alive, C, wl, fmode, ncoat,
+                               sv.img + spec_coat_at<SPEC, COAT>(g));
   // n points along the incoming travel direction: out of the solid when leaving it, into it when entering
   const double out = entering ? -dot(dir, n) : dot(dir, n);
   if constexpr ((flags & ODW_FLAG_CONVEX) != 0) skip = out > 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
@@ -2294,12 +2353,12 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   if constexpr (spec_cand_solid<SPEC>(flags >> ODW_SOLID_SHIFT)) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else only = -1;
 }
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, int... PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, bool COAT, int... PI>
 __device__ __forceinline__ void spec_hits(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                           cf64 group_gdir, int prim, int face, uint64_t ray, int nint, uint32_t* cnt,
                                           uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
                                           int& skip, int& only, bool& alive, const DeviceChroma* C, double wl, IndexList<int, PI...>) {
-  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
+  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
                                                   point, dir, power, medium, seq, skip, only, alive, C, wl), true)
                      : false) || ...);
 }
@@ -2366,8 +2425,10 @@ template <> struct HitBlockState<false> {
 //   explicit array or the spectrum draw (DeviceChroma), handed to interact()
 // FRESNEL (binary tree, or a kernel compiled for it): launches with a Fresnel mode on some lens group -- the hit group's mode
 //   from DeviceFresnel (tree) or the header (compiled), handed to interact()
+// COAT (with FRESNEL): launches with a thin-film coating on some group -- the hit group's layers from DeviceCoat (tree) or
+//   header and value image (compiled), handed to interact()
 template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false,
-          class SRC = NoSource, bool ASPH = false, bool CHROMA = false, bool FRESNEL = false>
+          class SRC = NoSource, bool ASPH = false, bool CHROMA = false, bool FRESNEL = false, bool COAT = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChroma* C = nullptr, const DeviceFresnel* F = nullptr) {
   static_assert(!ASPH || BVH, "aspheres: the binary tree (or a compiled kernel, which knows its scene from Spec::rare())");
   static_assert(!CHROMA || ((BVH || SPEC::enabled) && !STOCH && !BATCH), "spectral launches: the binary tree or a kernel compiled for them, no stochastic surfaces, no batches");
@@ -2585,7 +2646,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
       uint32_t* cnt = cnt_lds + threadIdx.x;
       uint32_t* hit_state = hit_lds + (threadIdx.x >> 6) * 4;
       if constexpr (SPEC::enabled) {
-        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
+        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
                               hist_win, point, dir, power, medium, seq, skip, only, alive, C, wl, __make_integer_seq<IndexList, int, SPEC::N>{});
       } else {
       cf64 pf = sv.prim_f64 + (size_t)prim * 16;
@@ -2607,8 +2668,16 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
       const int g = pi[1];
       int fmode = ODW_FRESNEL_NONE;
       if constexpr (FRESNEL) fmode = F->mode[g];
-      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA, FRESNEL>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
-                                 entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive, C, wl, fmode);
+      int ncoat = 0;
+      cf64 coat = nullptr;
+      if constexpr (COAT) {               // (the COAT kernels' argument is a DeviceCoat)
+        const DeviceCoat* FC = static_cast<const DeviceCoat*>(F);
+        ncoat = FC->coat_n[g];
+        coat = as_const(FC->coat) + 2 * ODW_COAT_LAYERS * g;
+      }
+      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA, FRESNEL, COAT>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
+                                 entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive, C, wl, fmode,
+                                 ncoat, coat);
       // outward normal of the solid = n against the travel direction when entering; for a facet of a convex
       // tessellated solid the FACET's own normal decides (the interpolated one of smooth shading can point out of
       // the solid where the ray still runs into it)
@@ -2689,6 +2758,26 @@ __global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_fresnel
   trace_body<true, false, SEG, false, NoSpec, false, POWER, NoSource, ASPH, CHROMA, true>(P, &C, &F);
 }
 
+// ... with a thin-film coating on some group (odw_set_coating): the same with COAT, layer counts and layers in DeviceCoat
+template <bool SEG, bool POWER, bool ASPH, bool CHROMA>
+__global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_coat_kernel(const TraceParams P, const DeviceChroma C,
+                                                                                     const DeviceCoat F) {
+  trace_body<true, false, SEG, false, NoSpec, false, POWER, NoSource, ASPH, CHROMA, true, true>(P, &C, &F);
+}
+
+// R of a coated surface n1 -> n2 at n cosines of incidence (odw_coated_reflectance, device): the ray loop's own evaluation
+__global__ __launch_bounds__(256) void odw_coating_kernel(double n1, double n2, int entering, int k, const double* __restrict__ layers,
+                                                          double wavelength_nm, const double* __restrict__ cos_i, uint64_t n,
+                                                          double* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const double d = cos_i[i];
+    const double mu = n1 * frcp(n2);
+    const double root = 1.0 - mu * mu * (1.0 - d * d);
+    out[i] = root < 0 ? 1.0 : coated_reflectance_dev(n1, n2, d, fsqrt(root), entering != 0, k, as_const(layers), wavelength_nm);
+  }
+}
+
 // R of a surface n1 -> n2 at n cosines of incidence (odw_fresnel_reflectance, device): the ray loop's own evaluation,
 // mu, root and cos_t as snells_law has them
 __global__ __launch_bounds__(256) void odw_fresnel_kernel(double n1, double n2, const double* __restrict__ cos_i, uint64_t n,
@@ -2736,6 +2825,9 @@ __global__ __launch_bounds__(256) void odw_disp_index_kernel(int kind, const Dis
 #ifndef ODW_SPEC_POWER
 #define ODW_SPEC_POWER false
 #endif
+#ifndef ODW_SPEC_COAT              // the FRESNEL variant's header of a scene with a coated group (Spec::coat(G), Spec::cc(G))
+#define ODW_SPEC_COAT false
+#endif
 #ifndef ODW_SPEC_SOURCE            // the header carries `struct SpecSource` and names it here when a source is bound
 #define ODW_SPEC_SOURCE NoSource
 #endif
@@ -2761,7 +2853,7 @@ extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kerne
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(
     const TraceParams P, const SpecTail<Spec::img_fits ? Spec::IMG : 4> T) {
   (void)T;
-  trace_body<false, false, false, ODW_SPEC_LEAN, Spec, false, ODW_SPEC_POWER, ODW_SPEC_SOURCE, false, false, true>(P);
+  trace_body<false, false, false, ODW_SPEC_LEAN, Spec, false, ODW_SPEC_POWER, ODW_SPEC_SOURCE, false, false, true, ODW_SPEC_COAT>(P);
 }
 #else
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(

@@ -154,7 +154,11 @@ std::string spec_source_text(uint64_t key) {
 // text, so part of the cache key.  Null: the text of before, byte for byte.
 // fresnel: the header of the variant for launches with a Fresnel mode set -- every group's mode as a constexpr
 // Spec::fresnel(G) and ODW_SPEC_FRESNEL; part of the text likewise.  Null, or every mode 0: the text of before, byte for byte.
-std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_kind = nullptr, const int32_t* fresnel = nullptr) {
+// coat_n (with fresnel): the layers of every group's thin-film coating -- the count is structure, a constexpr Spec::coat(G);
+// the (index, thickness) pairs are values, in the (longer) value image at Spec::cc(G); and ODW_SPEC_COAT.  Null, or no layer
+// anywhere: the FRESNEL text of before, byte for byte.
+std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_kind = nullptr, const int32_t* fresnel = nullptr,
+                      const int32_t* coat_n = nullptr) {
   const int n = hs.n_prims, ng = hs.n_groups;
   std::vector<int> type(n), group(n), flags(n), condw(n), dead(n);
   std::vector<unsigned long long> xf(n);
@@ -169,7 +173,9 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
     xf[p] = xf_pattern(&hs.prim_f64[16 * (size_t)p]);
   }
   // primitives with the same box, and where the kernel finds every value it reads (odw_build.h: the value image)
-  const SpecLayout L = spec_image_layout(hs, disp_kind);
+  bool any_fresnel = false;
+  for (int g = 0; fresnel && g < ng; ++g) any_fresnel |= fresnel[g] != 0;
+  const SpecLayout L = spec_image_layout(hs, disp_kind, any_fresnel ? coat_n : nullptr);
   const std::vector<int>&box_of = L.box_of, &box_shared = L.box_shared;
   std::vector<int> gtype(std::max(1, ng)), grec(std::max(1, ng));
   for (int g = 0; g < ng; ++g) { gtype[g] = hs.group_i32[4 * g]; grec[g] = hs.group_i32[4 * g + 1]; }
@@ -212,13 +218,13 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
     s += "  static constexpr bool chroma() { return true; }\n";
     s += table("int", "disp", ng, kinds.data(), fi) + table("int", "dc", ng, L.dc.data(), fi);
   }
-  bool any_fresnel = false;
-  for (int g = 0; fresnel && g < ng; ++g) any_fresnel |= fresnel[g] != 0;
   if (any_fresnel) {
     std::vector<int> modes(std::max(1, ng), 0);
     for (int g = 0; g < ng; ++g) modes[g] = fresnel[g];
     s += table("int", "fresnel", ng, modes.data(), fi);
   }
+  const bool any_coat = !L.cc.empty();
+  if (any_coat) s += table("int", "coat", ng, L.cn.data(), fi) + table("int", "cc", ng, L.cc.data(), fi);
   s += "  static constexpr int gf = " + std::to_string(L.gf) + ", gd = " + std::to_string(L.gd) + ", gi = " + std::to_string(L.gi) + ";\n";
   s += table("int", "frame", n, L.frame.data(), fi) + table("int", "par", n, L.par.data(), fi) +
        table("int", "box", n, L.box.data(), fi) + table("int", "der", n, L.der.data(), fi);
@@ -232,6 +238,7 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
   s += std::string("#define ODW_SPEC_STOCH ") + (n_samplers > 0 ? "true" : "false") + "\n";
   if (disp_kind) s += "#define ODW_SPEC_CHROMA true\n";
   if (any_fresnel) s += "#define ODW_SPEC_FRESNEL true\n";
+  if (any_coat) s += "#define ODW_SPEC_COAT true\n";
   return s;
 }
 
@@ -393,6 +400,8 @@ void spec_wait_at_exit() {
 // on the binary tree).
 // variants kSpecFresnel / kSpecFresnelPower: the kernel of launches with a Fresnel mode set (the context's modes are part of
 // its header; arguments and value image are the plain kernel's) -> ctx->spec_fresnel_fn[0 / 1]; bound like the CHROMA ones.
+// With a coating set (odw_set_coating) the same two slots hold the COAT kernel: layer counts in the header, the image longer
+// by the layers (ctx->spec_fresnel_layout).
 enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2, kSpecChroma = 3, kSpecChromaPower = 4, kSpecFresnel = 5, kSpecFresnelPower = 6 };
 int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   const bool batch = variant != kSpecSingle;      // (a variant rides on the single-scene kernel's bookkeeping)
@@ -435,7 +444,9 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   const std::string arch = prop.gcnArchName;
   // (the BATCH variant takes its rays from the batch's buffer, odw_batch_rays_kernel: never compiled against a source)
   if (chroma) ctx->spec_chroma_layout = spec_image_layout(ctx->hs, ctx->disp_kind);
-  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr, fresnel ? ctx->fresnel_mode : nullptr) +
+  const int32_t* coat_n = fresnel && ctx->coat_on ? ctx->coat_n : nullptr;
+  if (fresnel) ctx->spec_fresnel_layout = spec_image_layout(ctx->hs, nullptr, coat_n);
+  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr, fresnel ? ctx->fresnel_mode : nullptr, coat_n) +
                            (variant == kSpecBatch ? "" : spec_source_text(ctx->spec_source_key)) +
                            (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n"
                                                   : (variant == kSpecPower || variant == kSpecChromaPower || variant == kSpecFresnelPower) ? "#define ODW_SPEC_POWER true\n" : "");
@@ -558,14 +569,16 @@ void spec_note_launch(odw_ctx* ctx, uint64_t n_rays) {
 // it differs from the one there; a batch's images lie in its blocks (odw_upload_scene_batch), one per scene.
 // chroma (the variant of spectral launches): the longer image with the groups' dispersion coefficients, and the
 // wavelength tables as a third argument behind the tail.
-int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const DeviceChroma* chroma = nullptr) {
-  const SpecLayout& L = chroma ? ctx->spec_chroma_layout : ctx->spec_layout;
+// fresnel (the variant of launches with a Fresnel mode set): its own layout -- the plain one, or with a coating set the
+// longer image with the groups' layers.
+int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const DeviceChroma* chroma = nullptr, bool fresnel = false) {
+  const SpecLayout& L = chroma ? ctx->spec_chroma_layout : fresnel ? ctx->spec_fresnel_layout : ctx->spec_layout;
   if (L.n != ctx->hs.n_prims || L.size < kSpecImageLimits) return fail(ctx, ODW_ERR_DEVICE, "compiled kernel without its value image");
   constexpr size_t tail = (sizeof(TraceParams) + 7) & ~(size_t)7;
   const bool resident = !batch && L.fits(sizeof(TraceParams) + (chroma ? sizeof(DeviceChroma) : 0));
   std::vector<double>& img = ctx->spec_image_now;
   img.resize((size_t)L.words());
-  spec_image_build(ctx->hs, ctx->P.lim, L, img.data(), chroma ? ctx->disp_coef : nullptr, true);
+  spec_image_build(ctx->hs, ctx->P.lim, L, img.data(), chroma ? ctx->disp_coef : nullptr, true, fresnel && ctx->coat_on ? ctx->coat : nullptr);
   const double* dev = nullptr;
   if (batch) {
     if (!ctx->batch_img_off) return fail(ctx, ODW_ERR_DEVICE, "batch without value images");

@@ -23,13 +23,27 @@ _GROUP_DEFAULTS = dict(
     Dispersion='', DispersionCoefficients=[],
     # Fresnel reflection at a lens group's surfaces (not in the reference): '' -- the surface only bends the ray --,
     # 'Loss' (power *= 1 - R at every crossing) or 'Split' (reflected with probability R: ghost rays)
-    Fresnel='')
+    Fresnel='',
+    # thin-film coating of a lens group with a Fresnel mode (not in the reference): (index, thickness_nm) per layer, at most
+    # four, from the outside inwards -- the first touches the surroundings, the last the group's glass; on every face of the
+    # group; a flat list index, thickness, index, thickness, ... (as an FCStd file stores it) is read alike
+    Coating=[])
 
 # Fraunhofer lines the Abbe number is defined on (nm)
 LINE_F, LINE_d, LINE_C = 486.1327, 587.5618, 656.2725
 # Schott N-BK7 (Sellmeier; catalogue values)
 N_BK7 = dict(Dispersion='Sellmeier',
              DispersionCoefficients=[1.03961212, 0.231792344, 1.01046945, 0.00600069867, 0.0200179144, 103.560653])
+
+# magnesium fluoride, the classic single-layer antireflection coating (index near 550 nm)
+MGF2 = 1.38
+
+
+def quarterWave(index, wavelength_nm):
+  """the layer (index, thickness_nm) of optical thickness wavelength_nm / 4: on glass n it reflects
+  ((n - index^2) / (n + index^2))^2 of that wavelength at normal incidence"""
+  return (float(index), float(wavelength_nm) / (4.0 * float(index)))
+
 
 _RECORD_DEFAULT = dict(Mirror=False, Lens=False, Grating=False, Absorber=True, Vacuum=True)
 

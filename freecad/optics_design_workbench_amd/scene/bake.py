@@ -209,6 +209,7 @@ class BakedScene:
   group_disp_kind: np.ndarray = None                     # (G,) int32 dispersion of each group: 0 constant (group_ior), 1 Sellmeier, 2 Cauchy
   group_disp: np.ndarray = None                          # (G, 6) float64 its coefficients (Sellmeier B1 B2 B3 C1 C2 C3 / Cauchy A B C 0 0 0)
   group_fresnel: np.ndarray = None                       # (G,) int32 Fresnel mode of each group: 0 none, 1 'Loss', 2 'Split' (lenses only)
+  group_coating: np.ndarray = None                       # (G,) COATING_DTYPE thin-film coating of each group: n layers, (index, thickness_nm) each
 
   @property
   def n_prims(self):
@@ -320,6 +321,46 @@ def groupFresnel(groups, types):
   return mode
 
 
+COAT_LAYERS = 4                                              # ODW_COAT_LAYERS
+COATING_DTYPE = np.dtype([('n', np.int32), ('layers', np.float64, (COAT_LAYERS, 2))])
+
+
+def coatingLayers(value):
+  """the `Coating` property as a list of (index, thickness_nm): pairs, or the flat list an FCStd file stores"""
+  v = list(value) if value is not None else []
+  if v and np.ndim(v[0]) == 0:
+    if len(v) % 2:
+      raise ValueError(f'{len(v)} numbers: a flat list holds index, thickness_nm per layer')
+    v = [(v[k], v[k + 1]) for k in range(0, len(v), 2)]
+  return [(float(n), float(d)) for n, d in v]
+
+
+def groupCoating(groups, types, fresnel):
+  """group_coating COATING_DTYPE [G] from the groups' `Coating` ([(index, thickness_nm), ...] from the outside inwards).
+  ValueError naming the group: a coating on a group without a Fresnel mode, more than COAT_LAYERS layers, an index that is
+  not finite or below 1, a thickness that is not finite or negative."""
+  out = np.zeros(len(groups), dtype=COATING_DTYPE)
+  for gi, g in enumerate(groups):
+    try:
+      layers = coatingLayers(g._props.get('Coating'))
+    except (TypeError, ValueError) as e:
+      raise ValueError(f'{g.Name}: Coating: {e}') from None
+    if not layers:
+      continue
+    if not fresnel[gi]:
+      raise ValueError(f"{g.Name}: Coating on a group without a Fresnel mode ('Loss' or 'Split')")
+    if len(layers) > COAT_LAYERS:
+      raise ValueError(f'{g.Name}: Coating: {len(layers)} layers (at most {COAT_LAYERS})')
+    for j, (n, d) in enumerate(layers):
+      if not np.isfinite(n) or n < 1.0:
+        raise ValueError(f'{g.Name}: Coating: layer {j}: index {n:g} (finite and at least 1)')
+      if not np.isfinite(d) or d < 0.0:
+        raise ValueError(f'{g.Name}: Coating: layer {j}: thickness {d:g} nm (finite and not negative)')
+      out['layers'][gi, j] = n, d
+    out['n'][gi] = len(layers)
+  return out
+
+
 def bakeScene(doc, source=None, surfaceFamily=None):
   """flat tables for all optical groups of `doc` as seen by `source`"""
   groups = opticalObjects(doc)
@@ -428,9 +469,10 @@ def bakeScene(doc, source=None, surfaceFamily=None):
 
   disp_kind, disp = groupDispersion(groups, types, gt)
   fresnel = groupFresnel(groups, types)
+  coating = groupCoating(groups, types, fresnel)
 
   return BakedScene(
-      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef, group_disp_kind=disp_kind, group_disp=disp, group_fresnel=fresnel,
+      tri_normals=tri_normals, tri_edges=tri_edges, prim_coef=prim_coef, group_disp_kind=disp_kind, group_disp=disp, group_fresnel=fresnel, group_coating=coating,
       prim_type=np.concatenate([np.array([p.kind for p in prims], dtype=np.int32),
                                 np.full(n_tri, geometry.TRIANGLE, dtype=np.int32)]),
       prim_group=np.concatenate([np.array(prim_group, dtype=np.int32), tri_group]),

@@ -106,8 +106,8 @@ def _parse_property(prop, zf):
   if tag == 'Path':
     return child.attrib.get('value', '')
   if tag == 'FloatList':
-    # App::PropertyFloatList (DispersionCoefficients of a group; Spectrum of a point source as wavelength, weight,
-    # wavelength, weight, ...): a member of the zip, a uint32 count and that many float64
+    # App::PropertyFloatList (DispersionCoefficients of a group; its Coating as index, thickness, index, thickness, ...;
+    # Spectrum of a point source as wavelength, weight, wavelength, weight, ...): a member of the zip, a uint32 count and that many float64
     fname = child.attrib.get('file')
     if not fname or zf is None or fname not in zf.namelist():
       return []
@@ -200,7 +200,7 @@ _PROXY_PROPERTIES = {
       'OpticalType RefractiveIndex ReflectedProbabilityDensity RefractedProbabilityDensity PowerThetaDomain '
       'PowerPhiDomain RayModificationProbabilityDensity ModifyThetaDomain ModifyPhiDomain Reflectivity '
       'AbsorptionLength GratingType GratingLinesPerMillimeter GratingLinesOrientation GratingDiffractionOrder '
-      'RecordHits Dispersion DispersionCoefficients Fresnel').split(),
+      'RecordHits Dispersion DispersionCoefficients Fresnel Coating').split(),
   ('freecad.optics_design_workbench.freecad_elements.point_source', 'PointSourceProxy'): (
       'PowerDensity Wavelength FocalLength Divergence ThetaDomain PhiDomain RadiusDomain RandomNumberGeneratorMode '
       'ThetaResolutionNumericMode RadiusResolutionNumericMode PhiResolutionNumericMode Fans FanPhi0 RaysPerFan '
@@ -223,10 +223,10 @@ _PROXY_PROPERTIES = {
 }
 
 
-# properties this project adds to the reference's tables (dispersive glasses, polychromatic sources, Fresnel modes): documents written
+# properties this project adds to the reference's tables (dispersive glasses, polychromatic sources, Fresnel modes, coatings): documents written
 # by the reference's workbench do not carry them, so they count neither for nor against a proxy in repairProxies --
 # which documents get their proxy back is what it was
-_OPTIONAL_PROPERTIES = frozenset('Dispersion DispersionCoefficients Fresnel Spectrum SpectralDensity SpectrumDomain SpectrumResolution'.split())
+_OPTIONAL_PROPERTIES = frozenset('Dispersion DispersionCoefficients Fresnel Coating Spectrum SpectralDensity SpectrumDomain SpectrumResolution'.split())
 
 
 def repairProxies(doc):

@@ -191,6 +191,39 @@ class Tracer:
     mode = getattr(scene, 'group_fresnel', None)
     if mode is not None and np.any(np.asarray(mode) != 0):
       self.setFresnel(mode)
+    # (... and its coatings, which belong to the modes)
+    coating = getattr(scene, 'group_coating', None)
+    if coating is not None and np.any(_native.coating_tables(coating)[0] != 0):
+      self.setCoating(coating)
+
+  def setCoating(self, coating):
+    """Thin-film coatings of the uploaded scene's groups (`odw_set_coating`), after setFresnel: one list of (index,
+    thickness_nm) per group, from the outside inwards, at most four layers (or the bake's group_coating).  Groups with a
+    Fresnel mode only.  The stack's reflectance takes the bare one's place at every face of the group.  None or an empty
+    list clears it, and so do setFresnel and setScene."""
+    pi, pd = C.POINTER(C.c_int32), C.POINTER(C.c_double)
+    f = self._lib.odw_set_coating
+    f.argtypes = [C.c_void_p, C.c_int32, pi, pd]
+    if coating is None or len(coating) == 0:
+      self._chk(f(self._ctx, 0, None, None), 'odw_set_coating')
+      return
+    cnt, lay = _native.coating_tables(coating)
+    self._chk(f(self._ctx, len(cnt), cnt.ctypes.data_as(pi), lay.ctypes.data_as(pd)), 'odw_set_coating')
+
+  def coatedReflectance(self, n1, n2, cos_i, layers, wavelength_nm, entering=True, device=False):
+    """unpolarised reflectance of a surface from index n1 to n2 under the stack `layers` ((index, thickness_nm) from the
+    outside inwards; entering: the ray meets them in that order) at the cosines of incidence cos_i and wavelength_nm
+    (`odw_coated_reflectance`); device=True: evaluated by the kernel-side function"""
+    c = np.ascontiguousarray(cos_i, dtype=np.float64).reshape(-1)
+    lay = np.ascontiguousarray(layers, dtype=np.float64).reshape(-1, 2) if len(layers) else np.zeros((0, 2))
+    out = np.empty(len(c), np.float64)
+    pd = C.POINTER(C.c_double)
+    f = self._lib.odw_coated_reflectance
+    f.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_int32, C.c_int32, pd, C.c_double, C.c_uint64, pd, pd, C.c_int32]
+    self._chk(f(self._ctx, float(n1), float(n2), 1 if entering else 0, len(lay), lay.ctypes.data_as(pd) if len(lay) else None,
+                float(wavelength_nm), len(c), c.ctypes.data_as(pd), out.ctypes.data_as(pd), 1 if device else 0),
+              'odw_coated_reflectance')
+    return out
 
   def setFresnel(self, mode):
     """Fresnel modes of the uploaded scene's groups (`odw_set_fresnel`): mode [G] of 0 / '' (none), 1 / 'Loss'
@@ -435,6 +468,8 @@ class Tracer:
         raise _native.NativeError('setSceneBatch: unsupported: scenes with stochastic surfaces are traced one by one')
       if getattr(sc, 'group_fresnel', None) is not None and np.any(np.asarray(sc.group_fresnel) != 0):
         raise _native.NativeError('setSceneBatch: unsupported: scenes with a Fresnel mode are traced one by one')
+      if getattr(sc, 'group_coating', None) is not None and np.any(_native.coating_tables(sc.group_coating)[0] != 0):
+        raise _native.NativeError('setSceneBatch: unsupported: scenes with a coating are traced one by one')
       d, keep = _native.scene_desc(sc)
       descs.append(d)
       keeps.append(keep)

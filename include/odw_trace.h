@@ -573,6 +573,42 @@ int odw_compile_check_fresnel(const odw_scene_desc* scene, const odw_limits* lim
                               uint64_t header_capacity, uint64_t* code_bytes);
 /* test support, no device needed: odw_set_fresnel's validation (group_type [n_groups] ODW_OPT_*, or NULL)      */
 int odw_fresnel_check(int32_t n_groups, const int32_t* mode, const int32_t* group_type);
+/* ---- Thin-film coatings on lens groups (entry points more, no descriptor changed: still v12) ----
+ * A lens group with a Fresnel mode may carry a stack of up to ODW_COAT_LAYERS homogeneous layers, real indices, no
+ * dispersion: (index, thickness_nm) each, listed from the outside inwards (the first touches the surroundings, the
+ * last the group's glass); every face of the group carries the stack.  At a crossing that is not totally reflected
+ * the stack's unpolarised reflectance takes the place of the bare R above; everything else ('Loss', 'Split', the
+ * draw, total reflection, AbsorptionLength) is as there.  Characteristic matrices: with s2 = n1^2 (1 - cos_i^2),
+ * the layers in the order the ray meets them (listed order when entering, reversed when leaving), for layer j
+ *   cos_j = sqrt(1 - s2 / n_j^2), delta_j = 2 pi n_j d_j cos_j / lambda, eta_j = n_j cos_j (s), n_j / cos_j (p);
+ * the product of the layer matrices [[cos delta, i sin delta / eta], [i eta sin delta, cos delta]] is
+ * [[a, i b], [i c, d]] with real a, b, c, d, and with eta_0, eta_s those of the two media
+ *   R_pol = ((eta_0 a - eta_s d)^2 + (eta_0 eta_s b - c)^2) / ((eta_0 a + eta_s d)^2 + (eta_0 eta_s b + c)^2),
+ * R = (R_s + R_p) / 2 (R_p with numerator and denominator multiplied by cos_i cos_t: no division at grazing
+ * incidence).  lambda: the launch's wavelength; the ray's own in a spectral launch.
+ * A crossing at which some layer would hold an evanescent wave (s2 >= n_j^2) although the surface does not reflect
+ * totally takes the bare R: frustrated total reflection is not built.
+ * n_layers [n_groups], layers [n_groups * ODW_COAT_LAYERS * 2] (index, thickness_nm; rows beyond a group's count are
+ * ignored) for the uploaded scene's groups, after odw_set_fresnel; n_groups = 0 clears it, and so do
+ * odw_set_fresnel and odw_upload_scene.  ODW_ERR_INVALID naming the group: a coating on a group without a Fresnel
+ * mode, more than ODW_COAT_LAYERS layers, an index that is not finite or below 1, a thickness that is not finite
+ * or negative.  Launches with a coating set run COAT instantiations of the Fresnel kernels: the compiled kernel's
+ * header carries the layer counts (constexpr Spec::coat(G), part of the cache key) and finds the values in the
+ * value image at Spec::cc(G); the binary tree reads both from tables.  Same rows on both routes, bit for bit.   */
+#define ODW_COAT_LAYERS 4
+int odw_set_coating(odw_ctx* ctx, int32_t n_groups, const int32_t* n_layers, const double* layers);
+/* test support, no device needed: odw_set_coating's validation (mode [n_groups] ODW_FRESNEL_*, or NULL)         */
+int odw_coating_check(int32_t n_groups, const int32_t* n_layers, const double* layers, const int32_t* mode);
+/* R[i] of a surface from index n1 to n2 under the stack layers [n_layers * 2] at cos_i[i] and wavelength_nm
+ * (1 beyond the critical angle); entering != 0: the ray comes from the stack's outside.  device as in
+ * odw_fresnel_reflectance.                                                                                      */
+int odw_coated_reflectance(odw_ctx* ctx, double n1, double n2, int32_t entering, int32_t n_layers, const double* layers,
+                           double wavelength_nm, uint64_t n, const double* cos_i, double* R, int32_t device);
+/* test support, no device needed: odw_compile_check_fresnel with a stack per group (no layers anywhere: that
+ * entry point's header, byte for byte); ODW_ERR_INVALID as odw_set_fresnel and odw_set_coating                  */
+int odw_compile_check_coating(const odw_scene_desc* scene, const odw_limits* limits, const char* arch,
+                              const odw_source_desc* source, const int32_t* mode, const int32_t* n_layers,
+                              const double* layers, char* header_out, uint64_t header_capacity, uint64_t* code_bytes);
 int odw_set_limits(odw_ctx* ctx, const odw_limits* limits);
 int odw_set_detector(odw_ctx* ctx, const odw_detector_desc* det);
 /* capacity of the device hit list in rows (0 frees it)                     */
