@@ -1191,7 +1191,26 @@ __device__ __forceinline__ void intersect_tri(const SceneView& sv, Query& q, int
     best = fmin(best, seg_dist2(w - e1, e2 - e1));
     if (best > tol * tol) return;
   }
-  consider(sv, q, dot(e2, qv) * inv, p, 0, group, 0, 0);
+  // consider() for a facet (no trimming list), but for ties between FACETS: a facet met within 1e-3 distTol of the facet
+  // that leads -- an edge or a vertex they share, where their t differ by rounding alone -- joins it: the pair goes on
+  // as (the smaller t, the lower number), as in the oracle, whatever the last bits of t say.  For facets that all lie
+  // within that window of each other the outcome is a function of the set, not of the order they are visited in.  (Only
+  // one of them is recorded either way: the others then lie closer than distTol.  Where a facet that faces the ray meets
+  // one that faces away, the winner decides the entering bit.)  Against an analytic primitive that leads, and for
+  // analytic candidates (consider()), the exact comparison stays.
+  const double t = dot(e2, qv) * inv;
+  if (!(t > q.tol && t < q.tmax)) return;
+  const double tie = 1e-3 * q.tol;
+  const auto facet = [&](Best& b) {
+    if (fabs(t - b.t) <= tie && sv.prim_i32[4 * b.prim] == ODW_PRIM_TRIANGLE) {      // (b.t finite: b.prim is a primitive)
+      b.t = fmin(b.t, t);
+      b.prim = p < b.prim ? p : b.prim;
+    } else if (better(t, p, 0, b)) {
+      b.t = t; b.prim = p; b.face = 0;
+    }
+  };
+  facet(q.any);
+  if (q.medium >= 0 && group != q.medium) facet(q.oth);
 }
 
 // facet or interpolated normal of a triangle at the global point gp

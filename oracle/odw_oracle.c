@@ -575,8 +575,23 @@ static nearest_hit nearest_skipping(const odw_scene_desc* sc, const odw_limits* 
       nearest_hit h;
       h.found = 1; h.prim = p; h.face = 0; h.group = g; h.dist = t;
       h.point = gp; h.normal = ng;
-      if (better(t, p, 0, any.dist, any.prim, any.face)) any = h;
-      if (g != medium && better(t, p, 0, oth.dist, oth.prim, oth.face)) oth = h;
+      /* ties between FACETS: a facet met within 1e-3 distTol of the facet that leads (an edge or a vertex
+       * they share: their t differ by rounding alone) joins it -- the pair goes on as (the smaller t, the
+       * lower number); against an analytic primitive the exact comparison stays (intersect_tri of the kernels) */
+      const double tie = 1e-3 * tol;
+      nearest_hit* lead[2] = {&any, (g != medium) ? &oth : NULL};
+      for (int k = 0; k < 2; ++k) {
+        nearest_hit* b = lead[k];
+        if (!b) continue;
+        if (b->found && fabs(t - b->dist) <= tie && sc->prim_type[b->prim] == ODW_PRIM_TRIANGLE) {
+          double tm = fmin(b->dist, t);
+          if (p < b->prim) *b = h;
+          b->dist = tm;
+          b->point = add(start, mul(dn, tm));
+        } else if (better(t, p, 0, b->dist, b->prim, b->face)) {
+          *b = h;
+        }
+      }
       continue;
     }
     /* ray in local coordinates: lstart = M*start, ldir = M*(start+dir)-lstart

@@ -413,29 +413,65 @@ def aimed_sets(name='lattice'):
 BENCH_GROUPS = ('mirror', 'lens', 'reflection', 'transmission', 'vacuum', 'perfect', 'floor')
 
 
-def bench(**settings):
+def bench(faceted=False, **settings):
   """-> (scene, limits): a mirror of reflectivity 0.8, a ball lens and two glass blocks of absorbing glass, a reflection
   and a transmission grating (one slab of it inside a glass block: met from inside a medium), a vacuum ball, two pairs of
-  facing mirrors (reflectivity 1: the cap on intersections; 0.8: the power limit), an absorber under everything"""
+  facing mirrors (reflectivity 1: the cap on intersections; 0.8: the power limit), an absorber under everything.
+  faceted: every solid but the floor as a mesh -- the boxes of 12 facets, the lens ball of 24 segments with smooth normals,
+  the vacuum ball of 24 segments with flat ones (tests/mesh_cases.py)"""
   from freecad.optics_design_workbench_amd.scene import Document, bake
   doc = Document()
   box = lambda name, lo, hi: ec.centred_box(doc, name, lo, hi)
+  ball = lambda name, r, base, smooth: make.makeSphere(doc, name, r, base=base)
+  if faceted:
+    from tree_cases import _cube_mesh
+    box = lambda name, lo, hi: make.makeMesh(doc, *_cube_mesh(lo, hi), name=name)
+    ball = lambda name, r, base, smooth: make.makeTessellated(doc, make.makeSphere(doc, name, r, base=base), 24, smooth=smooth)
   make.makeMirror(doc, [box('M', (-15, -15, 50), (15, 15, 52)), box('P0', (790, -15, 10), (792, 15, 50)), box('P1', (808, -15, 10), (810, 15, 50))],
                   Reflectivity=0.8, RecordHits=True)
-  make.makeLens(doc, [make.makeSphere(doc, 'Ball', 8.0, base=(100.0, 0.0, 30.0)), box('Cube', (195, -5, 25), (205, 5, 35)),
+  make.makeLens(doc, [ball('Ball', 8.0, (100.0, 0.0, 30.0), True), box('Cube', (195, -5, 25), (205, 5, 35)),
                       box('Block', (485, -15, 20), (515, 15, 60))], RefractiveIndex=1.5, AbsorptionLength='40.0', RecordHits=True)
   make.makeGrating(doc, [box('GR', (285, -15, 50), (315, 15, 52))], RecordHits=True, GratingType='Reflection',
                    GratingLinesPerMillimeter=600.0, GratingLinesOrientation=np.array([1.0, 0.0, 0.0]))
   make.makeGrating(doc, [box('GT', (385, -15, 50), (415, 15, 52)), box('GI', (490, -10, 40), (510, 10, 42))], RecordHits=True,
                    GratingType='Transmission', RefractiveIndex=1.5, GratingLinesPerMillimeter=300.0,
                    GratingLinesOrientation=np.array([0.0, 1.0, 0.0]))
-  make.makeVacuum(doc, [make.makeSphere(doc, 'V', 5.0, base=(600.0, 0.0, 30.0))])
+  make.makeVacuum(doc, [ball('V', 5.0, (600.0, 0.0, 30.0), False)])
   make.makeMirror(doc, [box('F0', (690, -15, 10), (692, 15, 50)), box('F1', (708, -15, 10), (710, 15, 50))], Reflectivity=1.0,
                   RecordHits=True, name='PerfectMirrors')
-  make.makeAbsorber(doc, [box('Floor', (-100, -100, -42), (900, 100, -40))])
+  make.makeAbsorber(doc, [ec.centred_box(doc, 'Floor', (-100, -100, -42), (900, 100, -40))])
   make.makeSimulationSettings(doc, **dict(dict(DistanceTolerance='1e-6', MaxIntersections=6.0), **settings))
   src = make.makePointSource(doc)
   return bake.bakeScene(doc, src), bake.bakeLimits(doc, src)
+
+
+def bench_variant(sc, lim, variant):
+  """the bench as the interaction tests run it: 'capped' as it is, 'power-limit' with PowerTolerance 0.6, 'sequential'
+  with a sequence whose third step leaves the mirrors out -> (scene, limits)"""
+  import copy
+  import dataclasses
+  assert variant in ('capped', 'power-limit', 'sequential')
+  if variant == 'power-limit':
+    lim = dataclasses.replace(lim, power_tol=0.6)
+  if variant == 'sequential':
+    sc = copy.copy(sc)
+    every = (1 << len(sc.group_type)) - 1
+    sc.seq_enabled, sc.seq_mask = 1, np.array([every, every, every & ~1, every], np.uint64)
+  return sc, lim
+
+
+def bench_figures(rows, cnt, station, variant):
+  """what the stations of the bench record, whichever kernel traced them and whether its solids are faceted or not"""
+  per_ray = np.bincount((rows['tag'] & np.uint64(0xFFFFFFFFFFFF)).astype(np.int64), minlength=len(station))
+  assert cnt['grating_in_medium'] == (station == 'in-medium').sum() == 100
+  assert (per_ray[station == 'inside-ball'] == 1).all()
+  if variant != 'sequential':
+    assert (per_ray[station == 'tir'] == 4).all()                  # in, the side face (reflected totally), out, the floor
+    assert (per_ray[station == 'perfect'] == 6).all() and cnt['capped'] == (200 if variant == 'capped' else 100)
+    assert (per_ray[station == 'lossy'] == (6 if variant == 'capped' else 3)).all()
+    assert len(np.unique(rows['power'])) > 300                        # (the absorbing glass moves the power)
+  else:
+    assert cnt['capped'] == 0 and per_ray.max() <= 4
 
 
 def bench_rays():

@@ -12,9 +12,6 @@ launch to those of the same scene's plain launch (the grid kernel, or the tree a
 
 One exception, by the reference's own arithmetic: on tree_cases.far_back_set the oracle's points are 2.5e-9 / 7.2e-9 mm
 off the closed form (see there); the device is held to the closed form within ec.TOL, to the oracle in tags and counters."""
-import copy
-import dataclasses
-
 import numpy as np
 import pytest
 
@@ -234,14 +231,8 @@ def test_interactions(native_lib, oracle, monkeypatch, variant):
   """the bench of grid_cases through the tree (ODW_BVH_THRESHOLD=4 when the context is made, segment rows) against the oracle
   and against the flat kernel of a context made without it; the variants of test_gpu_grid.py::test_interactions.
   sequential: the per-lane `mask` test of the leaf loop"""
-  sc, lim = gc.bench()
+  sc, lim = gc.bench_variant(*gc.bench(), variant)
   o, d, station = gc.bench_rays()
-  if variant == 'power-limit':
-    lim = dataclasses.replace(lim, power_tol=0.6)
-  if variant == 'sequential':
-    sc = copy.copy(sc)
-    every = (1 << len(sc.group_type)) - 1
-    sc.seq_enabled, sc.seq_mask = 1, np.array([every, every, every & ~1, every], np.uint64)
   flat = _launch(sc, lim, o, d, segments=False, tree=False, structure='flat')
   monkeypatch.setenv('ODW_BVH_THRESHOLD', '4')
   tree = _launch(sc, lim, o, d, structure='grid')
@@ -256,17 +247,7 @@ def test_interactions(native_lib, oracle, monkeypatch, variant):
              float(np.abs(got['power'] - want['segments']['power']).max()))
   print(f'{variant}: segments against the oracle: p1 %.3e mm, p2 %.3e mm, powers %.3e over {len(got)} rows' % figures)
   assert figures[0] < ec.TOL and figures[1] < ec.TOL and figures[2] < ec.POWER_TOL
-  rows, cnt = tree['rows'], tree['counters']
-  per_ray = np.bincount((rows['tag'] & RAY).astype(np.int64), minlength=len(o))
-  assert cnt['grating_in_medium'] == (station == 'in-medium').sum() == 100
-  assert (per_ray[station == 'inside-ball'] == 1).all()
-  if variant != 'sequential':
-    assert (per_ray[station == 'tir'] == 4).all()                  # in, the side face (reflected totally), out, the floor
-    assert (per_ray[station == 'perfect'] == 6).all() and cnt['capped'] == (200 if variant == 'capped' else 100)
-    assert (per_ray[station == 'lossy'] == (6 if variant == 'capped' else 3)).all()
-    assert len(np.unique(rows['power'])) > 300                        # (the absorbing glass moves the power)
-  else:
-    assert cnt['capped'] == 0 and per_ray.max() <= 4
+  gc.bench_figures(tree['rows'], tree['counters'], station, variant)
 
 
 # ---- lists that are too small: the designed overflow --------------------------------------------------------------------------------
