@@ -705,7 +705,8 @@ __device__ __forceinline__ void cand_min2(Cands& c, double t, int f) {
 // loop must stay inside the instruction cache).
 // SPEC / PI: primitive PI of a compiled scene -- the caller passes its constants as p, type, group,
 // flags, cond_word, so everything that depends on them folds
-template <int RQ = ODW_RQ_ALL, class SPEC = NoSpec, int PI = 0>
+// FLAT (compiled kernels but the BATCH variant's): the entry faces of an untrimmed box without exec-mask regions
+template <int RQ = ODW_RQ_ALL, class SPEC = NoSpec, int PI = 0, bool FLAT = false>
 __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, int p, int type, int group,
                                                int flags, int cond_word) {
   constexpr bool PARAB = (RQ & ODW_RQ_PARAB) != 0, ELL = (RQ & ODW_RQ_ELLIPSOID) != 0, CON = (RQ & ODW_RQ_CONICOID) != 0;
@@ -815,9 +816,36 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       if (ok_ && (t_ < bt || (t_ == bt && (FACE) < bf))) { bt = t_; bf = (FACE); }            \
     }
     // entry faces: low face when moving in +axis direction
+    if constexpr (FLAT) {
+      // The same choice without exec-mask regions: each face's distance where the face is valid, +inf where not;
+      // the least of the three; the first face in x, y, z order that has it (faces are numbered in that order, so
+      // that is the tie rule `FACE < bf` of the loop below; a valid face has a finite distance -- t = inf fails the
+      // rectangle tests -- so bt < inf exactly when some face is valid).  As three regions the faces cost more than
+      // their own instructions: the compiler sinks everything used behind them (the exit planes, t_in, t_out) to its
+      // first use, where the operands come out of other basic blocks and each gets a canonicalising v_max_f64 x, x, x
+      // in front of the fmax / fmin that reads it -- nine per box test; moving t_in and t_out up in the source does
+      // not help, the sinking pass moves them back.  In one block there is none (profiles/r10/README.md).
+#define ODW_BOX_TRY(T, FACE, P1, D1, S1, P2, D2, S2, TK)                                      \
+      double TK;                                                                              \
+      {                                                                                       \
+        const double t_ = (T);                                                                \
+        const double u_ = fma(t_, D1, P1), v_ = fma(t_, D2, P2);                              \
+        const bool ok_ = ODW_BOX_OK(((fmask >> (FACE)) & 1) != 0, t_ > tol, u_ >= -tol, u_ <= (S1), \
+                                    v_ >= -tol, v_ <= (S2));                                  \
+        TK = ok_ ? t_ : (double)INFINITY;                                                     \
+      }
+      ODW_BOX_TRY(nx_, px ? 0 : 1, o.y, d.y, ODW_SYT, o.z, d.z, ODW_SZT, tx_);
+      ODW_BOX_TRY(ny_, py ? 2 : 3, o.z, d.z, ODW_SZT, o.x, d.x, ODW_SXT, ty_);
+      ODW_BOX_TRY(nz_, pz ? 4 : 5, o.x, d.x, ODW_SXT, o.y, d.y, ODW_SYT, tz_);
+#undef ODW_BOX_TRY
+      bt = fmin(fmin(tx_, ty_), tz_);
+      bf = tx_ == bt ? (px ? 0 : 1) : (ty_ == bt ? (py ? 2 : 3) : (pz ? 4 : 5));
+      bf = bt < INFINITY ? bf : 0;
+    } else {
     ODW_BOX_FACE(nx_, px ? 0 : 1, o.y, d.y, ODW_SYT, o.z, d.z, ODW_SZT);
     ODW_BOX_FACE(ny_, py ? 2 : 3, o.z, d.z, ODW_SZT, o.x, d.x, ODW_SXT);
     ODW_BOX_FACE(nz_, pz ? 4 : 5, o.x, d.x, ODW_SXT, o.y, d.y, ODW_SYT);
+    }
     c.t0 = bt;
     c.f0 = bf;
     const double t_in = fmax(fmax(nx_, ny_), nz_);
@@ -1311,6 +1339,47 @@ __device__ __forceinline__ bool ray_box_centred(SpecBox b, d3 oi, d3 inv, double
   lo = fmax(lo, fma(-b.hz, w, a)); hi = fmin(hi, fma(b.hz, w, a));
   return hi >= fmax(lo, 0.0) && lo < tmax;
 }
+// The same screen with |1/d| and -(o/d) handed in as VALUES (compiled kernels but the BATCH variant's).  The screens of
+// a segment sit in different basic blocks, behind exec-mask branches; instruction selection folds |x| and -x into an
+// instruction only within a block, so fabs(inv) and -oi, common to all screens, were formed once in the block that
+// dominates them: three v_and_b32 and three v_xor_b32 with a v_mov_b32 each, twelve instructions per segment, and two
+// more register pairs per axis live across the segment.  spec_reciprocals() makes both by instructions of their own:
+// |1/d| by the last fma of the reciprocal's Newton step a second time, on |r| (r -> -r flips the sign of that fma's
+// result and nothing else: it IS |1/d|, to the bit), -(o/d) by the product with -o.  Three fma per segment, no copy,
+// and every screen takes plain operands: same fma, same operands' values, same fmax / fmin chains as above.
+struct SpecRecip { d3 inv, w, noi; };     // 1/d, |1/d|, -(o/d), component by component
+__device__ __forceinline__ SpecRecip spec_reciprocals(d3 start, d3 dn) {
+  SpecRecip rc;
+  // (frcp1, its last fma also on |r|)
+  const double rx = __builtin_amdgcn_rcp(dn.x), ry = __builtin_amdgcn_rcp(dn.y), rz = __builtin_amdgcn_rcp(dn.z);
+  const double ex = fma(-dn.x, rx, 1.0), ey = fma(-dn.y, ry, 1.0), ez = fma(-dn.z, rz, 1.0);
+  rc.inv = mk(fma(ex, rx, rx), fma(ey, ry, ry), fma(ez, rz, rz));
+  rc.w = mk(fma(ex, fabs(rx), fabs(rx)), fma(ey, fabs(ry), fabs(ry)), fma(ez, fabs(rz), fabs(rz)));
+  rc.noi = mk(-start.x * rc.inv.x, -start.y * rc.inv.y, -start.z * rc.inv.z);
+#if ODW_DOUBLE == 9
+  {
+    const d3 d2 = mk(opq(dn.x), opq(dn.y), opq(dn.z));
+    const double sx = __builtin_amdgcn_rcp(d2.x), sy = __builtin_amdgcn_rcp(d2.y), sz = __builtin_amdgcn_rcp(d2.z);
+    const double fx = fma(-d2.x, sx, 1.0), fy = fma(-d2.y, sy, 1.0), fz = fma(-d2.z, sz, 1.0);
+    const d3 inv2 = mk(fma(fx, sx, sx), fma(fy, sy, sy), fma(fz, sz, sz));
+    const d3 w2 = mk(fma(fx, fabs(sx), fabs(sx)), fma(fy, fabs(sy), fabs(sy)), fma(fz, fabs(sz), fabs(sz)));
+    const d3 noi2 = mk(-start.x * inv2.x, -start.y * inv2.y, -start.z * inv2.z);
+    rc.inv = inv2.x == rc.inv.x ? rc.inv : inv2;
+    rc.w = w2.x == rc.w.x ? rc.w : w2;
+    rc.noi = noi2.y == rc.noi.y ? rc.noi : noi2;
+  }
+#endif
+  return rc;
+}
+__device__ __forceinline__ bool ray_box_centred(SpecBox b, const SpecRecip& rc, double tmax) {
+  double a = fma(b.cx, rc.inv.x, rc.noi.x);
+  double lo = fma(-b.hx, rc.w.x, a), hi = fma(b.hx, rc.w.x, a);
+  a = fma(b.cy, rc.inv.y, rc.noi.y);
+  lo = fmax(lo, fma(-b.hy, rc.w.y, a)); hi = fmin(hi, fma(b.hy, rc.w.y, a));
+  a = fma(b.cz, rc.inv.z, rc.noi.z);
+  lo = fmax(lo, fma(-b.hz, rc.w.z, a)); hi = fmin(hi, fma(b.hz, rc.w.z, a));
+  return hi >= fmax(lo, 0.0) && lo < tmax;
+}
 // does primitive PI of a compiled scene leave code at all (spec_prim), and does that code screen a box of its own
 template <class SPEC>
 constexpr bool spec_live(int pi) { return !SPEC::dead(pi) && (SPEC::seq() || ((SPEC::umask() >> SPEC::group(pi)) & 1) != 0); }
@@ -1339,14 +1408,31 @@ __device__ __forceinline__ SpecBox spec_box(const SceneView& sv) {
 //            primitive culled by its bounding box first -- the analogue of the
 //            reference's shell/face BoundBox culls (ray.py:353-398);
 // BVH=true : stack traversal, node stack in LDS (one column per thread).
-// one primitive of a compiled scene (flat loop unrolled over SPEC)
+// the exact test of a compiled scene's primitive whose box the ray meets short of the cut
+template <class SPEC, int PI, bool FLAT>
+__device__ __forceinline__ void spec_prim_exact(const SceneView& sv, Query& q, bool in_box) {
+  constexpr int flags = SPEC::flags(PI);
+  if (in_box)
+    intersect_prim<SPEC::rare(), SPEC, PI, FLAT>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
+#if ODW_DOUBLE == 3 || ODW_DOUBLE == 4 || ODW_DOUBLE == 12
+  // (the second pass finds the candidates already known: consider_spec leaves early, before the trimming tests)
+  if (in_box && SPEC::type(PI) == (ODW_DOUBLE == 3 ? ODW_PRIM_CYLINDER : (ODW_DOUBLE == 4 ? ODW_PRIM_BOX : ODW_PRIM_SPHERE))) {
+    Query q2 = q;
+    q2.start.x = opq(q.start.x);
+    intersect_prim<SPEC::rare(), SPEC, PI, FLAT>(sv, q2, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
+    q.any = q2.any; q.oth = q2.oth;
+  }
+#endif
+}
+// one primitive of a compiled scene (flat loop unrolled over SPEC).  LEAN (every compiled kernel but the BATCH
+// variant's): the screen takes |1/d| and -(o/d) as values (rc), the box faces are the flat ones; else oi, inv as before
 // boxhit: the outcome of the box test of every primitive so far.  Operands of a Common that must lie inside
 // each other (a lens = sphere in cylinder, cylinder in sphere) carry the SAME box -- each one's own box cut by
 // the other's -- which shows in the structure: equal sets {primitive} + {primitives it must be inside}
 // (SPEC::box_of = the first primitive with that set).  The later ones reuse the first one's outcome (taken
 // with a cut at least as wide: conservative).
-template <class SPEC, int PI>
-__device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid,
+template <class SPEC, int PI, bool LEAN>
+__device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, d3 inv, const SpecRecip& rc, int skip_solid,
                                           uint64_t mask, bool* boxhit, SpecBox& pending) {
   constexpr int flags = SPEC::flags(PI);
   // relevant groups: a constant without sequential mode (ignored groups' primitives leave no code),
@@ -1368,40 +1454,33 @@ __device__ __forceinline__ void spec_prim(const SceneView& sv, Query& q, d3 oi, 
         in_box = boxhit[SPEC::box_of(PI)];
       } else {
         const double cut = q.cut;
-        in_box = ray_box_centred(own, oi, inv, cut);
+        if constexpr (LEAN) in_box = ray_box_centred(own, rc, cut);
+        else in_box = ray_box_centred(own, oi, inv, cut);
 #if ODW_DOUBLE == 1
-        in_box = in_box & ray_box_centred(own, mk(opq(oi.x), oi.y, oi.z), inv, cut);
+        if constexpr (LEAN) in_box = in_box & ray_box_centred(own, SpecRecip{rc.inv, rc.w, mk(opq(rc.noi.x), rc.noi.y, rc.noi.z)}, cut);
+        else in_box = in_box & ray_box_centred(own, mk(opq(oi.x), oi.y, oi.z), inv, cut);
 #endif
       }
       boxhit[PI] = in_box;
-      if (in_box)
-        intersect_prim<SPEC::rare(), SPEC, PI>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
-#if ODW_DOUBLE == 3 || ODW_DOUBLE == 4 || ODW_DOUBLE == 12
-      // (the second pass finds the candidates already known: consider_spec leaves early, before the trimming tests)
-      if (in_box && SPEC::type(PI) == (ODW_DOUBLE == 3 ? ODW_PRIM_CYLINDER : (ODW_DOUBLE == 4 ? ODW_PRIM_BOX : ODW_PRIM_SPHERE))) {
-        Query q2 = q;
-        q2.start.x = opq(q.start.x);
-        intersect_prim<SPEC::rare(), SPEC, PI>(sv, q2, PI, SPEC::type(PI), SPEC::group(PI), flags, SPEC::cond_word(PI));
-        q.any = q2.any; q.oth = q2.oth;
-      }
-#endif
+      spec_prim_exact<SPEC, PI, LEAN>(sv, q, in_box);
     } else if constexpr (SPEC::box_of(PI) == PI) {
       // (skipped for this lane -- not relevant, or the convex solid just left --, but a later primitive may
       //  ask for this box: its own test then)
-      boxhit[PI] = SPEC::box_shared(PI) ? ray_box_centred(own, oi, inv, q.cut) : false;
+      if constexpr (LEAN) boxhit[PI] = SPEC::box_shared(PI) ? ray_box_centred(own, rc, q.cut) : false;
+      else boxhit[PI] = SPEC::box_shared(PI) ? ray_box_centred(own, oi, inv, q.cut) : false;
     }
   }
 }
 template <class T, T... I> struct IndexList {};      // (std::integer_sequence without <utility>: runtime compilation has no libstdc++)
-template <class SPEC, int... PI>
-__device__ __forceinline__ void spec_prims(const SceneView& sv, Query& q, d3 oi, d3 inv, int skip_solid,
+template <class SPEC, bool LEAN, int... PI>
+__device__ __forceinline__ void spec_prims(const SceneView& sv, Query& q, d3 oi, d3 inv, const SpecRecip& rc, int skip_solid,
                                            uint64_t mask, IndexList<int, PI...>) {
   bool boxhit[sizeof...(PI)] = {};
   // the first block; every spec_prim that uses one asks for the next (from sv.img as it stands at this segment: a
   // batch's image moves with the hand-out unit's scene)
   SpecBox pending = {};
   if constexpr (spec_next_box<SPEC>(0) >= 0) pending = spec_box<SPEC, spec_next_box<SPEC>(0)>(sv);
-  (spec_prim<SPEC, PI>(sv, q, oi, inv, skip_solid, mask, boxhit, pending), ...);
+  (spec_prim<SPEC, PI, LEAN>(sv, q, oi, inv, rc, skip_solid, mask, boxhit, pending), ...);
 }
 
 // ---- a wave inside one isolated solid (compiled kernels) ----
@@ -1448,7 +1527,7 @@ constexpr int spec_cand_count() {
 template <class SPEC, int S, int PI>
 __device__ __forceinline__ void spec_solid_prim(const SceneView& sv, Query& q) {
   if constexpr (spec_live<SPEC>(PI) && spec_solid<SPEC>(PI) == S)
-    intersect_prim<SPEC::rare(), SPEC, PI>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), SPEC::flags(PI), SPEC::cond_word(PI));
+    intersect_prim<SPEC::rare(), SPEC, PI, true>(sv, q, PI, SPEC::type(PI), SPEC::group(PI), SPEC::flags(PI), SPEC::cond_word(PI));
 }
 // PF opens a candidate solid S: if the wave's first live lane stands in S, S is isolated in this scene, and every
 // live lane stands in S with S's group as its medium, the primitives of S in index order -- true; else nothing
@@ -1492,7 +1571,8 @@ __device__ __forceinline__ void ray_reciprocals(d3 start, d3 dn, d3& inv, d3& oi
 #endif
 }
 
-// UNIFORM (compiled kernels): the instantiation carries spec_uniform.  Not the BATCH variant's: the sweep's launches
+// UNIFORM (compiled kernels): the instantiation carries spec_uniform, and its general loop the screens on |1/d| and
+// -(o/d) as values and the flat box faces (spec_prim: LEAN).  Not the BATCH variant's: the sweep's launches
 // (a wide source, rays that miss the lens beside rays that cross it: mixed waves) ran 1 - 2 % slower with it
 // (profiles/r09/README.md), so a batch keeps the general loop alone and its code is what it was.
 template <bool BVH, class SPEC = NoSpec, bool ASPH = false, bool UNIFORM = true>
@@ -1517,8 +1597,10 @@ __device__ __forceinline__ int nearest(const DeviceScene& sc, const SceneView& s
     bool uniform = false;
     if constexpr (UNIFORM && spec_cand_count<SPEC>() > 0) uniform = spec_uniform<SPEC>(sv, q, only_solid, __make_integer_seq<IndexList, int, SPEC::N>{});
     if (!uniform) {
-      ray_reciprocals(start, dn, inv, oi);
-      spec_prims<SPEC>(sv, q, oi, inv, skip_solid, mask, __make_integer_seq<IndexList, int, SPEC::N>{});
+      SpecRecip rc = {};
+      if constexpr (UNIFORM) rc = spec_reciprocals(start, dn);
+      else ray_reciprocals(start, dn, inv, oi);
+      spec_prims<SPEC, UNIFORM>(sv, q, oi, inv, rc, skip_solid, mask, __make_integer_seq<IndexList, int, SPEC::N>{});
       only_solid = -1;
     }
   } else if (!BVH) {
