@@ -892,11 +892,19 @@ __device__ __forceinline__ void intersect_prim(const SceneView& sv, Query& q, in
       side = !(fma(xl, xl, yl * yl) < lim && fma(xh, xh, yh * yh) < lim);
     }
     if (side) {
-      const double rz = R1 + k * o.z;
+      // The quadratic from the point of the line nearest the frame's origin (|d| = 1), as the torus has it, not from the
+      // ray's origin: the terms of c cancel to the square of the crossing's distance from the axis (a cone: from the
+      // apex), and from an origin 1200 mm away, or 30 mm from an apex the line passes at 1e-3 mm, they lost 1e-9 to
+      // 8e-9 mm of the crossing (tests/test_gpu_revolution.py: the sets `back` and `apex`).
+      const double ts = -dot(o, d);
+      const double ox = fma(ts, d.x, o.x), oy = fma(ts, d.y, o.y), oz = fma(ts, d.z, o.z);
+      const double rz = R1 + k * oz;
       double t0 = INFINITY, t1 = INFINITY;
       const int nr = quad_roots(d.x * d.x + d.y * d.y - k * k * d.z * d.z,
-                                o.x * d.x + o.y * d.y - k * rz * d.z - f2 * d.z,
-                                o.x * o.x + o.y * o.y - rz * rz - 2.0 * f2 * o.z, t0, t1);
+                                ox * d.x + oy * d.y - k * rz * d.z - f2 * d.z,
+                                ox * ox + oy * oy - rz * rz - 2.0 * f2 * oz, t0, t1);
+      t0 += ts;
+      t1 += ts;
       const double z0 = o.z + t0 * d.z, z1 = o.z + t1 * d.z;
       c.t0 = (bool)((int)(nr >= 1) & (int)(z0 >= -tol) & (int)(z0 <= ODW_HT) & (int)((R1 + k * z0) >= -tol)) ? t0 : c.t0;
       c.t1 = (bool)((int)(nr == 2) & (int)(z1 >= -tol) & (int)(z1 <= ODW_HT) & (int)((R1 + k * z1) >= -tol)) ? t1 : c.t1;

@@ -170,6 +170,10 @@ static v3 xf_point(const double* m, v3 p) {
            m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7],
            m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11]);
 }
+/* direction transform: R v */
+static v3 xf_vec(const double* m, v3 v) {
+  return V(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z);
+}
 /* inverse of a rigid (R|t): p = R^T (q - t) */
 static v3 xf_point_inv(const double* m, v3 q) {
   v3 d = V(q.x - m[3], q.y - m[7], q.z - m[11]);
@@ -371,13 +375,18 @@ static int prim_candidates(int type, const double* par, int facemask, v3 o, v3 d
       if (type == ODW_PRIM_CYLINDER) { R2 = par[0]; H = par[1]; k = 0; }
       else { R2 = par[1]; H = par[2]; k = (R2 - R1) / H; }
       if (facemask & 1) {
+        /* from the point of the line nearest the frame's origin (|d| = 1), not from the ray's origin: the terms of c
+         * cancel to the square of the crossing's distance from the axis (a cone: from the apex) */
         double r[2];
-        double rz = R1 + k * o.z;
+        double ts = -dot(o, d);
+        v3 oc = add(o, mul(d, ts));
+        double rz = R1 + k * oc.z;
         double a = d.x * d.x + d.y * d.y - k * k * d.z * d.z;
-        double bh = o.x * d.x + o.y * d.y - k * rz * d.z;
-        double c = o.x * o.x + o.y * o.y - rz * rz;
+        double bh = oc.x * d.x + oc.y * d.y - k * rz * d.z;
+        double c = oc.x * oc.x + oc.y * oc.y - rz * rz;
         int nr = quad_roots(a, bh, c, r);
         for (int i = 0; i < nr; ++i) {
+          r[i] += ts;
           v3 p = add(o, mul(d, r[i]));
           if (p.z < -tol || p.z > H + tol) continue;
           double rr = R1 + k * p.z;
@@ -406,9 +415,12 @@ static int prim_candidates(int type, const double* par, int facemask, v3 o, v3 d
       double f = par[0], H = par[1];
       if (facemask & 1) {
         double r[2];
-        int nr = quad_roots(d.x * d.x + d.y * d.y, o.x * d.x + o.y * d.y - 2.0 * f * d.z,
-                            o.x * o.x + o.y * o.y - 4.0 * f * o.z, r);
+        double ts = -dot(o, d);                       /* (as for the cylinder and the cone) */
+        v3 oc = add(o, mul(d, ts));
+        int nr = quad_roots(d.x * d.x + d.y * d.y, oc.x * d.x + oc.y * d.y - 2.0 * f * d.z,
+                            oc.x * oc.x + oc.y * oc.y - 4.0 * f * oc.z, r);
         for (int i = 0; i < nr; ++i) {
+          r[i] += ts;
           v3 p = add(o, mul(d, r[i]));
           if (p.z < -tol || p.z > H + tol) continue;
           v3 g = V(p.x, p.y, -2.0 * f);
@@ -594,10 +606,11 @@ static nearest_hit nearest_skipping(const odw_scene_desc* sc, const odw_limits* 
       }
       continue;
     }
-    /* ray in local coordinates: lstart = M*start, ldir = M*(start+dir)-lstart
-     * (ray.py:348-349) */
+    /* ray in local coordinates: lstart = M*start, ldir = R*dir.  (ray.py:348-349 takes M*(start+dir)-lstart, which
+     * loses the direction's last digits to the size of `start`: 13 m from the origin a direction good to 2e-12, and a
+     * crossing 200 mm on displaced by 4e-10 mm; the kernels rotate the direction, as here) */
     v3 lstart = xf_point(M, start);
-    v3 ldir = sub(xf_point(M, add(start, dn)), lstart);
+    v3 ldir = xf_vec(M, dn);
     int flags = sc->prim_flags[p];
     cand cs[8];
     int nc = prim_candidates(sc->prim_type[p], sc->prim_params + 4 * (size_t)p,
@@ -912,7 +925,7 @@ static nearest_hit nearest_strict(const odw_scene_desc* sc, const odw_limits* li
         continue;
       }
       v3 lstart = xf_point(M, start);
-      v3 ldir = sub(xf_point(M, add(start, dn)), lstart);                  /* ray.py:348-349 */
+      v3 ldir = xf_vec(M, dn);                                             /* (as in nearest_skipping) */
       cand cs[8];
       int nc = prim_candidates(sc->prim_type[p], sc->prim_params + 4 * (size_t)p, 1 << fc[i].face,
                                lstart, ldir, tol, cs);

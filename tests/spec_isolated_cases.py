@@ -119,7 +119,7 @@ def rays_fan(seed=44, n=N):
 EDGE_OFFSETS = (0.0, 0.5, -0.5, 2.0, -2.0)      # of distTol
 # rays of rays_edges() that enter lens A and whose next segment does not end on it, counted on the CPU oracle
 # (tests/test_spec_isolated_build.py holds the oracle to it): what the retry after an empty short search is for
-EDGE_PASS_BY = 1438
+EDGE_PASS_BY = 1432
 
 
 def rays_edges(seed=45, n=N):

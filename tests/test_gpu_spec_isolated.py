@@ -91,7 +91,7 @@ def test_rows_equal_the_generic_kernels(tracers, native_lib, name):
     assert all((mask >> s) & 1 for s in lenses)
   got = both(tracers, pr, *rays())
   if name == 'edges':
-    # (the oracle counts EDGE_PASS_BY = 1438 such rays, tests/test_spec_isolated_build.py; the device's arithmetic
+    # (the oracle counts EDGE_PASS_BY = 1432 such rays, tests/test_spec_isolated_build.py; the device's arithmetic
     #  agrees with the oracle's to 1e-9 mm, not to the bit, and rays aimed exactly at an edge may fall either way:
     #  1559 on an MI355X -- the case holds them on the device too, which is what it is there for)
     assert ic.EDGE_PASS_BY > 0 and ic.passes_by(got['hits'], pr) > 0
