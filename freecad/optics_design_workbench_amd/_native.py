@@ -26,6 +26,8 @@ ABI_VERSION = 12
 CNT_NAMES = ['traced_rays', 'recorded_hits', 'segments', 'escaped', 'died', 'capped',
              'hist_overflow', 'hits_dropped', 'grating_in_medium']
 TRACE_RECORD_HITS, TRACE_HISTOGRAM, TRACE_RECORD_SEGMENTS, TRACE_POWER_HISTOGRAM = 1, 2, 4, 8
+TRACE_BAND_HISTOGRAM = 16                 # ODW_TRACE_BAND_HISTOGRAM: the detector's band planes (odw_set_detector_bands)
+BAND_MAX = 64                             # ODW_BAND_MAX: bands of a detector at most
 POWER_QUANTUM_BITS = 32                   # ODW_POWER_QUANTUM_BITS: a hit's weight is rint(clamp(power, 0, 2^20) * 2^32)
 FLAG_FLIP_NORMAL, FLAG_CONVEX = 1, 2      # ODW_FLAG_* of prim_flags (include/odw_trace.h)
 PRIM_PARABOLOID, PRIM_ELLIPSOID, PRIM_CONICOID, PRIM_ASPHERE = 6, 7, 8, 9    # ODW_PRIM_*: the rare kinds (scene.geometry holds the whole list of kinds)
@@ -53,7 +55,9 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_set_dispersion', 'odw_set_spectrum', 'odw_trace_rays_spectral', 'odw_ray_wavelengths', 'odw_dispersion_index',
            'odw_dispersion_check', 'odw_spectrum_check', 'odw_compiled_chroma_info', 'odw_compile_check_chroma',
            'odw_set_fresnel', 'odw_compiled_fresnel_info', 'odw_fresnel_reflectance', 'odw_compile_check_fresnel', 'odw_fresnel_check',
-           'odw_set_coating', 'odw_coating_check', 'odw_coated_reflectance', 'odw_compile_check_coating']
+           'odw_set_coating', 'odw_coating_check', 'odw_coated_reflectance', 'odw_compile_check_coating',
+           'odw_set_detector_bands', 'odw_fetch_band_histogram', 'odw_fetch_band_power_histogram', 'odw_device_band_histogram',
+           'odw_band_index', 'odw_compiled_bands_info', 'odw_compile_check_bands']
 
 # dispersion of a group (ODW_DISP_*) and spectrum of a point source (ODW_SPECTRUM_*)
 DISP_NONE, DISP_SELLMEIER, DISP_CAUCHY = 0, 1, 2
@@ -302,6 +306,45 @@ def compile_check_chroma(scene, limits, arch=None, source=None):
          kinds.ctypes.data_as(_pi), buf, len(buf), C.byref(size))
   check(None, rc, 'odw_compile_check_chroma')
   return buf.value.decode(), int(size.value)
+
+
+def compile_check_bands(scene, limits, arch=None, source=None, power=False):
+  """Host only (no GPU): header and code size of the CHROMA variant that fills the detector's band planes
+  (`odw_compile_check_bands`); power: with the power plane"""
+  d, keep = scene_desc(scene)
+  lim = LimitsDesc(float(limits.max_ray_length), int(limits.max_intersections), float(limits.dist_tol),
+                   float(limits.power_tol))
+  kinds = _arr(scene.group_disp_kind, np.int32)
+  buf = C.create_string_buffer(1 << 20)
+  size = C.c_uint64(0)
+  f = lib().odw_compile_check_bands
+  f.argtypes = [C.POINTER(SceneDescCoef), C.POINTER(LimitsDesc), C.c_char_p, C.POINTER(SourceDesc), _pi, C.c_int32, C.c_char_p,
+                C.c_uint64, C.POINTER(C.c_uint64)]
+  sd, keep_source = source_desc(source) if source is not None else (None, None)
+  rc = f(C.byref(d), C.byref(lim), arch.encode() if arch else None, C.byref(sd) if sd is not None else None,
+         kinds.ctypes.data_as(_pi), 1 if power else 0, buf, len(buf), C.byref(size))
+  check(None, rc, 'odw_compile_check_bands')
+  return buf.value.decode(), int(size.value)
+
+
+def band_edges_check(edges):
+  """Host only (no GPU): `odw_set_detector_bands`' check of the edges, without a context; raises NativeError naming the edge"""
+  e = np.ascontiguousarray(edges, np.float64).ravel()
+  f = lib().odw_set_detector_bands
+  f.argtypes = [C.c_void_p, C.c_int32, _pd]
+  check(None, f(None, len(e), e.ctypes.data_as(_pd)), 'odw_set_detector_bands')
+
+
+def band_index(edges, wavelengths, device=False):
+  """The band (int32; -1: none) of every wavelength among `edges` (nm), numpy.histogram's rule (`odw_band_index`); device:
+  by the trace kernels' own search on the current GPU, else on the host (no GPU needed)"""
+  e = np.ascontiguousarray(edges, np.float64).ravel()
+  w = np.ascontiguousarray(wavelengths, np.float64)
+  out = np.empty(w.shape, np.int32)
+  f = lib().odw_band_index
+  f.argtypes = [_pd, C.c_int32, _pd, C.c_uint64, _pi, C.c_int32]
+  check(None, f(e.ctypes.data_as(_pd), len(e), w.ctypes.data_as(_pd), w.size, out.ctypes.data_as(_pi), 1 if device else 0), 'odw_band_index')
+  return out
 
 
 def compile_check_fresnel(scene, limits, arch=None, source=None, modes=None):

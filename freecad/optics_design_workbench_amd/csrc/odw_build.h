@@ -151,6 +151,41 @@ inline double disp_index(int kind, const double* coef, double wavelength_nm) {
   return std::numeric_limits<double>::quiet_NaN();
 }
 
+// The band of a wavelength among n_edges strictly increasing edges (odw_set_detector_bands), numpy.histogram's rule:
+// e_b <= wl < e_(b+1), wl == e_K in band K - 1, -1 outside [e_0, e_K] and for NaN.  Plain float64 comparisons -- the
+// device twin (odw_kernels.hip: band_index_dev) is the same expression, and numpy.searchsorted(edges, wl, 'right') - 1
+// with the last edge folded in is what the tests hold both against.
+inline int band_index(const double* edges, int n_edges, double wl) {
+  int c = 0;
+  for (int k = 0; k < n_edges; ++k) c += wl >= edges[k] ? 1 : 0;
+  return c == n_edges ? (wl == edges[n_edges - 1] ? n_edges - 2 : -1) : c - 1;
+}
+
+// odw_set_detector_bands' check of the edges (`who`: the entry point named in the message)
+inline int bands_validate(const char* who, int n_edges, const double* edges, std::string& err) {
+  char buf[200];
+  if (n_edges < 2 || !edges) {
+    std::snprintf(buf, sizeof buf, "%s: band edges: at least two edges (one band) are needed", who);
+    err = buf;
+    return ODW_ERR_INVALID;
+  }
+  if (n_edges - 1 > ODW_BAND_MAX) {
+    std::snprintf(buf, sizeof buf, "%s: %d bands: a detector takes at most ODW_BAND_MAX = %d", who, n_edges - 1, ODW_BAND_MAX);
+    err = buf;
+    return ODW_ERR_INVALID;
+  }
+  for (int k = 0; k < n_edges; ++k) {
+    const char* what = !std::isfinite(edges[k]) ? "is not finite" : !(edges[k] > 0) ? "is not positive"
+                       : (k > 0 && !(edges[k] > edges[k - 1])) ? "is not above its predecessor (edges must be strictly increasing)" : nullptr;
+    if (what) {
+      std::snprintf(buf, sizeof buf, "%s: band edge %d (%.17g nm) %s", who, k, edges[k], what);
+      err = buf;
+      return ODW_ERR_INVALID;
+    }
+  }
+  return ODW_OK;
+}
+
 // odw_set_dispersion's check of kind / coef; group_i32 (may be null: no scene at hand) adds the groups' types
 inline int disp_validate(int n_groups, const int32_t* kind, const double* coef, const int32_t* group_i32, std::string& err) {
   if (n_groups < 0 || n_groups > ODW_MAX_GROUPS || (n_groups && (!kind || !coef)))

@@ -108,7 +108,7 @@ struct odw_ctx {
   DeviceDetector h_det;
   DevBuf hits, hit_count, chunk_counter;
   // ONE block holds what ranks sum: [kResultsHead words: the ODW_CNT_COUNT counters, padded] [n_bins histogram words]
-  // [power_on: n_bins words of the power plane]
+  // [power_on: n_bins words of the power plane] [band_n: K * n_bins band counts] [band_n and power_on: K * n_bins band power]
   // -- a multi-GPU job reduces it with a single collective (odw_device_results); `counters` and `hist` are views into it
   DevBuf results, hist, counters;
   DevBuf segs, seg_count;                  // RecordRays segment list
@@ -139,6 +139,12 @@ struct odw_ctx {
   bool emitter_active = false;   // the most recently uploaded source is a surface source
   uint64_t hit_capacity = 0, n_bins = 0;   // hit_capacity: rows the caller asked for
   bool power_on = false;                   // odw_enable_power_histogram: n_bins words of hit weights directly behind the histogram
+  int band_n = 0;                          // odw_set_detector_bands: edges (K + 1; 0: no bands) -- K count planes behind the power
+  double band_edges[ODW_BAND_MAX + 1] = {};//   plane's place, then with power_on K power planes
+  DevBuf d_band_edges;
+  uint64_t band_k() const { return band_n ? (uint64_t)band_n - 1 : 0; }
+  // words behind the counters: (1 + P)(1 + K) planes of n_bins
+  uint64_t plane_words() const { return n_bins * (power_on ? 2 : 1) * (1 + band_k()); }
   uint64_t hit_slots = 0;                  // rows allocated (capacity + slack for block reservations)
   // batch launches (odw_upload_scene_batch / odw_trace_batch): the value tables of batch_n scenes of one structure side by
   // side, one segment of the batch's hit list and one pair of counters per scene.  odw_batch_select makes a segment the
@@ -207,6 +213,8 @@ struct odw_ctx {
   double spec_lo = 0, spec_hi = 0;         // its ends (nm)
   hipFunction_t spec_chroma_fn[2] = {nullptr, nullptr};   // the compiled kernel's variants for spectral launches: without / with the power plane
   bool spec_chroma_failed = false;         // ... could not be built for this binding: spectral launches walk the tree
+  hipFunction_t spec_bands_fn[2] = {nullptr, nullptr};    // ... and their BANDS variants (band planes): without / with the power plane
+  bool spec_bands_failed = false;
   SpecLayout spec_chroma_layout;           // ... and their value image (the plain one + the dispersion coefficients)
   DevBuf chroma_nodes, chroma_prims;       // the binary tree spectral launches walk in a scene that has none of its own
   int chroma_n_nodes = 0;                  // 0: to be built
@@ -565,6 +573,9 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   const bool spectral = ray_wl != nullptr || (!explicit_rays && ctx->spec_n > 0);
   if (ctx->batch_launch && ctx->disp_on)
     return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: a batch with a dispersion set (per-scene dispersion is out of scope)");
+  if (ctx->batch_launch && ctx->band_n)
+    return fail(ctx, ODW_ERR_UNSUPPORTED, "odw_trace_batch: a batch with detector bands set (band planes: batches carry no spectrum, and one detector "
+                                          "cannot serve several scenes; clear them with odw_set_detector_bands(ctx, 0, NULL))");
   if (spectral) {
     if (ctx->batch_launch) return fail(ctx, ODW_ERR_UNSUPPORTED, "spectral launch: batches carry no spectrum (spectral batches are out of scope)");
     if (ctx->n_samplers > 0) return fail(ctx, ODW_ERR_UNSUPPORTED, "spectral launch: scenes with stochastic surfaces are not supported");
@@ -619,6 +630,15 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   if ((flags & ODW_TRACE_HISTOGRAM) && !ctx->P.det_enabled) flags &= ~ODW_TRACE_HISTOGRAM;
   // (the kernels add to the words behind the histogram under this flag: never without a plane there)
   if (!(flags & ODW_TRACE_HISTOGRAM) || !ctx->power_on) flags &= ~(uint32_t)ODW_TRACE_POWER_HISTOGRAM;
+  // (likewise the band planes; a launch that asks for them and cannot fill them is refused, not run without)
+  if (!(flags & ODW_TRACE_HISTOGRAM) || !ctx->band_n) flags &= ~(uint32_t)ODW_TRACE_BAND_HISTOGRAM;
+  const bool bands = (flags & ODW_TRACE_BAND_HISTOGRAM) != 0;     // the BANDS kernels: DeviceBands in DeviceChroma's place
+  if (bands) {
+    if (!spectral) return fail(ctx, ODW_ERR_UNSUPPORTED, "band planes: the launch is monochromatic (no spectrum bound, no wavelength per ray): "
+                                                         "its total plane is its one band's plane; bands for monochromatic launches are out of scope");
+    if (flags & ODW_TRACE_RECORD_SEGMENTS) return fail(ctx, ODW_ERR_UNSUPPORTED, "band planes: a launch with ODW_TRACE_RECORD_SEGMENTS (record_segments) cannot fill them");
+    if (!ctx->d_band_edges.p) return fail(ctx, ODW_ERR_DEVICE, "band planes without their edge table");
+  }
   TraceParams& P = ctx->P;
   const bool batch = ctx->batch_launch;
   std::memset(&P.batch, 0, sizeof P.batch);
@@ -695,7 +715,16 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // while the single-scene kernel is bound, ODW_COMPILE_STRUCTURE only; one attempt per binding, and a variant that cannot
   // be built does not become the error of a launch that succeeds on the tree
   const bool segments = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0;
-  if (spectral && !fresnel && !segments && ctx->spec_fn && !ctx->spec_chroma_fn[pw] && !ctx->spec_chroma_failed) {
+  if (bands && !fresnel && ctx->spec_fn && !ctx->spec_bands_fn[pw] && !ctx->spec_bands_failed) {
+    // (its BANDS variant: on the first spectral launch with band planes, under the same rules)
+    const std::string keep_err = ctx->err;
+    if (spec_bind(ctx, pw ? kSpecBandsPower : kSpecBands) != ODW_OK) {
+      ctx->spec_bands_fn[pw] = nullptr;
+      ctx->spec_bands_failed = true;
+      ctx->err = keep_err;
+    }
+  }
+  if (spectral && !bands && !fresnel && !segments && ctx->spec_fn && !ctx->spec_chroma_fn[pw] && !ctx->spec_chroma_failed) {
     const std::string keep_err = ctx->err;
     if (spec_bind(ctx, pw ? kSpecChromaPower : kSpecChroma) != ODW_OK) {
       ctx->spec_chroma_fn[pw] = nullptr;
@@ -716,14 +745,23 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
   // (after the bindings above: they decide `compiled`.)  A spectral launch goes to the compiled kernel when its CHROMA
   // variant is bound for the scene as it is, else to the binary tree -- never to the flat, grid or mesh kernel, which know
   // no wavelength per ray
-  const bool chroma_compiled = spectral && !fresnel && !segments && ctx->spec_fn && ctx->spec_chroma_fn[pw] && ctx->spec_lean == ctx->hs.lean;
+  const hipFunction_t chroma_fn = bands ? ctx->spec_bands_fn[pw] : ctx->spec_chroma_fn[pw];
+  const bool chroma_compiled = spectral && !fresnel && !segments && ctx->spec_fn && chroma_fn && ctx->spec_lean == ctx->hs.lean;
   // A launch with a Fresnel mode set: the compiled kernel's FRESNEL variant where it is bound for the scene as it is and the
   // launch is monochromatic, else the binary tree (spectral + Fresnel: always) -- never the flat, grid or mesh kernel
   const bool fresnel_compiled = fresnel && !spectral && !segments && ctx->spec_fn && ctx->spec_fresnel_fn[pw] && ctx->spec_lean == ctx->hs.lean;
   const TraceKernel kernel = fresnel ? (fresnel_compiled ? TraceKernel::compiled : TraceKernel::tree)
                              : spectral ? (chroma_compiled ? TraceKernel::compiled : TraceKernel::tree) : choose_kernel(ctx, flags, batch);
-  DeviceChroma chroma;
+  DeviceBands chroma;                      // (the CHROMA kernels without BANDS take its DeviceChroma part)
   std::memset(&chroma, 0, sizeof chroma);
+  if (bands) {
+    chroma.band_edges = (const double*)ctx->d_band_edges.p;
+    chroma.n_edges = ctx->band_n;
+    chroma.n_bins = (int32_t)ctx->n_bins;
+    chroma.count_off = ctx->n_bins * (ctx->power_on ? 2 : 1);
+    chroma.power_off = chroma.count_off + ctx->n_bins * ctx->band_k();
+  }
+  const DeviceChroma& chroma_only = chroma;
   DeviceFresnel fresnel_arg;
   fresnel_arg.mode = (const int32_t*)ctx->d_fresnel_mode.p;
   const bool coated = fresnel && ctx->coat_on;
@@ -849,17 +887,26 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
     }
     // (a coating on some group: the COAT instantiations; without, the kernels of before)
 #define ODW_FRESNEL_LAUNCH(S, W, A, C) do { \
-      if (coated) hipLaunchKernelGGL((odw_trace_coat_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, coat_arg); \
-      else hipLaunchKernelGGL((odw_trace_fresnel_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, fresnel_arg); } while (0)
+      if (coated) hipLaunchKernelGGL((odw_trace_coat_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma_only, coat_arg); \
+      else hipLaunchKernelGGL((odw_trace_fresnel_kernel<S, W, A, C>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma_only, fresnel_arg); } while (0)
+    // (band planes: spectral, no segment rows -- the BANDS kernels, POWER x ASPH)
+#define ODW_FRESNEL_BANDS_LAUNCH(W, A) do { \
+      if (coated) hipLaunchKernelGGL((odw_trace_coat_bands_kernel<W, A>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, coat_arg); \
+      else hipLaunchKernelGGL((odw_trace_fresnel_bands_kernel<W, A>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma, fresnel_arg); } while (0)
 #define ODW_FRESNEL_LAUNCH_C(S, W, A) do { if (spectral) ODW_FRESNEL_LAUNCH(S, W, A, true); else ODW_FRESNEL_LAUNCH(S, W, A, false); } while (0)
 #define ODW_FRESNEL_LAUNCH_A(S, W) do { if (asph) ODW_FRESNEL_LAUNCH_C(S, W, true); else ODW_FRESNEL_LAUNCH_C(S, W, false); } while (0)
+    if (bands) {
+      if (pw) { if (asph) ODW_FRESNEL_BANDS_LAUNCH(true, true); else ODW_FRESNEL_BANDS_LAUNCH(true, false); }
+      else { if (asph) ODW_FRESNEL_BANDS_LAUNCH(false, true); else ODW_FRESNEL_BANDS_LAUNCH(false, false); }
+    } else
     if (segments) { if (pw) ODW_FRESNEL_LAUNCH_A(true, true); else ODW_FRESNEL_LAUNCH_A(true, false); }
     else { if (pw) ODW_FRESNEL_LAUNCH_A(false, true); else ODW_FRESNEL_LAUNCH_A(false, false); }
+#undef ODW_FRESNEL_BANDS_LAUNCH
 #undef ODW_FRESNEL_LAUNCH_A
 #undef ODW_FRESNEL_LAUNCH_C
 #undef ODW_FRESNEL_LAUNCH
   } else if (chroma_compiled) {
-    int rc = spec_launch(ctx, grid, ctx->spec_chroma_fn[pw], false, &chroma);
+    int rc = spec_launch(ctx, grid, chroma_fn, false, &chroma, false, bands ? sizeof(DeviceBands) : sizeof(DeviceChroma));
     if (rc) return rc;
   } else if (spectral) {
     Pc = P;
@@ -869,10 +916,16 @@ int launch_trace(odw_ctx* ctx, uint64_t first, uint64_t n, uint64_t seed, uint32
       Pc.scene.n_nodes = ctx->chroma_n_nodes;
     }
     const bool seg = (flags & ODW_TRACE_RECORD_SEGMENTS) != 0;
-#define ODW_CHROMA_LAUNCH(S, W, A) hipLaunchKernelGGL((odw_trace_chroma_kernel<S, W, A>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma)
+#define ODW_CHROMA_LAUNCH(S, W, A) hipLaunchKernelGGL((odw_trace_chroma_kernel<S, W, A>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma_only)
+#define ODW_CHROMA_BANDS_LAUNCH(W, A) hipLaunchKernelGGL((odw_trace_chroma_bands_kernel<W, A>), dim3(grid), dim3(256), lds, ctx->stream, Pc, chroma)
 #define ODW_CHROMA_LAUNCH_A(S, W) do { if (asph) ODW_CHROMA_LAUNCH(S, W, true); else ODW_CHROMA_LAUNCH(S, W, false); } while (0)
+    if (bands) {
+      if (pw) { if (asph) ODW_CHROMA_BANDS_LAUNCH(true, true); else ODW_CHROMA_BANDS_LAUNCH(true, false); }
+      else { if (asph) ODW_CHROMA_BANDS_LAUNCH(false, true); else ODW_CHROMA_BANDS_LAUNCH(false, false); }
+    } else
     if (seg) { if (pw) ODW_CHROMA_LAUNCH_A(true, true); else ODW_CHROMA_LAUNCH_A(true, false); }
     else { if (pw) ODW_CHROMA_LAUNCH_A(false, true); else ODW_CHROMA_LAUNCH_A(false, false); }
+#undef ODW_CHROMA_BANDS_LAUNCH
 #undef ODW_CHROMA_LAUNCH_A
 #undef ODW_CHROMA_LAUNCH
   } else if (use_spec) {
@@ -1090,7 +1143,7 @@ void odw_destroy(odw_ctx* ctx) {
                     &ctx->em_t_tab, &ctx->em_t_guide, &ctx->em_o, &ctx->em_d, &ctx->em_tri_nrm, &ctx->tri_nrm, &ctx->phi_guide, &ctx->asph})
     release(*b);
   for (DevBuf* b : {&ctx->d_disp_kind, &ctx->d_disp_coef, &ctx->spec_tab, &ctx->ray_wl, &ctx->wl_rays, &ctx->wl_out, &ctx->chroma_nodes,
-                    &ctx->chroma_prims, &ctx->d_fresnel_mode, &ctx->fr_in, &ctx->fr_out, &ctx->d_coat_n, &ctx->d_coat, &ctx->coat_layers})
+                    &ctx->chroma_prims, &ctx->d_band_edges, &ctx->d_fresnel_mode, &ctx->fr_in, &ctx->fr_out, &ctx->d_coat_n, &ctx->d_coat, &ctx->coat_layers})
     release(*b);
   for (auto& sb : ctx->surf_bufs) { release(sb.phi_tab); release(sb.t_tab); release(sb.t_guide); }
   release(ctx->d_samplers);
@@ -1402,6 +1455,8 @@ int odw_set_dispersion(odw_ctx* ctx, int32_t n_groups, const int32_t* kind, cons
   // (the groups' formulas are part of the compiled CHROMA variant's header: bound again by the next spectral launch)
   ctx->spec_chroma_fn[0] = ctx->spec_chroma_fn[1] = nullptr;
   ctx->spec_chroma_failed = false;
+  ctx->spec_bands_fn[0] = ctx->spec_bands_fn[1] = nullptr;
+  ctx->spec_bands_failed = false;
   return upload_dispersion(ctx);
 }
 
@@ -1411,8 +1466,31 @@ int odw_compiled_chroma_info(odw_ctx* ctx, int32_t* bound) {
   return ODW_OK;
 }
 
+int odw_compiled_bands_info(odw_ctx* ctx, int32_t* bound) {
+  if (!ctx || !bound) return fail(ctx, ODW_ERR_INVALID, "odw_compiled_bands_info: bad argument");
+  *bound = (ctx->spec_fn && (ctx->spec_bands_fn[0] || ctx->spec_bands_fn[1]) && !ctx->spec_dirty && !ctx->bvh_dirty) ? ctx->compile_mode : 0;
+  return ODW_OK;
+}
+
+namespace {
+// odw_compile_check_chroma (bands = false: its header and kernel as ever) and odw_compile_check_bands
+int compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                         const int32_t* disp_kind, bool bands, bool power, char* header_out, uint64_t header_capacity, uint64_t* code_bytes);
+}  // namespace
+
 int odw_compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
                              const int32_t* disp_kind, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
+  return compile_check_chroma(scene, limits, arch, source, disp_kind, false, false, header_out, header_capacity, code_bytes);
+}
+
+int odw_compile_check_bands(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                            const int32_t* disp_kind, int32_t power, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
+  return compile_check_chroma(scene, limits, arch, source, disp_kind, true, power != 0, header_out, header_capacity, code_bytes);
+}
+
+namespace {
+int compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limits, const char* arch, const odw_source_desc* source,
+                         const int32_t* disp_kind, bool bands, bool power, char* header_out, uint64_t header_capacity, uint64_t* code_bytes) {
   if (!scene || !limits || !disp_kind) return fail(nullptr, ODW_ERR_INVALID, "odw_compile_check_chroma: bad argument");
   HostScene tmp;
   std::string refusal;
@@ -1422,8 +1500,9 @@ int odw_compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limi
   compute_boxes(tmp, limits->dist_tol, boxes);
   const std::string why = spec_ineligible(tmp);
   if (!why.empty()) return fail(nullptr, ODW_ERR_UNSUPPORTED, "odw_compile_check_chroma: " + why);
-  const std::string text = spec_text(tmp, 0, disp_kind) +
-      (source ? spec_source_text(spec_source_key(source->xform, source->n_t_rows, true, std::isfinite(source->focal_length))) : "");
+  const std::string text = spec_text(tmp, 0, disp_kind, nullptr, nullptr, bands) +
+      (source ? spec_source_text(spec_source_key(source->xform, source->n_t_rows, true, std::isfinite(source->focal_length))) : "") +
+      (power ? "#define ODW_SPEC_POWER true\n" : "");
   if (header_out && header_capacity) {
     const size_t k = std::min<size_t>(text.size(), (size_t)header_capacity - 1);
     std::memcpy(header_out, text.data(), k);
@@ -1435,6 +1514,7 @@ int odw_compile_check_chroma(const odw_scene_desc* scene, const odw_limits* limi
   if (code_bytes) *code_bytes = code.size();
   return ODW_OK;
 }
+}  // namespace
 
 int odw_set_spectrum(odw_ctx* ctx, int32_t mode, int32_t n_knots, const double* wavelength_nm, const double* cdf) {
   if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_set_spectrum: null ctx");
@@ -2051,6 +2131,7 @@ int odw_set_detector(odw_ctx* ctx, const odw_detector_desc* det) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   DeviceDetector& d = ctx->h_det;
   ctx->power_on = false;                 // (the power plane belongs to one detector: enabled again after every call)
+  ctx->band_n = 0;                       // (... and so do the band planes)
   if (!det) { d.enabled = 0; ctx->P.det_enabled = 0; ctx->n_bins = 0; return ODW_OK; }
   if (det->nx <= 0 || det->ny <= 0 || !(det->x_hi > det->x_lo) || !(det->y_hi > det->y_lo))
     return fail(ctx, ODW_ERR_INVALID, "odw_set_detector: bad window");
@@ -2543,7 +2624,7 @@ int odw_reset_results(odw_ctx* ctx) {
   HIPCHK(ctx, hipMemsetAsync(ctx->counters.p, 0, ODW_CNT_COUNT * sizeof(uint64_t), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->hit_count.p, 0, 2 * sizeof(uint64_t), ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->seg_count.p, 0, sizeof(uint64_t), ctx->stream));
-  if (ctx->n_bins) HIPCHK(ctx, hipMemsetAsync(ctx->hist.p, 0, ctx->n_bins * (ctx->power_on ? 2 : 1) * sizeof(uint64_t), ctx->stream));
+  if (ctx->n_bins) HIPCHK(ctx, hipMemsetAsync(ctx->hist.p, 0, ctx->plane_words() * sizeof(uint64_t), ctx->stream));
   return ODW_OK;
 }
 
@@ -2785,14 +2866,26 @@ int odw_fetch_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins) {
 
 int odw_enable_power_histogram(odw_ctx* ctx, int on) {
   if (!ctx) return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: null ctx");
-  if (!on) { ctx->power_on = false; return ODW_OK; }
+  if (!on) {
+    // (with bands the band count planes move up into the power plane's place: laid out again, zeroed)
+    if (ctx->power_on && ctx->band_n) {
+      HIPCHK(ctx, hipSetDevice(ctx->device));
+      HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+      HIPCHK(ctx, hipMemsetAsync((uint64_t*)ctx->hist.p + ctx->n_bins, 0, ctx->n_bins * ctx->band_k() * sizeof(uint64_t), ctx->stream));
+    }
+    ctx->power_on = false;
+    return ODW_OK;
+  }
   if (!ctx->P.det_enabled || ctx->n_bins == 0) return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: odw_set_detector first");
   if (ctx->n_bins >= (1ull << 31)) return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: a power plane takes fewer than 2^31 bins");
+  if (2 * ctx->n_bins * (1 + ctx->band_k()) >= (1ull << 31))
+    return fail(ctx, ODW_ERR_INVALID, "odw_enable_power_histogram: with the detector's bands the results block would take 2^31 words or more");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // a running launch may still write the old block
-  int rc = ensure_results(ctx, 2 * ctx->n_bins, ctx->n_bins);
+  int rc = ensure_results(ctx, 2 * ctx->n_bins * (1 + ctx->band_k()), ctx->n_bins);
   if (rc) return rc;
-  HIPCHK(ctx, hipMemsetAsync((uint64_t*)ctx->hist.p + ctx->n_bins, 0, ctx->n_bins * sizeof(uint64_t), ctx->stream));
+  // (the power plane, and with bands every band plane: the block is laid out again)
+  HIPCHK(ctx, hipMemsetAsync((uint64_t*)ctx->hist.p + ctx->n_bins, 0, ctx->n_bins * (1 + 2 * ctx->band_k()) * sizeof(uint64_t), ctx->stream));
   ctx->power_on = true;
   return ODW_OK;
 }
@@ -2813,6 +2906,109 @@ int odw_fetch_power_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins) {
       return fail(ctx, ODW_ERR_CAPACITY, "odw_fetch_power_histogram: bin " + std::to_string(k) + " holds " + std::to_string(counts[k]) +
                   " hits (>= 2^32): its power sum may have wrapped");
     }
+  return ODW_OK;
+}
+
+int odw_set_detector_bands(odw_ctx* ctx, int32_t n_edges, const double* edges_nm) {
+  // (without a context: the check of the edges alone, as odw_dispersion_check checks a dispersion)
+  if (n_edges != 0) {
+    std::string err;
+    const int rc = bands_validate("odw_set_detector_bands", n_edges, edges_nm, err);
+    if (rc) return fail(ctx, rc, err);
+  }
+  if (!ctx) return n_edges ? ODW_OK : fail(ctx, ODW_ERR_INVALID, "odw_set_detector_bands: null ctx");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (n_edges == 0) {
+    if (ctx->band_n) HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->band_n = 0;
+    return ODW_OK;
+  }
+  if (!ctx->P.det_enabled || ctx->n_bins == 0) return fail(ctx, ODW_ERR_INVALID, "odw_set_detector_bands: bands need a detector (odw_set_detector first)");
+  const uint64_t K = (uint64_t)n_edges - 1, planes = (ctx->power_on ? 2 : 1) * (1 + K);
+  if (ctx->n_bins * planes >= (1ull << 31)) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "odw_set_detector_bands: %llu planes of %llu bins: the results block must stay below 2^31 words "
+                  "(the kernels index it with 32-bit products)", (unsigned long long)planes, (unsigned long long)ctx->n_bins);
+    return fail(ctx, ODW_ERR_INVALID, buf);
+  }
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));   // a running launch may still write the old block / read the old edges
+  const uint64_t front = ctx->n_bins * (ctx->power_on ? 2 : 1);
+  int rc = ensure_results(ctx, ctx->n_bins * planes, front);
+  if (rc) return rc;
+  if ((rc = upload(ctx, ctx->d_band_edges, edges_nm, (size_t)n_edges * sizeof(double)))) return rc;
+  std::memcpy(ctx->band_edges, edges_nm, (size_t)n_edges * sizeof(double));
+  ctx->band_n = n_edges;
+  HIPCHK(ctx, hipMemsetAsync((uint64_t*)ctx->hist.p + front, 0, (ctx->n_bins * planes - front) * sizeof(uint64_t), ctx->stream));
+  return ODW_OK;
+}
+
+int odw_fetch_band_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_words) {
+  if (!ctx || !out) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_histogram: bad argument");
+  if (!ctx->band_n || !ctx->n_bins) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_histogram: no bands (odw_set_detector_bands)");
+  if (n_words != ctx->band_k() * ctx->n_bins) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_histogram: word count mismatch (K * nx * ny)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const uint64_t* src = (const uint64_t*)ctx->hist.p + ctx->n_bins * (ctx->power_on ? 2 : 1);
+  HIPCHK(ctx, hipMemcpyAsync(out, src, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  return ODW_OK;
+}
+
+int odw_fetch_band_power_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_words) {
+  if (!ctx || !out) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_power_histogram: bad argument");
+  if (!ctx->band_n || !ctx->n_bins) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_power_histogram: no bands (odw_set_detector_bands)");
+  if (!ctx->power_on) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_power_histogram: no power plane (odw_enable_power_histogram)");
+  if (n_words != ctx->band_k() * ctx->n_bins) return fail(ctx, ODW_ERR_INVALID, "odw_fetch_band_power_histogram: word count mismatch (K * nx * ny)");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<uint64_t> counts(n_words);
+  const uint64_t* src = (const uint64_t*)ctx->hist.p + 2 * ctx->n_bins;
+  HIPCHK(ctx, hipMemcpyAsync(counts.data(), src, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(out, src + n_words, n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  // (odw_fetch_power_histogram's rule, per band plane)
+  for (uint64_t k = 0; k < n_words; ++k)
+    if (counts[k] >> 32) {
+      std::memset(out, 0, n_words * sizeof(uint64_t));
+      return fail(ctx, ODW_ERR_CAPACITY, "odw_fetch_band_power_histogram: band " + std::to_string(k / ctx->n_bins) + ", bin " + std::to_string(k % ctx->n_bins) +
+                  " holds " + std::to_string(counts[k]) + " hits (>= 2^32): its power sum may have wrapped");
+    }
+  return ODW_OK;
+}
+
+int odw_band_index(const double* edges_nm, int32_t n_edges, const double* wavelengths_nm, uint64_t n, int32_t* out_i32, int32_t on_device) {
+  std::string err;
+  const int vrc = bands_validate("odw_band_index", n_edges, edges_nm, err);
+  if (vrc) return fail(nullptr, vrc, err);
+  if (n && (!wavelengths_nm || !out_i32)) return fail(nullptr, ODW_ERR_INVALID, "odw_band_index: bad argument");
+  if (!on_device) {
+    for (uint64_t i = 0; i < n; ++i) out_i32[i] = band_index(edges_nm, n_edges, wavelengths_nm[i]);
+    return ODW_OK;
+  }
+  if (n == 0) return ODW_OK;
+  // (context-free: buffers of its own on the current device, the null stream)
+  odw_ctx* const ctx = nullptr;
+  DevBuf e, w, o;
+  hipError_t he = hipMalloc(&e.p, (size_t)n_edges * sizeof(double));
+  if (he == hipSuccess) he = hipMalloc(&w.p, n * sizeof(double));
+  if (he == hipSuccess) he = hipMalloc(&o.p, n * sizeof(int32_t));
+  if (he == hipSuccess) he = hipMemcpy(e.p, edges_nm, (size_t)n_edges * sizeof(double), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(w.p, wavelengths_nm, n * sizeof(double), hipMemcpyHostToDevice);
+  if (he == hipSuccess) {
+    const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + 255) / 256, 4096));
+    hipLaunchKernelGGL(odw_band_index_kernel, dim3(grid), dim3(256), 0, nullptr, (const double*)e.p, (int)n_edges, (const double*)w.p, n, (int32_t*)o.p);
+    he = hipGetLastError();
+  }
+  if (he == hipSuccess) he = hipMemcpy(out_i32, o.p, n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  for (DevBuf* b : {&e, &w, &o}) if (b->p) (void)hipFree(b->p);
+  HIPCHK(ctx, he);
+  return ODW_OK;
+}
+
+int odw_device_band_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_words) {
+  if (!ctx || !dptr || !n_words) return fail(ctx, ODW_ERR_INVALID, "odw_device_band_histogram: bad argument");
+  const bool on = ctx->band_n && ctx->n_bins;
+  const uint64_t front = ctx->n_bins * (ctx->power_on ? 2 : 1);
+  *dptr = on ? (void*)((uint64_t*)ctx->hist.p + front) : nullptr;
+  *n_words = on ? ctx->plane_words() - front : 0;
   return ODW_OK;
 }
 
@@ -2838,7 +3034,7 @@ int odw_sample(odw_ctx* ctx, uint64_t first_ray, uint64_t n_rays, uint64_t seed,
 int odw_device_results(odw_ctx* ctx, void** dptr, uint64_t* n_words, uint64_t* hist_offset_words) {
   if (!ctx || !dptr || !n_words || !hist_offset_words) return fail(ctx, ODW_ERR_INVALID, "odw_device_results: bad argument");
   *dptr = ctx->results.p;
-  *n_words = kResultsHead + ctx->n_bins * (ctx->power_on ? 2 : 1);
+  *n_words = kResultsHead + ctx->plane_words();
   *hist_offset_words = kResultsHead;
   return ODW_OK;
 }

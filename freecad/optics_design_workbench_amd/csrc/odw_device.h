@@ -256,6 +256,16 @@ struct DeviceChroma {
   const double* disp_coef;      // [ODW_MAX_GROUPS * ODW_DISP_COEFS]
 };
 
+// ... of the BANDS instantiations (spectral launches that fill the detector's band planes, odw_set_detector_bands): DeviceChroma
+// and the band edges.  The CHROMA kernels without BANDS keep the argument -- and with it the argument segment -- they had.
+// The planes lie in the results block behind the histogram (and its power plane): K count planes from word count_off of
+// P.out.hist on, K power planes from word power_off on, band-major.
+struct DeviceBands : DeviceChroma {
+  const double* band_edges;     // [n_edges] nm, strictly increasing
+  int32_t n_edges, n_bins;      // K + 1; nx * ny of the detector
+  uint64_t count_off, power_off;
+};
+
 // Kernel argument of the FRESNEL instantiations of the binary tree (launches with a Fresnel mode on some lens group),
 // behind DeviceChroma.  A kernel compiled against the scene carries the modes in its header instead (Spec::fresnel(G)).
 struct DeviceFresnel {

@@ -2062,11 +2062,28 @@ __device__ __forceinline__ unsigned long long power_quanta(double power) {
   const double c = power > 0.0 ? fmin(power, ODW_POWER_MAX) : 0.0;     // (NaN > 0 is false)
   return (unsigned long long)(long long)rint(c * (double)(1ull << ODW_POWER_QUANTUM_BITS));   // (exact product; nearest, ties to even)
 }
+// The band of a wavelength among n_edges strictly increasing edges: the device twin of band_index (odw_build.h) -- the
+// same float64 comparisons, so numpy.histogram's rule to the bit: e_b <= wl < e_(b+1), wl == e_K in band K - 1, -1
+// outside [e_0, e_K] and for NaN.  The edge index is the loop's counter -- wave-uniform, scalar loads through a pointer
+// in the constant address space --, the count a sum of compare results: no array indexed by lane, no call.
+template <class CP>
+__device__ __forceinline__ int band_index_dev(CP edges, int n_edges, double wl) {
+  int c = 0;
+  for (int k = 0; k < n_edges; ++k) c += wl >= edges[k] ? 1 : 0;
+  return c == n_edges ? (wl == edges[n_edges - 1] ? n_edges - 2 : -1) : c - 1;
+}
+// The band planes (ODW_TRACE_BAND_HISTOGRAM, include/odw_trace.h): K count planes and, with the power plane, K planes of
+// hit weights behind the histogram, band-major.  BANDS is a template parameter for the reason POWER is one; only the
+// kernels of spectral launches have the instantiation.  The band is found here, from the lane's wavelength at the
+// moment of recording -- a ray records once or twice in its life; a band carried through the ray loop would be one more
+// live register in kernels that spill --; u64 atomics in HBM, the LDS window keeps serving the total plane only.
+typedef const DeviceBands ODW_CONST* cbands;
 // PT: TraceParams, or TraceParams in the constant address space (the kernel's argument segment)
-template <bool BLOCKS, int CS = 256, bool CA = false, bool POWER = false, class PT>
+template <bool BLOCKS, int CS = 256, bool CA = false, bool POWER = false, bool BANDS = false, class PT>
 __device__ __forceinline__ void record_hit(const PT& P, uint64_t ray, int group, d3 p, d3 d,
                                            double power, bool entering, uint32_t* cnt,
-                                           volatile uint32_t* hit_state, uint32_t* win = nullptr) {
+                                           volatile uint32_t* hit_state, uint32_t* win = nullptr,
+                                           cbands B = nullptr, double wl = 0.0) {
   if (P.flags & ODW_TRACE_RECORD_HITS) {
     const uint64_t active = __ballot(1);
     const int lane = __lane_id();
@@ -2151,6 +2168,14 @@ __device__ __forceinline__ void record_hit(const PT& P, uint64_t ray, int group,
           atomicAdd(P.out.hist + ((size_t)ix * (size_t)det->ny + (size_t)iy), 1ull);
         if constexpr (POWER)        // (n_bins < 2^31: odw_enable_power_histogram)
           atomicAdd(P.out.hist + ((size_t)(det->nx * det->ny) + (size_t)(ix * det->ny + iy)), power_quanta(power));
+        if constexpr (BANDS) {      // (the whole block < 2^31 words: odw_set_detector_bands)
+          const int b = band_index_dev(as_const(B->band_edges), B->n_edges, wl);
+          if (b >= 0) {
+            const size_t at = (size_t)b * (size_t)B->n_bins + (size_t)(ix * det->ny + iy);
+            atomicAdd(P.out.hist + (B->count_off + at), 1ull);
+            if constexpr (POWER) atomicAdd(P.out.hist + (B->power_off + at), power_quanta(power));
+          }
+        }
       } else if (CA)
         atomicAdd(&cnt[ODW_CNT_HIST_OVERFLOW * CS], 1u);
       else
@@ -2173,6 +2198,21 @@ __device__ __noinline__ void record_hit_flat(ckargs kargs, uint64_t ray, int gro
   const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)) << 32) |
                      (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
   record_hit<true, 256, false, POWER>(*(ckargs)(uintptr_t)u, ray, group, p, d, power, entering, cnt, hit_state, win);
+}
+
+// ... of the compiled kernel's BANDS variant: the same with the band planes; bands: the address of the kernel's DeviceBands
+// argument in the argument segment (wave-uniform like kargs), wl: the lane's wavelength.  A function of its own: record_hit_flat keeps its name.
+template <bool POWER>
+__device__ __noinline__ void record_hit_flat_bands(ckargs kargs, uint64_t ray, int group, d3 p, d3 d, double power,
+                                                   bool entering, uint32_t* cnt, uint32_t* hit_state, uint32_t* win,
+                                                   cbands bands, double wl) {
+  const uint64_t a = (uint64_t)(uintptr_t)kargs, b = (uint64_t)(uintptr_t)bands;
+  const uint64_t u = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)) << 32) |
+                     (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
+  const uint64_t v = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(b >> 32)) << 32) |
+                     (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)b);
+  record_hit<true, 256, false, POWER, true>(*(ckargs)(uintptr_t)u, ray, group, p, d, power, entering, cnt, hit_state, win,
+                                            (cbands)(uintptr_t)v, wl);
 }
 
 // RecordRays (generic_source.py:78-118): one row per segment Ray.traceRay yields.  Only a
@@ -2300,18 +2340,35 @@ __device__ __forceinline__ double group_index(cf64 group_f64, int g, const Devic
 // COAT (FRESNEL launches with a thin-film coating on some group): ncoat layers at coat for the hit group -- the count a
 // constant where the scene is compiled in; with layers, R is the stack's (coated_reflectance_dev) at the launch's wavelength
 // or the ray's; without, and in every instantiation without COAT, the bare one as before.
+// BANDS (spectral launches with band planes): the kernel's argument behind TraceParams -- behind the value image's tail in
+// a compiled kernel -- is a DeviceBands; record_hit gets it and wl.  It is read where it lies, in the kernel's argument
+// segment (bands_arg), never through &C: the address of a by-value kernel argument is that of a copy in scratch memory,
+// which no constant-address-space load may touch.
+template <class SPEC>
+__device__ __forceinline__ cbands bands_arg() {
+  size_t off = (sizeof(TraceParams) + 7) & ~(size_t)7;
+  if constexpr (SPEC::enabled) off += sizeof(double*) + sizeof(double) * (size_t)(SPEC::img_fits ? SPEC::IMG : 4);    // (SpecTail)
+  return (cbands)((const char ODW_CONST*)__builtin_amdgcn_kernarg_segment_ptr() + off);
+}
 template <bool BVH, bool STOCH, bool LEAN, bool POWER = false, class SPEC = NoSpec, bool CHROMA = false, bool FRESNEL = false,
-          bool COAT = false>
+          bool COAT = false, bool BANDS = false>
 __device__ __forceinline__ void interact(const TraceParams& P, cf64 group_f64, ci32 group_i32, cf64 group_gdir, int g,
                                          int gtype, bool record, d3 n, bool entering, uint64_t ray, int nint,
                                          uint32_t* cnt, uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power,
                                          int& medium, int& seq, bool& alive, const DeviceChroma* C = nullptr, double wl = 0.0,
                                          int fmode = ODW_FRESNEL_NONE, int ncoat = 0, cf64 coat = nullptr) {
   static_assert(!COAT || FRESNEL, "coatings: launches with a Fresnel mode");
+  static_assert(!BANDS || CHROMA, "band planes: spectral launches");
   if (record) {
     cnt[ODW_CNT_RECORDED_HITS * 256] += 1u;
     // (block reservations and the histogram window only in the flat kernels: in the BVH kernels
     // their state costs more registers / LDS than the atomics cost time)
+    if constexpr (BANDS) {
+      cbands B = bands_arg<SPEC>();        // (interact is inlined into the kernel: the segment is the kernel's)
+      if (BVH) record_hit<false, 256, false, POWER, true>(P, ray, g, point, dir, power, entering, cnt, hit_state, nullptr, B, wl);
+      else record_hit_flat_bands<POWER>((ckargs)__builtin_amdgcn_kernarg_segment_ptr(), ray, g, point, dir, power, entering, cnt,
+                                        hit_state, win, B, wl);
+    } else
     if (BVH) record_hit<false, 256, false, POWER>(P, ray, g, point, dir, power, entering, cnt, hit_state);
     else record_hit_flat<POWER>((ckargs)__builtin_amdgcn_kernarg_segment_ptr(), ray, g, point, dir, power, entering, cnt,
                          hit_state, win);   // (interact is inlined into the kernel: the pointer is the kernel's)
@@ -2424,7 +2481,7 @@ constexpr int spec_coat_at(int g) {
 
 // the hit is on primitive PI of a compiled scene: its type, frame pattern, flags, group and the group's
 // optical type / recording switch are constants
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, bool COAT, int PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, bool COAT, bool BANDS, int PI>
 __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                          cf64 group_gdir, int face, uint64_t ray, int nint, uint32_t* cnt,
                                          uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
@@ -2449,7 +2506,7 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   constexpr int fmode = spec_fresnel<SPEC, FRESNEL>(g);
   // (COAT: the group's layer count from the header, its layers from the image -- a group without layers folds likewise)
   constexpr int ncoat = spec_coat<SPEC, COAT>(g);
-  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
+  interact<false, STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT, BANDS>(P, group_f64, group_i32, group_gdir, g, SPEC::gtype(g), SPEC::record(g), n, entering, ray,
                                nint, cnt, hit_state, win, point, dir, power, medium, seq, alive, C, wl, fmode, ncoat,
                                sv.img + spec_coat_at<SPEC, COAT>(g));
   // n points along the incoming travel direction: out of the solid when leaving it, into it when entering
@@ -2462,12 +2519,12 @@ __device__ __forceinline__ void spec_hit(const TraceParams& P, const SceneView& 
   if constexpr (spec_cand_solid<SPEC>(flags >> ODW_SOLID_SHIFT)) only = out < 0 ? (flags >> ODW_SOLID_SHIFT) : -1;
   else only = -1;
 }
-template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, bool COAT, int... PI>
+template <bool STOCH, bool LEAN, bool POWER, class SPEC, bool CHROMA, bool FRESNEL, bool COAT, bool BANDS, int... PI>
 __device__ __forceinline__ void spec_hits(const TraceParams& P, const SceneView& sv, cf64 group_f64, ci32 group_i32,
                                           cf64 group_gdir, int prim, int face, uint64_t ray, int nint, uint32_t* cnt,
                                           uint32_t* hit_state, uint32_t* win, d3 point, d3& dir, double& power, int& medium, int& seq,
                                           int& skip, int& only, bool& alive, const DeviceChroma* C, double wl, IndexList<int, PI...>) {
-  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
+  (void)((prim == PI ? (spec_hit<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT, BANDS, PI>(P, sv, group_f64, group_i32, group_gdir, face, ray, nint, cnt, hit_state, win,
                                                   point, dir, power, medium, seq, skip, only, alive, C, wl), true)
                      : false) || ...);
 }
@@ -2536,13 +2593,15 @@ template <> struct HitBlockState<false> {
 //   from DeviceFresnel (tree) or the header (compiled), handed to interact()
 // COAT (with FRESNEL): launches with a thin-film coating on some group -- the hit group's layers from DeviceCoat (tree) or
 //   header and value image (compiled), handed to interact()
+// BANDS (with CHROMA): launches that fill the detector's band planes -- C is a DeviceBands, handed to interact()
 template <bool BVH, bool STOCH, bool SEG, bool LEAN = false, class SPEC = NoSpec, bool BATCH = false, bool POWER = false,
-          class SRC = NoSource, bool ASPH = false, bool CHROMA = false, bool FRESNEL = false, bool COAT = false>
+          class SRC = NoSource, bool ASPH = false, bool CHROMA = false, bool FRESNEL = false, bool COAT = false, bool BANDS = false>
 __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChroma* C = nullptr, const DeviceFresnel* F = nullptr) {
   static_assert(!ASPH || BVH, "aspheres: the binary tree (or a compiled kernel, which knows its scene from Spec::rare())");
   static_assert(!CHROMA || ((BVH || SPEC::enabled) && !STOCH && !BATCH), "spectral launches: the binary tree or a kernel compiled for them, no stochastic surfaces, no batches");
   static_assert(!FRESNEL || ((BVH || SPEC::enabled) && !STOCH && !BATCH), "Fresnel launches: the binary tree or a kernel compiled for them, no stochastic surfaces, no batches");
   static_assert(!BATCH || (!BVH && !SEG), "batch launches: flat kernels, no segment rows");
+  static_assert(!BANDS || (CHROMA && !SEG), "band planes: spectral launches (C is a DeviceBands), no segment rows");
   extern __shared__ int bvh_stack[];  // ODW_BVH_STACK x 256 ints (BVH variant only)
   // per-thread event counters live in LDS (one column per thread, ds_add_u32
   // at the event): eight fewer VGPRs across the whole ray loop
@@ -2755,7 +2814,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
       uint32_t* cnt = cnt_lds + threadIdx.x;
       uint32_t* hit_state = hit_lds + (threadIdx.x >> 6) * 4;
       if constexpr (SPEC::enabled) {
-        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
+        spec_hits<STOCH, LEAN, POWER, SPEC, CHROMA, FRESNEL, COAT, BANDS>(P, sv, group_f64, group_i32, group_gdir, prim, face, P.first_ray + i, nint, cnt, hit_state,
                               hist_win, point, dir, power, medium, seq, skip, only, alive, C, wl, __make_integer_seq<IndexList, int, SPEC::N>{});
       } else {
       cf64 pf = sv.prim_f64 + (size_t)prim * 16;
@@ -2784,7 +2843,7 @@ __device__ __forceinline__ void trace_body(const TraceParams& P, const DeviceChr
         ncoat = FC->coat_n[g];
         coat = as_const(FC->coat) + 2 * ODW_COAT_LAYERS * g;
       }
-      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA, FRESNEL, COAT>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
+      interact<BVH, STOCH, LEAN, POWER, NoSpec, CHROMA, FRESNEL, COAT, BANDS>(P, group_f64, group_i32, group_gdir, g, group_i32[4 * g], group_i32[4 * g + 1] != 0, n,
                                  entering, P.first_ray + i, nint, cnt, hit_state, hist_win, point, dir, power, medium, seq, alive, C, wl, fmode,
                                  ncoat, coat);
       // outward normal of the solid = n against the travel direction when entering; for a facet of a convex
@@ -2874,6 +2933,31 @@ __global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_coat_ke
   trace_body<true, false, SEG, false, NoSpec, false, POWER, NoSource, ASPH, CHROMA, true, true>(P, &C, &F);
 }
 
+// Spectral launches that fill the detector's band planes (odw_set_detector_bands): the three kernels above with BANDS,
+// POWER x ASPH (no segment rows; CHROMA always).  Kernels of their own names with DeviceBands in DeviceChroma's place: the
+// instantiations above keep their names, arguments and code.
+template <bool POWER, bool ASPH>
+__global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_chroma_bands_kernel(const TraceParams P, const DeviceBands C) {
+  trace_body<true, false, false, false, NoSpec, false, POWER, NoSource, ASPH, true, false, false, true>(P, &C);
+}
+template <bool POWER, bool ASPH>
+__global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_fresnel_bands_kernel(const TraceParams P, const DeviceBands C,
+                                                                                              const DeviceFresnel F) {
+  trace_body<true, false, false, false, NoSpec, false, POWER, NoSource, ASPH, true, true, false, true>(P, &C, &F);
+}
+template <bool POWER, bool ASPH>
+__global__ __launch_bounds__(256, ODW_WAVES_PER_SIMD_BVH) void odw_trace_coat_bands_kernel(const TraceParams P, const DeviceBands C,
+                                                                                           const DeviceCoat F) {
+  trace_body<true, false, false, false, NoSpec, false, POWER, NoSource, ASPH, true, true, true, true>(P, &C, &F);
+}
+
+// the band of n wavelengths among n_edges edges (odw_band_index, on_device): record_hit's own search
+__global__ __launch_bounds__(256) void odw_band_index_kernel(const double* __restrict__ edges, int n_edges, const double* __restrict__ wl,
+                                                             uint64_t n, int32_t* __restrict__ out) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) out[i] = band_index_dev(as_const(edges), n_edges, wl[i]);
+}
+
 // R of a coated surface n1 -> n2 at n cosines of incidence (odw_coated_reflectance, device): the ray loop's own evaluation
 __global__ __launch_bounds__(256) void odw_coating_kernel(double n1, double n2, int entering, int k, const double* __restrict__ layers,
                                                           double wavelength_nm, const double* __restrict__ cos_i, uint64_t n,
@@ -2948,7 +3032,16 @@ struct SpecTail {
   const double* image;
   double v[N];
 };
-#ifdef ODW_SPEC_CHROMA
+#if defined(ODW_SPEC_CHROMA) && defined(ODW_SPEC_BANDS)
+// the variant for spectral launches that fill the detector's band planes: the one below with DeviceBands as its third
+// argument and BANDS (the band search sits in the out-of-line record_hit_flat_bands)
+extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(
+    const TraceParams P, const SpecTail<Spec::img_fits ? Spec::IMG : 4> T, const DeviceBands C) {
+  (void)T;
+  static_assert(Spec::chroma(), "ODW_SPEC_BANDS with a header that is not a spectral one");
+  trace_body<false, false, false, ODW_SPEC_LEAN, Spec, false, ODW_SPEC_POWER, ODW_SPEC_SOURCE, false, true, false, false, true>(P, &C);
+}
+#elif defined(ODW_SPEC_CHROMA)
 // the variant for spectral launches (the header's Spec has chroma(), disp(G), dc(G)): a wavelength per lane, the
 // wavelength tables in a third argument behind the tail
 extern "C" __global__ __launch_bounds__(256, ODW_SPEC_WAVES) void odw_spec_kernel(

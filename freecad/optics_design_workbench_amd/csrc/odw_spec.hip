@@ -157,8 +157,10 @@ std::string spec_source_text(uint64_t key) {
 // coat_n (with fresnel): the layers of every group's thin-film coating -- the count is structure, a constexpr Spec::coat(G);
 // the (index, thickness) pairs are values, in the (longer) value image at Spec::cc(G); and ODW_SPEC_COAT.  Null, or no layer
 // anywhere: the FRESNEL text of before, byte for byte.
+// bands (with disp_kind): the header of the CHROMA variant that fills the detector's band planes -- the kernel's third
+// argument is a DeviceBands (so img_fits counts its size), and ODW_SPEC_BANDS.  False: the CHROMA text of before, byte for byte.
 std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_kind = nullptr, const int32_t* fresnel = nullptr,
-                      const int32_t* coat_n = nullptr) {
+                      const int32_t* coat_n = nullptr, bool bands = false) {
   const int n = hs.n_prims, ng = hs.n_groups;
   std::vector<int> type(n), group(n), flags(n), condw(n), dead(n);
   std::vector<unsigned long long> xf(n);
@@ -211,7 +213,7 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
   s += "  static constexpr int iso = " + std::to_string(L.iso) + ";\n";
   // the value image: its size, whether it travels in the kernel arguments, and the offset of every piece
   s += "  static constexpr int IMG = " + std::to_string(L.words()) + ";\n";
-  s += std::string("  static constexpr bool img_fits = ") + (L.fits(sizeof(TraceParams) + (disp_kind ? sizeof(DeviceChroma) : 0)) ? "true" : "false") + ";\n";
+  s += std::string("  static constexpr bool img_fits = ") + (L.fits(sizeof(TraceParams) + (disp_kind ? (bands ? sizeof(DeviceBands) : sizeof(DeviceChroma)) : 0)) ? "true" : "false") + ";\n";
   if (disp_kind) {
     std::vector<int> kinds(std::max(1, ng), 0);
     for (int g = 0; g < ng; ++g) kinds[g] = disp_kind[g];
@@ -237,6 +239,7 @@ std::string spec_text(const HostScene& hs, int n_samplers, const int32_t* disp_k
   // stochastic surfaces: the kernel variant with scatter() (the sampler tables themselves are run-time data)
   s += std::string("#define ODW_SPEC_STOCH ") + (n_samplers > 0 ? "true" : "false") + "\n";
   if (disp_kind) s += "#define ODW_SPEC_CHROMA true\n";
+  if (disp_kind && bands) s += "#define ODW_SPEC_BANDS true\n";
   if (any_fresnel) s += "#define ODW_SPEC_FRESNEL true\n";
   if (any_coat) s += "#define ODW_SPEC_COAT true\n";
   return s;
@@ -402,15 +405,23 @@ void spec_wait_at_exit() {
 // its header; arguments and value image are the plain kernel's) -> ctx->spec_fresnel_fn[0 / 1]; bound like the CHROMA ones.
 // With a coating set (odw_set_coating) the same two slots hold the COAT kernel: layer counts in the header, the image longer
 // by the layers (ctx->spec_fresnel_layout).
-enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2, kSpecChroma = 3, kSpecChromaPower = 4, kSpecFresnel = 5, kSpecFresnelPower = 6 };
+// variants kSpecBands / kSpecBandsPower: the CHROMA kernel that also fills the detector's band planes (DeviceBands as its
+// third argument, ODW_SPEC_BANDS in its header) -> ctx->spec_bands_fn[0 / 1]; bound like the CHROMA ones, on the first
+// spectral launch with band planes.
+enum { kSpecSingle = 0, kSpecBatch = 1, kSpecPower = 2, kSpecChroma = 3, kSpecChromaPower = 4, kSpecFresnel = 5, kSpecFresnelPower = 6,
+       kSpecBands = 7, kSpecBandsPower = 8 };
 int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   const bool batch = variant != kSpecSingle;      // (a variant rides on the single-scene kernel's bookkeeping)
-  const bool chroma = variant == kSpecChroma || variant == kSpecChromaPower;
+  const bool bands = variant == kSpecBands || variant == kSpecBandsPower;
+  const bool chroma = variant == kSpecChroma || variant == kSpecChromaPower || bands;
   const bool fresnel = variant == kSpecFresnel || variant == kSpecFresnelPower;
   if (variant == kSpecBatch) {
     ctx->spec_batch_fn = nullptr;
   } else if (variant == kSpecPower) {
     ctx->spec_power_fn = nullptr;
+  } else if (bands) {
+    ctx->spec_bands_fn[variant == kSpecBandsPower] = nullptr;
+    if (ctx->compile_mode != ODW_COMPILE_STRUCTURE) return ODW_OK;
   } else if (chroma) {
     ctx->spec_chroma_fn[variant == kSpecChromaPower] = nullptr;
     if (ctx->compile_mode != ODW_COMPILE_STRUCTURE) return ODW_OK;
@@ -422,6 +433,8 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
     ctx->spec_fresnel_failed = false;
     ctx->spec_chroma_fn[0] = ctx->spec_chroma_fn[1] = nullptr;
     ctx->spec_chroma_failed = false;
+    ctx->spec_bands_fn[0] = ctx->spec_bands_fn[1] = nullptr;
+    ctx->spec_bands_failed = false;
     ctx->spec_power_fn = nullptr;
     ctx->spec_power_failed = false;
     ctx->spec_power_wait = nullptr;
@@ -446,10 +459,10 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   if (chroma) ctx->spec_chroma_layout = spec_image_layout(ctx->hs, ctx->disp_kind);
   const int32_t* coat_n = fresnel && ctx->coat_on ? ctx->coat_n : nullptr;
   if (fresnel) ctx->spec_fresnel_layout = spec_image_layout(ctx->hs, nullptr, coat_n);
-  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr, fresnel ? ctx->fresnel_mode : nullptr, coat_n) +
+  const std::string text = spec_text(ctx->hs, ctx->n_samplers, chroma ? ctx->disp_kind : nullptr, fresnel ? ctx->fresnel_mode : nullptr, coat_n, bands) +
                            (variant == kSpecBatch ? "" : spec_source_text(ctx->spec_source_key)) +
                            (variant == kSpecBatch ? "#define ODW_SPEC_BATCH true\n"
-                                                  : (variant == kSpecPower || variant == kSpecChromaPower || variant == kSpecFresnelPower) ? "#define ODW_SPEC_POWER true\n" : "");
+                                                  : (variant == kSpecPower || variant == kSpecChromaPower || variant == kSpecFresnelPower || variant == kSpecBandsPower) ? "#define ODW_SPEC_POWER true\n" : "");
   const char* xo = getenv("ODW_SPEC_OPTS");
   const std::string jkey = arch + "|" + (xo ? xo : "") + "|" + text;
   const std::string key = std::to_string(ctx->device) + "|" + jkey;
@@ -530,6 +543,10 @@ int spec_bind(odw_ctx* ctx, int variant = kSpecSingle) {
   } else {
     ctx->spec_cache_hit = 1;
   }
+  if (bands) {
+    ctx->spec_bands_fn[variant == kSpecBandsPower] = it->second.fn;
+    return ODW_OK;
+  }
   if (chroma) {
     ctx->spec_chroma_fn[variant == kSpecChromaPower] = it->second.fn;
     return ODW_OK;
@@ -571,11 +588,13 @@ void spec_note_launch(odw_ctx* ctx, uint64_t n_rays) {
 // wavelength tables as a third argument behind the tail.
 // fresnel (the variant of launches with a Fresnel mode set): its own layout -- the plain one, or with a coating set the
 // longer image with the groups' layers.
-int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const DeviceChroma* chroma = nullptr, bool fresnel = false) {
+// chroma_bytes: the size of that argument -- sizeof(DeviceBands) for the BANDS variant, whose `chroma` is one.
+int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const DeviceChroma* chroma = nullptr, bool fresnel = false,
+                size_t chroma_bytes = sizeof(DeviceChroma)) {
   const SpecLayout& L = chroma ? ctx->spec_chroma_layout : fresnel ? ctx->spec_fresnel_layout : ctx->spec_layout;
   if (L.n != ctx->hs.n_prims || L.size < kSpecImageLimits) return fail(ctx, ODW_ERR_DEVICE, "compiled kernel without its value image");
   constexpr size_t tail = (sizeof(TraceParams) + 7) & ~(size_t)7;
-  const bool resident = !batch && L.fits(sizeof(TraceParams) + (chroma ? sizeof(DeviceChroma) : 0));
+  const bool resident = !batch && L.fits(sizeof(TraceParams) + (chroma ? chroma_bytes : 0));
   std::vector<double>& img = ctx->spec_image_now;
   img.resize((size_t)L.words());
   spec_image_build(ctx->hs, ctx->P.lim, L, img.data(), chroma ? ctx->disp_coef : nullptr, true, fresnel && ctx->coat_on ? ctx->coat : nullptr);
@@ -597,11 +616,12 @@ int spec_launch(odw_ctx* ctx, unsigned grid, hipFunction_t fn, bool batch, const
   std::vector<char>& args = ctx->spec_args;
   static_assert(sizeof(DeviceChroma) % 8 == 0 && alignof(DeviceChroma) == 8, "DeviceChroma follows the tail without padding");
   const size_t tail_end = tail + sizeof(double*) + nv * sizeof(double);
-  args.assign(tail_end + (chroma ? sizeof(DeviceChroma) : 0), 0);
+  static_assert(sizeof(DeviceBands) % 8 == 0 && alignof(DeviceBands) == 8, "DeviceBands follows the tail without padding");
+  args.assign(tail_end + (chroma ? chroma_bytes : 0), 0);
   std::memcpy(args.data(), &ctx->P, sizeof(TraceParams));
   std::memcpy(args.data() + tail, &dev, sizeof dev);
   std::memcpy(args.data() + tail + sizeof dev, img.data(), nv * sizeof(double));
-  if (chroma) std::memcpy(args.data() + tail_end, chroma, sizeof(DeviceChroma));
+  if (chroma) std::memcpy(args.data() + tail_end, chroma, chroma_bytes);
   size_t size = args.size();
   void* config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args.data(), HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
   HIPCHK(ctx, hipModuleLaunchKernel(fn, grid, 1, 1, 256, 1, 1, 0, ctx->stream, nullptr, config));

@@ -13,8 +13,8 @@ import weakref
 import numpy as np
 
 from .. import _native
-from .._native import (CNT_NAMES, HIT_DTYPE, POWER_QUANTUM_BITS, SEGMENT_DTYPE, TRACE_HISTOGRAM, TRACE_POWER_HISTOGRAM, TRACE_RECORD_HITS,
-                       TRACE_RECORD_SEGMENTS)
+from .._native import (CNT_NAMES, HIT_DTYPE, POWER_QUANTUM_BITS, SEGMENT_DTYPE, TRACE_BAND_HISTOGRAM, TRACE_HISTOGRAM, TRACE_POWER_HISTOGRAM,
+                       TRACE_RECORD_HITS, TRACE_RECORD_SEGMENTS)
 
 
 # Contexts that are still open when the interpreter ends are closed in ITS order, at the start of its shutdown (atexit),
@@ -138,6 +138,7 @@ class Tracer:
     _LIVE.add(self)
     self._det = None
     self._power = False
+    self._bands = None
     self._keep = {}
     # ODW_COMPILE=structure: every tracer of the process compiles its scenes (test campaigns)
     if os.environ.get('ODW_COMPILE'):
@@ -340,8 +341,11 @@ class Tracer:
     # fresnel: likewise for launches with a Fresnel mode set (`odw_compiled_fresnel_info`); 0 also when no mode is set
     fr = C.c_int32(0)
     self._chk(self._lib.odw_compiled_fresnel_info(self._ctx, C.byref(fr)), 'odw_compiled_fresnel_info')
+    # bands: likewise for spectral launches that fill the detector's band planes (`odw_compiled_bands_info`)
+    bd = C.c_int32(0)
+    self._chk(self._lib.odw_compiled_bands_info(self._ctx, C.byref(bd)), 'odw_compiled_bands_info')
     return dict(mode=int(b.value), seconds=float(sec.value), cache=int(hit.value), power=int(pw.value), source=int(key.value),
-                chroma=int(ch.value), fresnel=int(fr.value))
+                chroma=int(ch.value), fresnel=int(fr.value), bands=int(bd.value))
 
   def setSurfaceSeed(self, seed):
     """Philox key of the stochastic-surface draws in traceRays launches"""
@@ -382,15 +386,23 @@ class Tracer:
     self._chk(self._lib.odw_set_limits(self._ctx, C.byref(d)), 'odw_set_limits')
     self.limits = lim
 
-  def setDetector(self, det, power=False):
+  def setDetector(self, det, power=False, bands=None):
     """det: dict(group, origin, ex, ey, x_lo, x_hi, y_lo, y_hi, nx, ny) or None
     power: keep a power plane beside the counts (`odw_enable_power_histogram`): every binned hit also adds its power,
     in fixed point (rint(power * 2^32) as uint64 -- integer sums, independent of launch order and GPU count), to
-    `powerHistogram()`; launches with `histogram=True` then fill both planes"""
+    `powerHistogram()`; launches with `histogram=True` then fill both planes
+    bands: K + 1 band edges in nm (strictly increasing, finite, > 0, K <= 64; `odw_set_detector_bands`): spectral launches
+    with `histogram=True` -- `trace` under a spectrum, `traceRays(..., wavelengths=)` -- also count every binned hit in the
+    plane of its wavelength's band (numpy.histogram's rule on the edges) -> `bandHistogram()`, and with `power` weigh it
+    there -> `bandPowerHistogram()`.  Launches that cannot fill the planes (monochromatic, `record_segments`, batches)
+    raise NativeError.  None: no bands, exactly as before."""
     self._power = False
+    self._bands = None
     if det is None:
       self._chk(self._lib.odw_set_detector(self._ctx, None), 'odw_set_detector')
       self._det = None
+      if bands is not None:
+        self._setBands(bands)              # (refused by name: bands need a detector)
       return
     d = _native.DetectorDesc()
     d.group = int(det.get('group', -1))
@@ -404,6 +416,17 @@ class Tracer:
     if power:
       self._chk(self._lib.odw_enable_power_histogram(self._ctx, C.c_int(1)), 'odw_enable_power_histogram')
       self._power = True
+    if bands is not None:
+      self._setBands(bands)
+
+  def _setBands(self, bands):
+    e = np.ascontiguousarray(bands, dtype=np.float64).ravel()
+    f = self._lib.odw_set_detector_bands
+    f.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]
+    if len(e) == 0:
+      raise ValueError('bands: at least two edges (None: no bands)')
+    self._chk(f(self._ctx, C.c_int32(len(e)), e.ctypes.data_as(C.POINTER(C.c_double))), 'odw_set_detector_bands')
+    self._bands = e
 
   def reserveHits(self, capacity):
     self._chk(self._lib.odw_reserve_hits(self._ctx, C.c_uint64(int(capacity))), 'odw_reserve_hits')
@@ -416,7 +439,8 @@ class Tracer:
   def _flags(self, record_hits, histogram, record_segments=False):
     return ((TRACE_RECORD_HITS if record_hits else 0) | (TRACE_HISTOGRAM if histogram else 0)
             | (TRACE_RECORD_SEGMENTS if record_segments else 0)
-            | (TRACE_POWER_HISTOGRAM if histogram and self._power else 0))
+            | (TRACE_POWER_HISTOGRAM if histogram and self._power else 0)
+            | (TRACE_BAND_HISTOGRAM if histogram and self._bands is not None else 0))
 
   def trace(self, first, n, seed, record_hits=True, histogram=True, record_segments=False):
     """asynchronous: rays first..first+n-1 of Philox stream `seed`"""
@@ -716,6 +740,36 @@ class Tracer:
     """power per detector bin, float64 (nx, ny), in units of the source's power: `powerHistogramRaw() * 2^-32`"""
     return self.powerHistogramRaw().astype(np.float64) * 2.0 ** -POWER_QUANTUM_BITS
 
+  def _bandPlanes(self, name):
+    if self._det is None or self._bands is None:
+      raise ValueError('no bands: setDetector(det, bands=edges)')
+    k, nx, ny = len(self._bands) - 1, self._det['nx'], self._det['ny']
+    out = np.zeros(k * nx * ny, dtype=np.uint64)
+    self._chk(getattr(self._lib, name)(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_uint64(len(out))), name)
+    return out.reshape(k, nx, ny)
+
+  def bandHistogram(self):
+    """the band count planes: uint64 (K, nx, ny); plane b counts the binned hits of spectral launches whose wavelength
+    lies in band b of `setDetector(..., bands=)` -- `bandHistogram().sum(0) <= histogram()`, equal where the edges
+    cover every wavelength"""
+    return self._bandPlanes('odw_fetch_band_histogram')
+
+  def bandPowerHistogramRaw(self):
+    """the band power planes as raw quanta: uint64 (K, nx, ny), `powerHistogramRaw()`'s rules per band plane"""
+    if not self._power:
+      raise ValueError('no power plane: setDetector(det, power=True, bands=edges)')
+    return self._bandPlanes('odw_fetch_band_power_histogram')
+
+  def bandPowerHistogram(self):
+    """power per band and detector bin, float64 (K, nx, ny), in units of the source's power"""
+    return self.bandPowerHistogramRaw().astype(np.float64) * 2.0 ** -POWER_QUANTUM_BITS
+
+  @staticmethod
+  def bandIndex(edges, wavelengths, device=False):
+    """the band (int32, -1: none) of every wavelength among `edges`: the kernels' rule (`odw_band_index`), on the host
+    or, with device=True, by the kernels' own search on the GPU"""
+    return _native.band_index(edges, wavelengths, device=device)
+
   def sample(self, first, n, seed):
     t = np.empty(int(n))
     phi = np.empty(int(n))
@@ -739,6 +793,14 @@ class Tracer:
     self._chk(self._lib.odw_device_power_histogram(self._ctx, C.byref(p), C.byref(n)), 'odw_device_power_histogram')
     return _CudaArrayView(p.value, n.value, '<i8', self)
 
+  def bandHistogramView(self):
+    """the band planes in HBM: K count planes, then with the power plane K planes of raw quanta, as one int64 vector"""
+    if self._bands is None:
+      raise ValueError('no bands: setDetector(det, bands=edges)')
+    p, n = C.c_void_p(), C.c_uint64(0)
+    self._chk(self._lib.odw_device_band_histogram(self._ctx, C.byref(p), C.byref(n)), 'odw_device_band_histogram')
+    return _CudaArrayView(p.value, n.value, '<i8', self)
+
   def countersView(self):
     p, n = C.c_void_p(), C.c_uint64(0)
     self._chk(self._lib.odw_device_counters(self._ctx, C.byref(p), C.byref(n)), 'odw_device_counters')
@@ -746,7 +808,8 @@ class Tracer:
 
   def resultsView(self):
     """counters and histogram -- and, with `setDetector(..., power=True)`, the power plane directly behind the
-    histogram's nx * ny bins -- as ONE int64 vector in HBM (`odw_device_results`): what a multi-GPU job sums with a
+    histogram's nx * ny bins, and with `bands=` the K band count planes and (with power) K band power planes behind
+    those -- as ONE int64 vector in HBM (`odw_device_results`): what a multi-GPU job sums with a
     single reduce (the plane's uint64 quanta add as int64 words do).  -> (view, offset of the first histogram bin in words)"""
     p, n, off = C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
     self._chk(self._lib.odw_device_results(self._ctx, C.byref(p), C.byref(n), C.byref(off)), 'odw_device_results')

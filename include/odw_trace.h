@@ -413,6 +413,12 @@ enum {
 #define ODW_TRACE_POWER_HISTOGRAM 0x8 /* with ODW_TRACE_HISTOGRAM and an enabled power plane
                                        * (odw_enable_power_histogram): a binned hit also adds
                                        * its weight to the power plane; ignored otherwise      */
+#define ODW_TRACE_BAND_HISTOGRAM 0x10 /* with ODW_TRACE_HISTOGRAM and enabled bands
+                                       * (odw_set_detector_bands), on a spectral launch: a binned
+                                       * hit is also counted in the plane of its wavelength's band
+                                       * (and, under ODW_TRACE_POWER_HISTOGRAM, weighed there);
+                                       * ignored without the histogram flag or without bands    */
+#define ODW_BAND_MAX 64               /* bands of a detector at most (65 edges)                 */
 
 /* The weight of a hit (v12), wherever hits are summed by power -- the power plane of the
  * detector (odw_enable_power_histogram) and of the post-hoc binning (odw_hits_bin_power):
@@ -656,6 +662,50 @@ int odw_enable_power_histogram(odw_ctx* ctx, int on);
  * bin of the COUNT plane holds >= 2^32 hits: such a bin's power sum may have wrapped, and
  * no plane is handed out.                                                                   */
 int odw_fetch_power_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_bins);
+/* Spectral detector maps: the detector's count plane -- and its power plane -- once more per
+ * wavelength band.  edges_nm: n_edges = K + 1 band edges e_0 < e_1 < ... < e_K in nm, finite
+ * and > 0, 1 <= K <= ODW_BAND_MAX.  A hit of a SPECTRAL launch (odw_trace under a bound
+ * spectrum, odw_trace_rays_spectral) with ODW_TRACE_HISTOGRAM | ODW_TRACE_BAND_HISTOGRAM that
+ * lands in bin (ix, iy) is counted in the total plane as ever and in band b by numpy.histogram's
+ * rule on its ray's wavelength: e_b <= wl < e_(b+1), wl == e_K in band K - 1, a wavelength
+ * outside [e_0, e_K] in no band (so the band planes sum to at most the total plane, and to
+ * exactly it when the edges cover the spectrum).  The comparisons are plain float64 ones:
+ * numpy.searchsorted(edges, wl, 'right') - 1 is b.  With ODW_TRACE_POWER_HISTOGRAM and an
+ * enabled power plane the hit's weight q(power) goes to a band power plane too.  All planes are
+ * uint64 sums: bit for bit the same whatever the launch order, the split into launches or the
+ * number of GPUs.  The results block (odw_device_results), P = 1 with the power plane else 0:
+ *   [16 counter words][nx*ny counts][P: nx*ny power][K*nx*ny band counts, band-major]
+ *   [P: K*nx*ny band power, band-major]
+ * -- what exists keeps its offset, odw_reset_results zeroes all of it.  Call after
+ * odw_set_detector (ODW_ERR_INVALID without a detector) and after odw_enable_power_histogram
+ * (switching the power plane lays the block out again and zeroes the band planes); the call
+ * zeroes the band planes and may move the block.  n_edges == 0 clears the bands, and so does
+ * every odw_set_detector.  ODW_ERR_INVALID, by name: an edge that is not finite, not positive
+ * or not above its predecessor; more than ODW_BAND_MAX bands; a block of 2^31 words or more
+ * (the kernels index it with 32-bit products).
+ * Launches that cannot fill band planes are refused with ODW_ERR_UNSUPPORTED when the flag is
+ * set and bands are enabled: a launch that is not spectral (one wavelength: its total plane IS
+ * its band's plane), ODW_TRACE_RECORD_SEGMENTS, batches.                                      */
+int odw_set_detector_bands(odw_ctx* ctx, int32_t n_edges, const double* edges_nm);
+/* the K count planes, out[(b * nx + ix) * ny + iy]; n_words = K * nx * ny                    */
+int odw_fetch_band_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_words);
+/* the K power planes as raw quanta, likewise; needs the power plane; odw_fetch_power_histogram's
+ * capacity rule per band plane: ODW_ERR_CAPACITY when a band count bin holds >= 2^32 hits    */
+int odw_fetch_band_power_histogram(odw_ctx* ctx, uint64_t* out, uint64_t n_words);
+/* The band of n wavelengths among n_edges edges (the rule above; -1: no band), context-free:
+ * on_device == 0 on the host; else by a one-line kernel on the current device, the trace
+ * kernels' own search (wavelengths and out are host arrays either way).                       */
+int odw_band_index(const double* edges_nm, int32_t n_edges, const double* wavelengths_nm, uint64_t n, int32_t* out_i32,
+                   int32_t on_device);
+/* is the compiled kernel's variant for band planes bound (0 / ODW_COMPILE_STRUCTURE), as
+ * odw_compiled_chroma_info tells it for spectral launches                                     */
+int odw_compiled_bands_info(odw_ctx* ctx, int32_t* bound);
+/* odw_compile_check_chroma for that variant (power != 0: with the power plane): its header --
+ * the CHROMA header with the kernel's third argument counted as the longer one, and
+ * ODW_SPEC_BANDS -- and the size of its code for `arch`; no device needed                     */
+int odw_compile_check_bands(const odw_scene_desc* scene, const odw_limits* limits, const char* arch,
+                            const odw_source_desc* source, const int32_t* disp_kind, int32_t power,
+                            char* header_out, uint64_t header_capacity, uint64_t* code_bytes);
 /* Overlapped row fetch for continuous runs that keep every hit (the reference
  * buffers hits while the workers trace on and flushes them every few seconds,
  * results_store.py:405-457): two hit lists.  odw_swap_hit_lists puts the list
@@ -964,6 +1014,10 @@ int odw_device_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_bins);
  * odw_fetch_power_histogram copies (histogram.py:54,78 with weights=).  No
  * plane enabled: *dptr = NULL, *n_bins = 0                                   */
 int odw_device_power_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_bins);
+/* the band planes (odw_set_detector_bands): everything behind the histogram and its power
+ * plane -- K count planes, then with the power plane K power planes --, n_words words; no
+ * bands: *dptr = NULL, *n_words = 0.  odw_device_results covers them too: one reduce.       */
+int odw_device_band_histogram(odw_ctx* ctx, void** dptr, uint64_t* n_words);
 int odw_device_counters(odw_ctx* ctx, void** dptr, uint64_t* n);
 int odw_stream(odw_ctx* ctx, void** hip_stream);
 
