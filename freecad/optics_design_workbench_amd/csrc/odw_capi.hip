@@ -1776,6 +1776,38 @@ int odw_table_slopes(const double* cdf, const double* edges, int32_t n_tables, i
   return ODW_OK;
 }
 
+// What sample_tables (odw_kernels.hip) takes for granted of an azimuth table, beyond cdf[0] = 0 and cdf[np - 1] = 1:
+// nullptr, or what is wrong with it.
+//  - The cdf does not decrease: the guide and the binary search both assume a sorted column.
+//  - With one theta table per azimuth cell (rows > 1) the edges are those of numpy.linspace(e0, e1, np).  The row of a
+//    ray is argmin_i |mid_i - phi| (first minimum); the kernel evaluates that rule on the cell r = floor((phi - e0) /
+//    (e1 - e0) * rows) and its two neighbours only.  With U = ulp(max(|e0|, |e1|)), edges within 4 U of e0 + i w
+//    (w = (e1 - e0) / rows) and |w| >= 64 U: phi lies in a cell c of the table, so (phi - e0) / w is in [c - 4 U / |w|,
+//    c + 1 + 4 U / |w|]; the subtraction adds at most U / |w| to that, the division and the product 3 * 2^-53 * rows
+//    (< 1e-6 for any int32 count), so the computed value is within 5/64 + 1e-6 of [c, c + 1] and r is c - 1, c or
+//    c + 1.  r = c - 1 only for phi within 9/64 |w| of the edge e_c, where the nearest mid-point is that of c - 1 or of
+//    c: both in the window c - 2 .. c; likewise r = c + 1 only next to e_(c+1), nearest mid-point c or c + 1.  For
+//    r = c the window c - 1 .. c + 1 holds the nearest mid-point of any phi in cell c.  (mid-points of equidistant
+//    cells lie w apart up to 9 U, so no cell further off can win.)  Edges spaced otherwise -- geometrically, say --
+//    put the nearest mid-point anywhere: such a table is refused here, not searched there.
+static const char* azimuth_table_fault(const double* edges, const double* cdf, size_t np, size_t rows) {
+  for (size_t j = 1; j < np; ++j)
+    if (!(cdf[j] >= cdf[j - 1])) return "phi_cdf decreases";
+  if (rows <= 1) return nullptr;
+  const double e0 = edges[0], e1 = edges[np - 1];
+  if (!std::isfinite(e0) || !std::isfinite(e1) || e0 == e1)
+    return "phi_edges: with one theta table per azimuth cell the edges must be finite and span an interval";
+  const double m = std::fmax(std::fabs(e0), std::fabs(e1));
+  const double ulp = std::fmax(std::ldexp(1.0, std::ilogb(m) - 52), 4.9406564584124654e-324);
+  const double w = (e1 - e0) / (double)(np - 1);
+  if (!(std::fabs(w) >= 64.0 * ulp))
+    return "phi_edges: with one theta table per azimuth cell the cells must be at least 64 ulp of the larger end wide";
+  for (size_t i = 0; i < np; ++i)
+    if (!(std::fabs(edges[i] - ((double)i * w + e0)) <= 4.0 * ulp))
+      return "phi_edges: with one theta table per azimuth cell the edges must be equidistant (numpy.linspace) within 4 ulp";
+  return nullptr;
+}
+
 int odw_upload_surface_samplers(odw_ctx* ctx, const odw_surface_sampler_desc* samplers, int32_t n) {
   if (!ctx || n < 0 || (n && !samplers)) return fail(ctx, ODW_ERR_INVALID, "odw_upload_surface_samplers: bad argument");
   if (!ctx->have_scene) return fail(ctx, ODW_ERR_NO_SCENE, "odw_upload_surface_samplers before odw_upload_scene");
@@ -1814,8 +1846,9 @@ int odw_upload_surface_samplers(odw_ctx* ctx, const odw_surface_sampler_desc* sa
     for (size_t k = 0; k < nf; ++k) {
       const double* pc = s.phi_cdf + k * np;
       if (pc[0] != 0.0 || pc[np - 1] != 1.0) return fail(ctx, ODW_ERR_INVALID, "surface sampler: phi cdf must run from 0 to 1");
+      if (const char* fault = azimuth_table_fault(s.phi_edges, pc, np, rows))
+        return fail(ctx, ODW_ERR_INVALID, std::string("surface sampler: ") + fault);
       for (size_t j = 0; j < np; ++j) {
-        if (j && pc[j] < pc[j - 1]) return fail(ctx, ODW_ERR_INVALID, "surface sampler: cdf not monotone");
         ptab[(k * np + j) * 2] = pc[j];
         ptab[(k * np + j) * 2 + 1] = s.phi_edges[j];
       }
@@ -1911,6 +1944,8 @@ static int upload_source(odw_ctx* ctx, const odw_source_desc* s, bool guides) {
   const int np = s->n_phi_knots, nt = s->n_t_knots, rows = s->n_t_rows;
   if (s->phi_cdf[0] != 0.0 || s->phi_cdf[np - 1] != 1.0)
     return fail(ctx, ODW_ERR_INVALID, "phi cdf must run from 0 to 1");
+  if (const char* fault = azimuth_table_fault(s->phi_edges, s->phi_cdf, (size_t)np, (size_t)rows))
+    return fail(ctx, ODW_ERR_INVALID, std::string("odw_upload_source: ") + fault);
   std::vector<double> ptab((size_t)np * 2), ttab((size_t)rows * nt * 2);
   for (int i = 0; i < np; ++i) { ptab[2 * i] = s->phi_cdf[i]; ptab[2 * i + 1] = s->phi_edges[i]; }
   const int n_guide = guides ? kGuide : 1;

@@ -49,7 +49,8 @@ typedef const DeviceDetector ODW_CONST* cdetector;
 // ---- cheap float64 reciprocal / square root ------------------------------
 // v_rcp_f64 / v_rsq_f64 deliver ~26 bits; two Newton steps give ~1 ulp without
 // the v_div_scale/v_div_fmas/v_div_fixup tail of an IEEE division (used where
-// the result feeds tolerance tests with 1e-6 slack, never in the sampler).
+// the result feeds tolerance tests with 1e-6 slack; never in the sampler's tables, whose values are numpy.interp's
+// bit for bit -- make_ray's two normalisations do use frsqrt, held to exact rays by tests/test_gpu_source.py).
 __device__ __forceinline__ double frcp(double x) {
   double r = __builtin_amdgcn_rcp(x);
   r = fma(fma(-x, r, 1.0), r, r);
@@ -151,6 +152,7 @@ __device__ __forceinline__ void sample_tables(const TableView& s, double u_phi, 
   if (KNOWN ? !SINGLE_ROW : s.n_t_rows > 1) {
     // argmin_i |mid_i - phi| (first minimum): the candidate is the cell that
     // contains phi, the exact rule is applied to it and its two neighbours
+    // (equidistant edges only: the uploads refuse others, odw_capi.hip: azimuth_table_fault)
     const double e0 = s.phi_tab[1], e1 = s.phi_tab[2 * (s.n_phi_knots - 1) + 1];
     int r = (int)floor((phi - e0) / (e1 - e0) * (double)s.n_t_rows);
     r = max(0, min(s.n_t_rows - 1, r));
@@ -279,7 +281,8 @@ __device__ __forceinline__ d3 xf_vec_t_nz(P m, d3 v) {  // R^T v
 
 // sin and cos for |x| <~ 64 (source angles are domain-limited): one Cody-Waite
 // reduction step by pi/2 with fma, fdlibm kernel polynomials; <= 1 ulp of 1.0
-// absolute error (checked against libm on 4e6 points).  Replaces ocml's
+// absolute error (tests/test_gpu_source.py holds the rays made with it to 200-bit ones, at the multiples of pi / 2
+// and out to |x| = 64).  Replaces ocml's
 // sincos(double), whose large-argument path costs ~20 extra VGPRs.
 __device__ __forceinline__ void sincos_bounded(double x, double& s, double& c) {
   const double k = rint(x * 0.63661977236758134308);

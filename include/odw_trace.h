@@ -234,6 +234,18 @@ typedef struct odw_source_desc {
   const double* t_edges;   /* [n_t_knots]     variableRanges[theta or r]      */
   const double* t_cdf;     /* [n_t_rows*n_t_knots] each row / its last entry  */
                            /* (random_number_generator.py:441)                */
+  /* Refused with ODW_ERR_INVALID, by name (odw_upload_source, and likewise the
+   * tables of odw_upload_surface_samplers):
+   *  - a phi_cdf that decreases anywhere (like a row of t_cdf);
+   *  - with n_t_rows > 1, phi_edges that are not those of
+   *    numpy.linspace(e0, e1, n_phi_knots): finite, e0 != e1, every edge within
+   *    4 ulp of max(|e0|, |e1|) of e0 + i (e1 - e0) / (n_phi_knots - 1), and
+   *    cells no narrower than 64 such ulp.  The theta row of a ray is the cell
+   *    whose mid-point is nearest to phi; the kernels find it among the cell
+   *    floor((phi - e0) / (e1 - e0) * n_t_rows) and its two neighbours, which
+   *    holds the nearest mid-point only when the edges are equidistant.
+   *    (What VectorRandomVariable.tables() makes is; with n_t_rows == 1 no
+   *    row is looked for and any edges are taken.)                           */
 } odw_source_desc;
 
 /* Stochastic surface of a Mirror / Lens group =
