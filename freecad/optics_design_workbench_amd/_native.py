@@ -57,13 +57,15 @@ SYMBOLS = ['odw_abi_version', 'odw_create', 'odw_destroy', 'odw_last_error', 'od
            'odw_set_fresnel', 'odw_compiled_fresnel_info', 'odw_fresnel_reflectance', 'odw_compile_check_fresnel', 'odw_fresnel_check',
            'odw_set_coating', 'odw_coating_check', 'odw_coated_reflectance', 'odw_compile_check_coating',
            'odw_set_detector_bands', 'odw_fetch_band_histogram', 'odw_fetch_band_power_histogram', 'odw_device_band_histogram',
-           'odw_band_index', 'odw_compiled_bands_info', 'odw_compile_check_bands']
+           'odw_band_index', 'odw_compiled_bands_info', 'odw_compile_check_bands',
+           'odw_hits_bin_bands', 'odw_hits_bin_bands_info']
 
 # dispersion of a group (ODW_DISP_*) and spectrum of a point source (ODW_SPECTRUM_*)
 DISP_NONE, DISP_SELLMEIER, DISP_CAUCHY = 0, 1, 2
 DISP_KINDS = {'': 0, None: 0, 'Sellmeier': 1, 'Cauchy': 2}
 DISP_COEFS = 6                            # ODW_DISP_COEFS
 SPECTRUM_MODES = {'lines': 1, 'density': 2}
+ROW_WL_SPECTRUM, ROW_WL_TABLE = 1, 2      # ODW_ROW_WL_*: where odw_hits_bin_bands takes a row's wavelength from
 STREAM_WAVELENGTH = 6                     # ODW_STREAM_WAVELENGTH: word 3 of the Philox counter of the wavelength draw
 # Fresnel mode of a lens group (ODW_FRESNEL_*)
 FRESNEL_NONE, FRESNEL_LOSS, FRESNEL_SPLIT = 0, 1, 2

@@ -118,6 +118,7 @@ struct odw_ctx {
   // post-hoc binning of the rows in HBM (odw_posthoc.hip): the selection = sort_vals[1][0 .. ph_n)
   DevBuf ph_sel_entering, ph_flags, ph_x, ph_y, ph_sorted, ph_small, ph_part, ph_edges, ph_edges_b, ph_counts, ph_sel_hist;
   DevBuf ph_accel;                                   // tables of the polar binning (odw_posthoc.hip: PhbBinAccel)
+  DevBuf ph_wl;                                      // wavelength table of a band binning (odw_hits_bin_bands, table mode)
   DevBuf ph_bitmap, ph_before, ph_row_of;            // ordered selection without a sort (odw_posthoc.hip: ph_mark_kernel)
   uint64_t alt_hit_ray_end = 0;    // the same for the list odw_swap_hit_lists has put aside
   uint64_t hit_ray_end = 0;        // ray indices of the rows in the hit list lie below this (0: list empty; 1 << 48: unknown)
@@ -1151,7 +1152,7 @@ void odw_destroy(odw_ctx* ctx) {
   for (DevBuf* b : {&ctx->grid_bounds, &ctx->grid_cells, &ctx->grid_items}) release(*b);
   for (DevBuf* b : {&ctx->ph_bitmap, &ctx->ph_before, &ctx->ph_row_of}) release(*b);
   for (DevBuf* b : {&ctx->ph_sel_entering, &ctx->ph_flags, &ctx->ph_x, &ctx->ph_y, &ctx->ph_sorted, &ctx->ph_small,
-                    &ctx->ph_part, &ctx->ph_edges, &ctx->ph_edges_b, &ctx->ph_counts, &ctx->ph_sel_hist, &ctx->ph_accel})
+                    &ctx->ph_part, &ctx->ph_edges, &ctx->ph_edges_b, &ctx->ph_counts, &ctx->ph_sel_hist, &ctx->ph_accel, &ctx->ph_wl})
     release(*b);
   release(ctx->archive);
   release(ctx->archive_count);
@@ -2533,6 +2534,16 @@ int odw_archive_append(odw_ctx* ctx, odw_ctx* src, uint64_t* total_rows) {
       HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
       release(ctx->archive);
       ctx->archive = bigger;
+    }
+    // the spectrum the rows were drawn under travels with them to a context that has no source of its own (a run's
+    // archive): odw_hits_bin_bands draws the rows' wavelengths again from (seed, ray number) under it
+    if (src != ctx && src->spec_n > 0 && !ctx->have_source) {
+      if ((rc = ensure(ctx, ctx->spec_tab, src->spec_tab.bytes))) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->spec_tab.p, src->spec_tab.p, src->spec_tab.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+      ctx->spec_n = src->spec_n;
+      ctx->spec_mode = src->spec_mode;
+      ctx->spec_lo = src->spec_lo;
+      ctx->spec_hi = src->spec_hi;
     }
     // (slots tagged unused travel along: every pass over a hit list skips them)
     HIPCHK(ctx, hipMemcpyAsync((odw_hit*)ctx->archive.p + ctx->archive_slots, src->hits.p, used * sizeof(odw_hit),

@@ -539,6 +539,119 @@ __global__ __launch_bounds__(256) void ph_bin_kernel(const double* __restrict__ 
   }
 }
 
+// ---- ph_bin_kernel, split by wavelength band (odw_hits_bin_bands) -------------------------------------------------------------
+// A row's bin pair is ph_bin_kernel's (the same calls); its wavelength comes from its ray number -- the tag's low 48 bits --:
+// under a spectrum the ray loop's own draw (spectrum_wavelength of (seed, ray): odw_kernels.hip), after an explicit launch
+// the table that launch was given, wl[ray - first_ray].  Its band is band_index_dev's, the rule of the up-front band planes.
+// Planes: K bands, then the total (plane K = ph_bin_kernel's counts, bit for bit); a binned row in no band (or, in table
+// mode, with a ray outside the table: misc[1]) is counted in misc[0].
+// The band edges travel by value in the kernel's arguments: band_index_dev's loop counter is wave-uniform, so they are
+// read with scalar loads, as in the trace kernels.
+// Counts: the (K + 1) * nbins planes as u32 in LDS where they fit kPhLdsBins words (a block sees fewer than 2^32 rows: a
+// selection has fewer than 2^31), flushed with u64 atomics; otherwise u64 atomics in HBM, two per binned row.  Power
+// (POWER): always u64 atomics in HBM, two per binned row -- a u64 window of the same bins would halve what fits, and the
+// weighted planes are the rarer call.  power and tag are the last 16 bytes of a row: one load.
+struct PhBandEdges { double e[ODW_BAND_MAX + 1]; };
+struct PhBandWl {
+  int32_t mode, n_edges, spec_n, spec_mode;        // ODW_ROW_WL_*; K + 1; the bound spectrum
+  const double* spec_tab;
+  uint64_t seed;
+  const double* wl;                                // table mode: wavelengths of rays first_ray .. first_ray + n_wl - 1
+  uint64_t first_ray, n_wl;
+};
+
+template <bool LDS_COUNTS, bool POWER>
+__global__ __launch_bounds__(256) void ph_bin_bands_kernel(const double* __restrict__ X, const double* __restrict__ Y,
+                                                           uint64_t m, double ox, double oy, int polar,
+                                                           const double* __restrict__ edges_a, int na,
+                                                           const double* __restrict__ edges_b, int nb,
+                                                           const PhbBinAccel* __restrict__ accel, unsigned long long* __restrict__ counts,
+                                                           const odw_hit* __restrict__ hits, const uint32_t* __restrict__ sel,
+                                                           unsigned long long* __restrict__ power, const PhBandEdges E, const PhBandWl W,
+                                                           unsigned long long* __restrict__ misc) {
+  extern __shared__ double ph_bands_lds[];        // [edges | counts | guide], sized by the caller (ph_bin_lds_bytes)
+  __shared__ uint32_t s_misc[2];
+  const bool edges_in_lds = na + nb <= kPhLdsEdges;
+  const int nbins = (na - 1) * (nb - 1);
+  const int n_words = W.n_edges * nbins;          // K + 1 planes
+  const int total_at = (W.n_edges - 1) * nbins;
+  double* s_edges = ph_bands_lds;
+  uint32_t* s_counts = reinterpret_cast<uint32_t*>(ph_bands_lds + (edges_in_lds ? na + nb : 0));
+  uint16_t* s_guide = reinterpret_cast<uint16_t*>(s_counts + (LDS_COUNTS ? n_words : 0));
+  const bool az_fast = polar && accel && accel->az_on && edges_in_lds;
+  const bool r_fast = polar && accel && accel->r_on && edges_in_lds;
+  if (edges_in_lds) {
+    for (int k = threadIdx.x; k < na; k += blockDim.x) s_edges[k] = edges_a[k];
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) s_edges[na + k] = edges_b[k];
+  }
+  if (LDS_COUNTS)
+    for (int k = threadIdx.x; k < n_words; k += blockDim.x) s_counts[k] = 0;
+  if (r_fast)
+    for (int k = threadIdx.x; k < kPhbGuide + 2; k += blockDim.x) s_guide[k] = accel->guide[k];
+  if (threadIdx.x < 2) s_misc[threadIdx.x] = 0;
+  __syncthreads();
+  const double* ea = edges_in_lds ? s_edges : edges_a;
+  const double* eb = edges_in_lds ? s_edges + na : edges_b;
+  uint32_t n_none = 0, n_outside = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < m; j += stride) {
+    int ia, ib;
+    if (accel) {
+      ph_bin_pair(accel, az_fast, r_fast, s_guide, polar, ph_minus(X[j], ox), ph_minus(Y[j], oy), ea, na, eb, nb, ia, ib);
+    } else {
+      double a, b;
+      ph_coords(X[j], Y[j], ox, oy, polar, a, b);
+      ia = ph_bin(ea, na, a);
+      ib = ph_bin(eb, nb, b);
+    }
+    const bool binned = ia >= 0 && ib >= 0;
+    // (table mode looks at every selected row's ray: one outside the table refuses the call, binned or not)
+    if (binned || W.mode == ODW_ROW_WL_TABLE) {
+      const odw_hit* h = hits + sel[j];
+      uint64_t tag;
+      unsigned long long q = 0;
+      if constexpr (POWER) {
+        const ulonglong2 pt = *reinterpret_cast<const ulonglong2*>(&h->power);      // (power, tag): offset 48 of a 64-byte row
+        q = power_quanta(__longlong_as_double((long long)pt.x));
+        tag = pt.y;
+      } else {
+        tag = h->tag;
+      }
+      const uint64_t ray = ODW_HIT_RAY(tag);
+      double wl;
+      if (W.mode == ODW_ROW_WL_SPECTRUM) {
+        wl = spectrum_wavelength(W.spec_tab, W.spec_n, W.spec_mode, ray, W.seed);
+      } else {
+        const uint64_t r = ray - W.first_ray;          // (unsigned: a ray below first_ray wraps above n_wl)
+        const bool inside = r < W.n_wl;
+        wl = inside ? W.wl[r] : NAN;                   // (no wavelength: no band)
+        n_outside += inside ? 0u : 1u;
+      }
+      if (!binned) continue;
+      const int b = band_index_dev(E.e, W.n_edges, wl);
+      const int k = ia * (nb - 1) + ib;
+      if (LDS_COUNTS) atomicAdd(&s_counts[total_at + k], 1u);
+      else atomicAdd(counts + (total_at + k), 1ull);
+      if (POWER) atomicAdd(power + (total_at + k), q);
+      if (b >= 0) {
+        if (LDS_COUNTS) atomicAdd(&s_counts[b * nbins + k], 1u);
+        else atomicAdd(counts + (b * nbins + k), 1ull);
+        if (POWER) atomicAdd(power + (b * nbins + k), q);
+      } else {
+        ++n_none;
+      }
+    }
+  }
+  if (n_none) atomicAdd(&s_misc[0], n_none);
+  if (n_outside) atomicAdd(&s_misc[1], n_outside);
+  __syncthreads();
+  if (LDS_COUNTS) {
+    for (int k = threadIdx.x; k < n_words; k += blockDim.x)
+      if (s_counts[k]) atomicAdd(counts + k, (unsigned long long)s_counts[k]);
+  }
+  if (threadIdx.x < 2 && s_misc[threadIdx.x]) atomicAdd(misc + threadIdx.x, (unsigned long long)s_misc[threadIdx.x]);
+}
+
 // the moment sums by themselves (ph_moment_add / ph_moment_write above), one pass over the rows
 __global__ __launch_bounds__(256) void ph_moment_kernel(const odw_hit* __restrict__ hits, const uint32_t* __restrict__ sel, uint64_t m,
                                                         double* __restrict__ part) {
@@ -1033,6 +1146,133 @@ int odw_hits_bin(odw_ctx* ctx, int32_t polar, const double* origin, const double
 int odw_hits_bin_power(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
                        const double* edges_b, int32_t n_b, uint64_t* counts, uint64_t* power) {
   return ph_bin_run(ctx, "odw_hits_bin_power", polar, origin, edges_a, n_a, edges_b, n_b, counts, power, true);
+}
+
+namespace {
+// the route of odw_hits_bin_bands' count planes: the u32 window in LDS where (K + 1) * nbins words fit ph_bin_kernel's
+// budget (ODW_BIN_BANDS_HBM=1: never -- the tests hold the two routes against each other)
+bool ph_bands_in_lds(uint64_t nbins, int n_band_edges) {
+  return nbins * (uint64_t)n_band_edges <= (uint64_t)kPhLdsBins && !getenv("ODW_BIN_BANDS_HBM");
+}
+}  // namespace
+
+int odw_hits_bin_bands_info(int32_t n_a, int32_t n_b, int32_t n_band_edges, int32_t power, int32_t* counts_in_lds,
+                            int32_t* power_in_lds) {
+  (void)power;
+  if (n_a < 2 || n_b < 2 || !counts_in_lds || !power_in_lds) return fail(nullptr, ODW_ERR_INVALID, "odw_hits_bin_bands_info: bad argument");
+  if (n_band_edges < 2 || n_band_edges - 1 > ODW_BAND_MAX) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "odw_hits_bin_bands_info: %d bands: 1 to ODW_BAND_MAX = %d are taken", n_band_edges - 1, ODW_BAND_MAX);
+    return fail(nullptr, ODW_ERR_INVALID, buf);
+  }
+  *counts_in_lds = ph_bands_in_lds((uint64_t)(n_a - 1) * (uint64_t)(n_b - 1), n_band_edges) ? 1 : 0;
+  *power_in_lds = 0;                                  // (the power planes: always u64 atomics in HBM)
+  return ODW_OK;
+}
+
+int odw_hits_bin_bands(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
+                       const double* edges_b, int32_t n_b, const double* band_edges_nm, int32_t n_band_edges,
+                       int32_t wl_mode, uint64_t seed, uint64_t first_ray, uint64_t n_wl, const double* wl_nm,
+                       uint64_t* counts, uint64_t* power, uint64_t* n_no_band) {
+  const std::string who = "odw_hits_bin_bands";
+  if (!ctx || !origin || !edges_a || !edges_b || !counts || !n_no_band || n_a < 2 || n_b < 2 ||
+      (wl_mode != ODW_ROW_WL_SPECTRUM && wl_mode != ODW_ROW_WL_TABLE))
+    return fail(ctx, ODW_ERR_INVALID, who + ": bad argument");
+  std::string err;
+  int rc = bands_validate(who.c_str(), n_band_edges, band_edges_nm, err);
+  if (rc) return fail(ctx, rc, err);
+  for (int k = 1; k < n_a; ++k) if (!(edges_a[k] >= edges_a[k - 1])) return fail(ctx, ODW_ERR_INVALID, who + ": edges must increase monotonically");
+  for (int k = 1; k < n_b; ++k) if (!(edges_b[k] >= edges_b[k - 1])) return fail(ctx, ODW_ERR_INVALID, who + ": edges must increase monotonically");
+  if (wl_mode == ODW_ROW_WL_SPECTRUM) {
+    if (ctx->spec_n <= 0) return fail(ctx, ODW_ERR_INVALID, who + ": no spectrum bound (odw_set_spectrum): the rows' wavelengths cannot be drawn again");
+  } else {
+    if (n_wl == 0 || !wl_nm) return fail(ctx, ODW_ERR_INVALID, who + ": a wavelength table is needed (n_wl > 0, wl_nm)");
+    for (uint64_t i = 0; i < n_wl; ++i)
+      if (!(wl_nm[i] > 0) || !std::isfinite(wl_nm[i])) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "%s: wavelength %llu of the table (%.17g nm) is not positive and finite", who.c_str(),
+                      (unsigned long long)i, wl_nm[i]);
+        return fail(ctx, ODW_ERR_INVALID, buf);
+      }
+  }
+  if ((rc = ph_need_projection(ctx, who.c_str()))) return rc;
+  const bool weighted = power != nullptr;
+  const uint64_t m = ctx->ph_n;
+  const uint64_t nbins = (uint64_t)(n_a - 1) * (uint64_t)(n_b - 1);
+  const uint64_t plane_words = nbins * (uint64_t)n_band_edges;         // K + 1 planes
+  const uint64_t words = (weighted ? 2 : 1) * plane_words;             // [counts | power], then misc[2]
+  if (words >= (1ull << 31)) {
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "%s: %d planes of %llu bins%s: the output must stay below 2^31 words", who.c_str(), (int)n_band_edges,
+                  (unsigned long long)nbins, weighted ? ", twice" : "");
+    return fail(ctx, ODW_ERR_INVALID, buf);
+  }
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  ctx->phb_edges_host.clear();                       // (ph_bin_run: the batched chain's edges are not in these buffers any more)
+  if ((rc = upload(ctx, ctx->ph_edges, edges_a, (size_t)n_a * sizeof(double)))) return rc;
+  if ((rc = ensure(ctx, ctx->ph_edges_b, (size_t)n_b * sizeof(double)))) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->ph_edges_b.p, edges_b, (size_t)n_b * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ensure(ctx, ctx->ph_counts, (words + 2) * sizeof(uint64_t)))) return rc;
+  HIPCHK(ctx, hipMemsetAsync(ctx->ph_counts.p, 0, (words + 2) * sizeof(uint64_t), ctx->stream));
+  PhBandEdges E;
+  std::memset(&E, 0, sizeof E);
+  std::memcpy(E.e, band_edges_nm, (size_t)n_band_edges * sizeof(double));
+  PhBandWl W;
+  std::memset(&W, 0, sizeof W);
+  W.mode = wl_mode;
+  W.n_edges = n_band_edges;
+  if (wl_mode == ODW_ROW_WL_SPECTRUM) {
+    W.spec_n = ctx->spec_n;
+    W.spec_mode = ctx->spec_mode;
+    W.spec_tab = (const double*)ctx->spec_tab.p;
+    W.seed = seed;
+  } else {
+    // (the table of the call: as many bytes as the explicit launch that made the rows uploaded itself)
+    if ((rc = ensure(ctx, ctx->ph_wl, n_wl * sizeof(double)))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->ph_wl.p, wl_nm, n_wl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    W.wl = (const double*)ctx->ph_wl.p;
+    W.first_ray = first_ray;
+    W.n_wl = n_wl;
+  }
+  const unsigned grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((m + 255) / 256, (uint64_t)ctx->n_cu * 8));
+  const PhbBinAccel* accel = nullptr;
+  PhbBinAccel A;
+  if (polar && !getenv("ODW_BIN_PLAIN")) {
+    ph_make_accel(A, polar, edges_a, n_a, edges_b, n_b);
+    if (A.az_on || A.r_on) {
+      if ((rc = ensure(ctx, ctx->ph_accel, sizeof A))) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(ctx->ph_accel.p, &A, sizeof A, hipMemcpyHostToDevice, ctx->stream));
+      accel = (const PhbBinAccel*)ctx->ph_accel.p;
+    }
+  }
+  unsigned long long* d_counts = (unsigned long long*)ctx->ph_counts.p;
+  unsigned long long* d_misc = d_counts + words;
+  const odw_hit* rows = (const odw_hit*)ctx->hits.p;
+  const uint32_t* sel = (const uint32_t*)ctx->sort_vals[1].p;
+  const bool in_lds = ph_bands_in_lds(nbins, n_band_edges);
+  const size_t lds = ph_bin_lds_bytes(n_a, n_b, in_lds ? plane_words : 0, polar != 0);
+#define ODW_PH_BANDS(L, P)                                                                                                        \
+  hipLaunchKernelGGL((ph_bin_bands_kernel<L, P>), dim3(grid), dim3(256), lds, ctx->stream, (const double*)ctx->ph_x.p,           \
+                     (const double*)ctx->ph_y.p, m, origin[0], origin[1], (int)polar, (const double*)ctx->ph_edges.p, (int)n_a,   \
+                     (const double*)ctx->ph_edges_b.p, (int)n_b, accel, d_counts, rows, sel, d_counts + plane_words, E, W, d_misc)
+  if (weighted) { if (in_lds) ODW_PH_BANDS(true, true); else ODW_PH_BANDS(false, true); }
+  else { if (in_lds) ODW_PH_BANDS(true, false); else ODW_PH_BANDS(false, false); }
+#undef ODW_PH_BANDS
+  HIPCHK(ctx, hipGetLastError());
+  uint64_t misc[2] = {0, 0};
+  HIPCHK(ctx, hipMemcpyAsync(misc, d_misc, sizeof misc, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));      // (wl_nm, the edges and A may go away)
+  if (misc[1]) {
+    char buf[240];
+    std::snprintf(buf, sizeof buf, "%s: %llu selected row(s) of rays outside the wavelength table (rays %llu .. %llu): no planes",
+                  who.c_str(), (unsigned long long)misc[1], (unsigned long long)first_ray, (unsigned long long)(first_ray + n_wl - 1));
+    return fail(ctx, ODW_ERR_INVALID, buf);
+  }
+  HIPCHK(ctx, hipMemcpyAsync(counts, d_counts, plane_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (weighted) HIPCHK(ctx, hipMemcpyAsync(power, d_counts + plane_words, plane_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  *n_no_band = misc[0];
+  return ODW_OK;
 }
 
 // max and min of point . normal per candidate normal (odw_plane_screen)

@@ -1,7 +1,7 @@
 """notebook-facing API mirroring the reference's jupyter_utils
 (jupyter_utils/__init__.py:11-16): FreecadDocument, RawFolder, Hits, Histogram"""
 from .hits import Hits
-from .histogram import Histogram
+from .histogram import BandHistograms, Histogram
 from .transforms import applyTransformation, applyTransformationWithoutTranslation
 
 

@@ -19,6 +19,56 @@ def _radius_bins(kwargs, radius, polar):
   kwargs['bins'] = bins
 
 
+BAND_MAX = 64        # ODW_BAND_MAX (include/odw_trace.h): bands of one call at most
+
+
+def bandEdges(bands):
+  """the band edges (nm) of `histogram(bands=)` as a float64 array: K + 1 of them, finite, > 0, strictly increasing,
+  1 <= K <= 64 -- the rule of the detector's up-front band planes (`Tracer.setDetector(det, bands=)`); ValueError otherwise"""
+  e = np.ascontiguousarray(bands, dtype=np.float64)
+  if e.ndim != 1 or len(e) < 2:
+    raise ValueError('bands: at least two edges (one band) are needed')
+  if len(e) - 1 > BAND_MAX:
+    raise ValueError(f'bands: {len(e) - 1} bands: at most {BAND_MAX} are taken')
+  if not np.all(np.isfinite(e)) or not np.all(e > 0) or not np.all(e[1:] > e[:-1]):
+    raise ValueError('bands: edges must be finite, positive and strictly increasing (nm)')
+  return e
+
+
+def bandOf(edges, wavelengths):
+  """int64 band of every wavelength among the edges, -1: none -- numpy.histogram's rule: e_b <= wl < e_(b+1), wl == e_K in
+  band K - 1, nothing outside [e_0, e_K] (NaN: none)"""
+  e = np.asarray(edges, dtype=np.float64)
+  wl = np.asarray(wavelengths, dtype=np.float64)
+  b = np.searchsorted(e, wl, 'right') - 1
+  b = np.where(wl == e[-1], len(e) - 2, b)
+  return np.where((wl >= e[0]) & (wl <= e[-1]), b, -1).astype(np.int64)
+
+
+class BandHistograms:
+  """`histogram(bands=edges)`: the hits of one plane split by wavelength band.
+  total   the `Histogram` of all hits -- what the call without `bands` returns
+  bands   K `Histogram`s, one per band, sharing plane, origin and bin edges with the total (with weights='powers' on
+          rows in HBM each carries `powerQuanta`)
+  edges   the K + 1 band edges (nm)
+  noBand  binned hits whose wavelength lies in no band: total count - sum of the bands' counts
+  len() = K, [b] = bands[b]"""
+
+  def __init__(self, total, bands, edges, noBand):
+    self.total, self.bands = total, list(bands)
+    self.edges = np.asarray(edges, dtype=np.float64)
+    self.noBand = int(noBand)
+
+  def __len__(self):
+    return len(self.bands)
+
+  def __getitem__(self, b):
+    return self.bands[b]
+
+  def __iter__(self):
+    return iter(self.bands)
+
+
 class Histogram:
   '''
   Class representing a 2D polar or cartesian histogram.

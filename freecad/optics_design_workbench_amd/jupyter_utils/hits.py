@@ -16,7 +16,7 @@ import warnings
 
 import numpy as np
 
-from .histogram import Histogram
+from .histogram import BandHistograms, Histogram, bandEdges, bandOf
 
 _UNIT = np.eye(3)
 
@@ -180,12 +180,37 @@ class Hits:
     xy = self.planeProject3dPoints(self.hits[key], planeNormal=planeNormal, xInPlaneVec=xInPlaneVec)
     return xy[:, 0], xy[:, 1], planeNormal, xInPlaneVec
 
-  def histogram(self, planeNormal=None, xInPlaneVec=None, key='points', **kwargs):
+  def histogram(self, planeNormal=None, xInPlaneVec=None, key='points', bands=None, **kwargs):
+    """bands: K + 1 wavelength edges (nm; not in the reference) -- the hits are also binned band by band, by their
+    `initWavelength` column (StoreHitInitWavelength), numpy.histogram's rule on the edges -> `BandHistograms`
+    (`.total` = the histogram without `bands`, `.bands[b]` over the same plane, origin and edges, `.noBand`)"""
+    if bands is not None:
+      edges = bandEdges(bands)
+      if 'initWavelength' not in self.hits:
+        raise KeyError('histogram(bands=): the hits carry no initWavelength column: simulate with StoreHitInitWavelength '
+                       'switched on in the active simulation settings')
     x, y, n, ex = self._flat(key, planeNormal, xInPlaneVec)
     # weights='powers': a string names a column of the hit dictionary (arrays pass through to numpy.histogram2d)
     if isinstance(kwargs.get('weights'), str):
       kwargs['weights'] = np.asarray(self.hits[kwargs['weights']])
-    return Histogram(x, y, planeNormal=n, xInPlaneVec=ex, **kwargs)
+    total = Histogram(x, y, planeNormal=n, xInPlaneVec=ex, **kwargs)
+    if bands is None:
+      return total
+    # the bands over the total's own edges: the coordinates Histogram.__init__ binned
+    a, b = x - total._origin[0], y - total._origin[1]
+    if total._binCoords == 'polar':
+      a, b = np.arctan2(a, b), np.sqrt(a**2 + b**2)
+    band = bandOf(edges, np.asarray(self.hits['initWavelength'], dtype=np.float64))
+    weights = kwargs.get('weights')
+    planes = []
+    for k in range(len(edges) - 1):
+      sel = band == k
+      h = np.histogram2d(a[sel], b[sel], bins=[total.binX, total.binY],
+                         weights=None if weights is None else np.asarray(weights)[sel])[0]
+      planes.append(Histogram.fromBinned(h, total.binX, total.binY, n, ex, total._origin, total._binCoords))
+    none = band < 0
+    noBand = int(np.histogram2d(a[none], b[none], bins=[total.binX, total.binY])[0].sum())
+    return BandHistograms(total, planes, edges, noBand)
 
   def plot(self, hueKey=None, hueLabel=None, planeNormal=None, xInPlaneVec=None, plotKey='points', **kwargs):
     """scatter plot of the hits in plane coordinates, optionally coloured by a metadata column

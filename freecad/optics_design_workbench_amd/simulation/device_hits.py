@@ -17,7 +17,7 @@ import numpy as np
 
 from .. import _native
 from ..jupyter_utils import hits as _hits
-from ..jupyter_utils.histogram import Histogram, _radius_bins
+from ..jupyter_utils.histogram import BandHistograms, Histogram, _radius_bins, bandEdges
 
 _THIN = 300
 
@@ -227,12 +227,43 @@ class DeviceHits:
   def _flattest_direction(self, cloud, angleTol):
     return flattestDirection(self._tr._lib, cloud, angleTol)
 
+  def _rowWavelengths(self, wavelengths):
+    """where `histogram(bands=)` takes the rows' wavelengths from: (ODW_ROW_WL_SPECTRUM, seed, 0, None) or
+    (ODW_ROW_WL_TABLE, 0, first ray, table).  wavelengths: {'seed': s} (the rows were drawn under the bound spectrum with
+    that seed), (first, array) (ray first + i had wavelength array[i]), or None: what the tracer noted about the launches
+    that made its hit list (`Tracer.hitProvenance`)"""
+    if wavelengths is None:
+      prov = self._tr.hitProvenance()
+      if prov is None:
+        raise ValueError('histogram(bands=): nothing is known about the wavelengths of these rows (no launch of this '
+                         'tracer recorded them, or they were loaded): pass wavelengths={"seed": s} or wavelengths=(first, array)')
+      if prov[0] in ('mixed', 'mono'):
+        raise ValueError(f'histogram(bands=): {prov[1]}: pass wavelengths={{"seed": s}} or wavelengths=(first, array) '
+                         'if the rows\' wavelengths are known all the same')
+      wavelengths = {'seed': prov[1]} if prov[0] == 'seed' else (prov[1], prov[2])
+    if isinstance(wavelengths, dict):
+      if set(wavelengths) != {'seed'}:
+        raise ValueError('wavelengths: {"seed": s} or (first, array)')
+      return _native.ROW_WL_SPECTRUM, int(wavelengths['seed']), 0, None
+    try:
+      first, table = wavelengths
+    except (TypeError, ValueError):
+      raise ValueError('wavelengths: {"seed": s} or (first, array)') from None
+    return _native.ROW_WL_TABLE, 0, int(first), np.ascontiguousarray(table, dtype=np.float64).reshape(-1)
+
   def histogram(self, planeNormal=None, xInPlaneVec=None, key='points', origin=None, radius=None,
-                binCoords='cartesian', **kwargs):
+                binCoords='cartesian', bands=None, wavelengths=None, **kwargs):
+    """bands: K + 1 wavelength edges (nm) -- the rows are also binned band by band (`odw_hits_bin_bands`: one pass over
+    the rows in HBM; plane, origin and bin edges are chosen exactly as without `bands`) -> `BandHistograms`.  The rows'
+    wavelengths come from their ray numbers: see `wavelengths` in `_rowWavelengths` (a table is uploaded per call, 8 bytes
+    per ray).  Array `weights` together with `bands`: TypeError, as other arguments the device route does not take."""
     if key not in ('points', 'directions'):
       raise ValueError('DeviceHits.histogram bins points or directions')
     if self._n == 0:
       raise ValueError('no hits to bin')
+    if bands is not None:
+      bands = bandEdges(bands)
+      wavelengths = self._rowWavelengths(wavelengths)
     if planeNormal is None or xInPlaneVec is None:
       planeNormal, xInPlaneVec = self.detectPlaneNormal(planeNormal=planeNormal, xInPlaneVec=xInPlaneVec)
     ex = np.asarray(xInPlaneVec, dtype=np.float64)
@@ -266,6 +297,8 @@ class DeviceHits:
     if kwargs:
       raise TypeError(f'DeviceHits.histogram: unsupported arguments {sorted(kwargs)}')
     edges = self._edges(bins, polar, origin)
+    if bands is not None:
+      return self._bandHistograms(bands, wavelengths, weighted, polar, origin, edges, planeNormal, xInPlaneVec)
     counts = np.zeros((len(edges[0]) - 1) * (len(edges[1]) - 1), dtype=np.uint64)
     if weighted:
       pu = C.POINTER(C.c_uint64)
@@ -283,6 +316,35 @@ class DeviceHits:
     hist = counts.reshape(len(edges[0]) - 1, len(edges[1]) - 1).astype(np.float64)
     return Histogram.fromBinned(hist, edges[0], edges[1], planeNormal, xInPlaneVec, origin,
                                 'polar' if polar else 'cartesian')
+
+  def _bandHistograms(self, bands, wavelengths, weighted, polar, origin, edges, planeNormal, xInPlaneVec):
+    """one `odw_hits_bin_bands` call on the projected rows -> BandHistograms (planes 0 .. K-1 the bands, plane K the total)"""
+    tr = self._tr
+    pd, pu = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+    mode, seed, first, table = wavelengths
+    k = len(bands) - 1
+    shape = (len(edges[0]) - 1, len(edges[1]) - 1)
+    counts = np.zeros((k + 1) * shape[0] * shape[1], dtype=np.uint64)
+    quanta = np.zeros_like(counts) if weighted else None
+    none = C.c_uint64(0)
+    f = tr._lib.odw_hits_bin_bands
+    f.argtypes = [C.c_void_p, C.c_int32, pd, pd, C.c_int32, pd, C.c_int32, pd, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64,
+                  C.c_uint64, pd, pu, pu, pu]
+    tr._chk(f(tr._ctx, 1 if polar else 0, origin.ctypes.data_as(pd), edges[0].ctypes.data_as(pd), len(edges[0]),
+              edges[1].ctypes.data_as(pd), len(edges[1]), bands.ctypes.data_as(pd), len(bands), mode, seed, first,
+              0 if table is None else len(table), None if table is None else table.ctypes.data_as(pd),
+              counts.ctypes.data_as(pu), None if quanta is None else quanta.ctypes.data_as(pu), C.byref(none)),
+            'odw_hits_bin_bands')
+    coords = 'polar' if polar else 'cartesian'
+    counts = counts.reshape((k + 1,) + shape)
+    if weighted:
+      quanta = quanta.reshape((k + 1,) + shape)
+      made = [Histogram.fromBinned(q.astype(np.float64) * 2.0 ** -_native.POWER_QUANTUM_BITS, edges[0], edges[1], planeNormal,
+                                   xInPlaneVec, origin, coords, powerQuanta=q) for q in quanta]
+    else:
+      made = [Histogram.fromBinned(c.astype(np.float64), edges[0], edges[1], planeNormal, xInPlaneVec, origin, coords)
+              for c in counts]
+    return BandHistograms(made[k], made[:k], bands, int(none.value))
 
   def _edges(self, bins, polar, origin):
     """numpy.histogram2d's reading of `bins` (numpy/lib/_twodim_base_impl.py, _histograms_impl.py):

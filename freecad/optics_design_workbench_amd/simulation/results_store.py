@@ -424,11 +424,18 @@ class RunHits(Hits):
 
   def histogram(self, planeNormal=None, xInPlaneVec=None, key='points', **kwargs):
     dev = self._device() if key in ('points', 'directions') else None
+    # bands=: in HBM where the run's launches left a way back to the rows' wavelengths (one seed under a spectrum: every
+    # spectral run), else from the files' initWavelength column -- the host mirror
+    if dev is not None and kwargs.get('bands') is not None and kwargs.get('wavelengths') is None:
+      prov = dev._tr.hitProvenance()
+      if prov is None or prov[0] not in ('seed', 'table'):
+        dev = None
     if dev is not None and len(dev):
       try:
         return dev.histogram(planeNormal=planeNormal, xInPlaneVec=xInPlaneVec, key=key, **kwargs)
       except TypeError:                       # (an argument the device route does not take: the arrays, numpy)
         pass
+    kwargs.pop('wavelengths', None)           # (the device route's: the files carry the wavelengths themselves)
     return super().histogram(planeNormal=planeNormal, xInPlaneVec=xInPlaneVec, key=key, **kwargs)
 
   def deviceHits(self):

@@ -118,6 +118,9 @@ def releasePinnedMemory(keep=0):
   _POOL.trim(keep)
 
 
+_MONO = ('mono', 'the rows come from monochromatic launches (no spectrum bound, no wavelengths given)')
+
+
 class Tracer:
 
   def __init__(self, device=0, referenceStrict=None):
@@ -140,6 +143,9 @@ class Tracer:
     self._power = False
     self._bands = None
     self._keep = {}
+    self._spectral = False        # a spectrum is bound (setSpectrum): trace() is a spectral launch
+    self._prov = self._archiveProv = None
+    self._archiveOn = self._batchOn = False
     # ODW_COMPILE=structure: every tracer of the process compiles its scenes (test campaigns)
     if os.environ.get('ODW_COMPILE'):
       self.compileScene(os.environ['ODW_COMPILE'])
@@ -271,6 +277,7 @@ class Tracer:
     pd = C.POINTER(C.c_double)
     if spectrum is None:
       self._chk(self._lib.odw_set_spectrum(self._ctx, C.c_int32(0), C.c_int32(0), None, None), 'odw_set_spectrum')
+      self._spectral = False
       return
     w = np.ascontiguousarray(spectrum.wavelengths, dtype=np.float64)
     c = np.ascontiguousarray(spectrum.cdf, dtype=np.float64)
@@ -278,6 +285,7 @@ class Tracer:
       raise ValueError('Spectrum: wavelengths and cdf differ in shape')
     self._chk(self._lib.odw_set_spectrum(self._ctx, C.c_int32(_native.SPECTRUM_MODES[spectrum.mode]), C.c_int32(len(w)),
                                          w.ctypes.data_as(pd), c.ctypes.data_as(pd)), 'odw_set_spectrum')
+    self._spectral = True
 
   def rayWavelengths(self, rays, seed):
     """the wavelengths (nm) the bound spectrum gives the ray indices `rays` under `seed` (`odw_ray_wavelengths`)"""
@@ -364,6 +372,7 @@ class Tracer:
       d, keep = _native.source_desc(source)
       self._chk(self._lib.odw_upload_source(self._ctx, C.byref(d)), 'odw_upload_source')
     self.source = source
+    self._spectral = False
     # (the upload has cleared the previous source's spectrum: what this one carries, if anything)
     if getattr(source, 'spectrum', None) is not None:
       if hasattr(source, 'face_prim'):
@@ -447,6 +456,42 @@ class Tracer:
     self._chk(self._lib.odw_trace(self._ctx, C.c_uint64(int(first)), C.c_uint64(int(n)), C.c_uint64(int(seed)),
                                   C.c_uint32(self._flags(record_hits, histogram, record_segments))),
               'odw_trace')
+    if record_hits:
+      self._noteLaunch(('seed', int(seed)) if self._spectral else _MONO)
+
+  # -- where the wavelengths of the hit list's rows come from (DeviceHits.histogram(bands=)) -------------------------
+  @staticmethod
+  def _mergeProvenance(have, new):
+    """the provenance of a hit list after rows of provenance `new` joined rows of provenance `have` (None: no rows)"""
+    if have is None or new is None:
+      return new if have is None else ('mixed', 'rows of unknown wavelengths joined the hit list')
+    if have[0] == 'mixed':
+      return have
+    if new[0] == 'mixed':
+      return new
+    if 'mono' in (have[0], new[0]):
+      return have if have[0] == new[0] else ('mixed', 'monochromatic and spectral launches share the hit list')
+    if have[0] != new[0]:
+      return ('mixed', 'launches under a spectrum and launches with explicit wavelengths share the hit list')
+    if new[0] == 'seed':
+      return have if have[1] == new[1] else ('mixed', f'launches under two seeds ({have[1]} and {new[1]}) share the hit list')
+    if new[1] != have[1] + len(have[2]):
+      return ('mixed', f'the wavelength tables of the launches are not contiguous (rays {have[1]} .. {have[1] + len(have[2]) - 1}, '
+                       f'then from {new[1]})')
+    return ('table', have[1], np.concatenate([have[2], new[2]]))
+
+  def _noteLaunch(self, new):
+    self._archiveOn = self._batchOn = False       # (a launch writes the tracer's own list)
+    self._prov = self._mergeProvenance(self._prov, new)
+
+  def hitProvenance(self):
+    """what is known about the wavelengths of the rows `deviceHits()` sees: None (nothing: no recording launch, or rows put
+    back with loadHits), ('seed', s) -- every launch was a trace() with seed s under a bound spectrum --, ('table', first,
+    wavelengths) -- traceRays(wavelengths=) launches whose ray ranges follow each other --, ('mono', reason), or
+    ('mixed', reason) when the launches do not share one such description"""
+    if self._batchOn:
+      return ('mono', 'the rows come from a batch launch (batches carry one wavelength)')
+    return self._archiveProv if self._archiveOn else self._prov
 
   def traceRays(self, origins, directions, powers=None, first=0, record_hits=True, histogram=True,
                 record_segments=False, wavelengths=None):
@@ -465,11 +510,15 @@ class Tracer:
           self._ctx, C.c_uint64(int(first)), C.c_uint64(len(o)), o.ctypes.data_as(pd), d.ctypes.data_as(pd),
           p.ctypes.data_as(pd) if p is not None else None, w.ctypes.data_as(pd),
           C.c_uint32(self._flags(record_hits, histogram, record_segments))), 'odw_trace_rays_spectral')
+      if record_hits:
+        self._noteLaunch(('table', int(first), w.copy()))
       return
     self._chk(self._lib.odw_trace_rays(
         self._ctx, C.c_uint64(int(first)), C.c_uint64(len(o)), o.ctypes.data_as(pd), d.ctypes.data_as(pd),
         p.ctypes.data_as(pd) if p is not None else None,
         C.c_uint32(self._flags(record_hits, histogram, record_segments))), 'odw_trace_rays')
+    if record_hits:
+      self._noteLaunch(_MONO)
 
   # -- batches: scenes of one structure in one launch -------------------------------
   def setSceneBatch(self, scenes):
@@ -520,6 +569,7 @@ class Tracer:
     """the rows of scene k of the last traceBatch become the tracer's hit list (hits(), hitCount(), deviceHits(),
     hitColumns() ...); None: back to the tracer's own list"""
     self._chk(self._lib.odw_batch_select(self._ctx, C.c_int32(-1 if k is None else int(k))), 'odw_batch_select')
+    self._batchOn, self._archiveOn = k is not None, False
     if k is not None:
       self.scene = self.batchScenes[int(k)]
 
@@ -532,14 +582,18 @@ class Tracer:
     f = self._lib.odw_archive_append
     f.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
     self._chk(f(self._ctx, src._ctx, C.byref(n)), 'odw_archive_append')
+    # (the rows' provenance travels with them; so does the source's spectrum, inside odw_archive_append)
+    self._archiveProv = self._mergeProvenance(self._archiveProv, src._prov)
     return int(n.value)
 
   def archiveSelect(self, on=True):
     """the archive becomes the tracer's hit list (hits(), hitCount(), deviceHits() ...); False: back to its own list"""
     self._chk(self._lib.odw_archive_select(self._ctx, C.c_int32(1 if on else 0)), 'odw_archive_select')
+    self._archiveOn, self._batchOn = bool(on), False
 
   def archiveReset(self):
     self._chk(self._lib.odw_archive_reset(self._ctx), 'odw_archive_reset')
+    self._archiveProv, self._archiveOn = None, False
 
   def batchRows(self):
     """(rows recorded per scene, slots asked for per scene) of the last traceBatch"""
@@ -560,11 +614,13 @@ class Tracer:
 
   def reset(self):
     self._chk(self._lib.odw_reset_results(self._ctx), 'odw_reset_results')
+    self._prov = None
 
   def resetHits(self):
     """recycle the hit list (the reference's periodic flush,
     results_store.py:455-457); counters and histogram keep accumulating"""
     self._chk(self._lib.odw_reset_hits(self._ctx), 'odw_reset_hits')
+    self._prov = None
 
   # -- results --------------------------------------------------------------
   def counters(self):
@@ -695,6 +751,7 @@ class Tracer:
       rows['tag'] = (np.arange(n, dtype=np.uint64) | (np.uint64(int(group)) << np.uint64(48))
                      | ((ent != 0).astype(np.uint64) << np.uint64(63)))
     self._chk(self._lib.odw_load_hits(self._ctx, rows.ctypes.data_as(C.c_void_p), C.c_uint64(len(rows))), 'odw_load_hits')
+    self._prov, self._archiveOn, self._batchOn = None, False, False      # (rows of unknown wavelengths: histogram(bands=, wavelengths=))
     return self.deviceHits()
 
   def resetSegments(self):

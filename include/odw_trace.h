@@ -802,6 +802,37 @@ int odw_hits_bin(odw_ctx* ctx, int32_t polar, const double* origin, const double
  * power[same index].  Both planes are integer sums.                                         */
 int odw_hits_bin_power(odw_ctx* ctx, int32_t polar, const double* origin, const double* edges_a, int32_t n_a,
                        const double* edges_b, int32_t n_b, uint64_t* counts, uint64_t* power);
+/* odw_hits_bin / odw_hits_bin_power, split by wavelength band; replaces fetching the rows and
+ * numpy.histogram2d per band of Hits.histogram (hits.py:176-193) on a spectral run -- the
+ * reference has no band selection; the band rule is odw_set_detector_bands'.  Same selection,
+ * projection, edges and bin rule as odw_hits_bin (the polar tables included).
+ * counts[(K + 1) * nbins], K = n_band_edges - 1: planes 0 .. K-1 the bands (numpy.histogram's
+ * rule on band_edges_nm: finite, > 0, strictly increasing, K <= ODW_BAND_MAX), plane K the total
+ * plane = odw_hits_bin's; power: NULL or the same shape in quanta (odw_hits_bin_power's plane and
+ * its split); *n_no_band = binned rows whose wavelength lies in no band (total - sum of bands).
+ * A row's wavelength comes from its ray number (ODW_HIT_RAY of its tag):
+ *   ODW_ROW_WL_SPECTRUM  the draw of odw_trace under the bound spectrum (odw_set_spectrum; an
+ *                        archive takes the spectrum of the context it was appended from) for
+ *                        (seed, ray); first_ray, n_wl, wl_nm are ignored;
+ *   ODW_ROW_WL_TABLE     wl_nm[ray - first_ray], the table odw_trace_rays_spectral was given
+ *                        (> 0, finite).  The table is uploaded per call: as many bytes as that
+ *                        launch uploaded itself.  A selected row whose ray lies outside
+ *                        [first_ray, first_ray + n_wl) refuses the call (the message names the
+ *                        count) and no planes are delivered.
+ * Count planes are kept in LDS where (K + 1) * nbins <= 8192 words, else added by atomics in
+ * HBM (odw_hits_bin_bands_info; ODW_BIN_BANDS_HBM=1 forces the latter); power planes always
+ * by atomics in HBM.  Refused: no bound spectrum / no table, no projection yet, an output of
+ * 2^31 words or more.                                                                        */
+enum { ODW_ROW_WL_SPECTRUM = 1, ODW_ROW_WL_TABLE = 2 };
+int odw_hits_bin_bands(odw_ctx* ctx, int32_t polar, const double* origin,
+                       const double* edges_a, int32_t n_a, const double* edges_b, int32_t n_b,
+                       const double* band_edges_nm, int32_t n_band_edges,
+                       int32_t wl_mode, uint64_t seed, uint64_t first_ray, uint64_t n_wl, const double* wl_nm,
+                       uint64_t* counts, uint64_t* power, uint64_t* n_no_band);
+/* context-free, no device: which route a call of these sizes takes (1: planes in LDS, 0: HBM
+ * atomics); replaces nothing -- what the tests ask to know both routes are covered            */
+int odw_hits_bin_bands_info(int32_t n_a, int32_t n_b, int32_t n_band_edges, int32_t power,
+                            int32_t* counts_in_lds, int32_t* power_in_lds);
 /* mean[3] and variance[3] (about the mean) of the selected rows' points     */
 int odw_hits_moments(odw_ctx* ctx, double* mean, double* var);
 /* The screen of the plane search of `Hits.detectPlaneNormal` (jupyter_utils/hits.py:108-137: the direction along
